@@ -14,7 +14,18 @@ after the device-pointer split-phase calls, and G and the sums come back D2H wit
 
 ``value`` = (number of 128-trajectory shard evaluations completed by all ranks) / time, i.e.
 ``n_gpus * steps / seconds`` over exactly ``--steps`` steps; the median over the per-step
-times and the device-resident loop of round 1 are reported beside it as secondary keys.
+times is reported beside it as a secondary key.
+
+A plain run sets up, warms up, times the steps and prints the line; the phase times, roofline and
+phase-B figures in it come from the timed steps themselves (HIP events, the kernels' own work
+counters) and from the committed PMC summaries.  Everything that takes runs of its own is behind
+``--full``: the device-resident loop of round 1 (and ``J`` at the unperturbed pulses), the
+matrix-free propagator's line, the timed CPU baseline with its parity gate, and the latency of the
+gradient all-reduce (N > 1).
+
+``--dump-outputs DIR`` writes what the last timed step returned to its caller as ``DIR/<name>.npy``
+(float64): ``J`` and ``G``, and ``tau_re`` / ``tau_im`` (one GPU) or the all-reduced ``sums``
+(N > 1, rank 0).  The inputs depend only on the arguments, so two builds compare output for output.
 
 Prints ONE JSON line (rank 0).
 """
@@ -171,7 +182,14 @@ def main():
     ap.add_argument("--dt", type=float, default=None,
                     help="time step of the synthetic grid instead of 1.0 (secondary lines: the cells leave the range of the "
                          "four-product exponential at dt ~ 1.2 and need a squaring beyond dt ~ 1.7)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the measurements that take runs of their own: device-resident loop (and J), matrix-free "
+                         "line, CPU baseline, all-reduce latency")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write J, G and tau (N > 1: J, G and the sums) of the last timed step as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     rc = launch_ranks_if_needed(args)
     if rc is not None:
@@ -274,10 +292,11 @@ def main():
     sync()
     h.reset_timings()
     per_step = []
+    last = None
     t0 = time.perf_counter()
     for i in range(args.steps):
         ts = time.perf_counter()
-        boundary_step(args.warmup + i)
+        last = boundary_step(args.warmup + i)
         per_step.append(time.perf_counter() - ts)
     sync()
     elapsed = time.perf_counter() - t0
@@ -287,19 +306,34 @@ def main():
         elapsed = float(tt.item())
     tm = h.timings()   # HIP-event averages over the timed region, recorded on the kernel stream
     work = h.work()
-    # secondary: the device-resident loop of round 1 (pulses already in HBM, no per-call D2H, one check at the end)
-    x.copy_(torch.from_numpy(pr["pulsevals"]))
-    ev.eval_device(stream)
-    sync()
-    t1 = time.perf_counter()
-    for _ in range(args.steps):
+    if args.dump_outputs and rank == 0:
+        # what the caller of the timed path received from the last step, before anything else touches the buffers
+        from grape_jl_amd.sharded import functional_value
+        if dist is None:
+            J_last, G_last, tau_last = last
+            dump = {"J": np.array([J_last]), "G": G_last, "tau_re": tau_last.real, "tau_im": tau_last.imag}
+        else:
+            sums = sums_host.numpy().copy()
+            J_last = functional_value(ev.functional, sums.tolist(), ev.K_total, getattr(h, "lambda_b", 0.0))
+            dump = {"J": np.array([J_last]), "G": G_host.numpy().copy(), "sums": sums}
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, arr in dump.items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), np.ascontiguousarray(arr, dtype=np.float64))
+    J, resident_elapsed = None, None
+    if args.full:
+        # secondary: the device-resident loop of round 1 (pulses already in HBM, no per-call D2H, one check at the end)
+        x.copy_(torch.from_numpy(pr["pulsevals"]))
         ev.eval_device(stream)
-    sync()
-    resident_elapsed = time.perf_counter() - t1
-    h.check(stream)
-    J = ev.J_device()
+        sync()
+        t1 = time.perf_counter()
+        for _ in range(args.steps):
+            ev.eval_device(stream)
+        sync()
+        resident_elapsed = time.perf_counter() - t1
+        h.check(stream)
+        J = ev.J_device()
     allreduce_us = None
-    if dist is not None and world > 1:
+    if args.full and dist is not None and world > 1:
         # latency of the gradient all-reduce (L*N_T doubles): the collective is latency-bound,
         # its bandwidth over xGMI is irrelevant at 16 KB
         sync()
@@ -429,12 +463,10 @@ def main():
                         "grape_check inside the timed region" if dist is None else
                         "per step: fresh pulsevals H2D, grape_forward_device, RCCL all-reduce (8 doubles), "
                         "grape_backward_device, RCCL all-reduce (G), D2H of G and the sums, grape_check",
-            "device_resident_loop": {"evals_per_s": world * args.steps / resident_elapsed,
-                                     "ms_per_step": resident_elapsed / args.steps * 1e3,
-                                     "note": "secondary: pulses resident in HBM, no per-call D2H (round-1 headline)"},
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "vs_baseline_note": "BASELINE.md holds no published number for this metric (the reference publishes none); the "
-                                "in-run CPU baseline and speedup_vs_cpu_baseline are below",
+                                + ("in-run CPU baseline and speedup_vs_cpu_baseline are below" if args.full else
+                                   "in-run CPU baseline and speedup_vs_cpu_baseline are reported with --full"),
             "dtype": "f64", "data": "synthetic",
             "config": {"workload": f"{args.config}: N={N}, L={L} controls, N_T={N_T} time steps, "
                                    f"{K_local} trajectories per GPU ({K_total} total), J_T_sm, ExpProp"
@@ -495,9 +527,13 @@ def main():
                                         3: "deriv3g_asm (general operators, csrc/asm/gen_d3s.py)",
                                         4: "deriv4_asm (blocked path, csrc/asm/gen_d4.py)"}.get(int(work.get("asm_deriv_kernel", 0)), "?"),
                              "blocked_products": "lg_gemm_asm (csrc/asm/gen_lg.py)" if work.get("asm_blocked_products", 0) else None},
-            "J": J,
         }
-        if not args.no_matrix_free and N <= 256 and world == 1:
+        if args.full:
+            res["device_resident_loop"] = {"evals_per_s": world * args.steps / resident_elapsed,
+                                           "ms_per_step": resident_elapsed / args.steps * 1e3,
+                                           "note": "secondary: pulses resident in HBM, no per-call D2H (round-1 headline)"}
+            res["J"] = J
+        if args.full and not args.no_matrix_free and N <= 256 and world == 1:
             # secondary line, NOT `value`: the same evaluation with prop_method = GRAPE_PROP_SERIES (matrix-free
             # polynomial propagator, the role of the reference's Cheby/Newton methods), rank 0's shard only
             hm = g.GrapeHip(pr["H0"], pr["Hc"], pr["tlist"], pr["psi0"], pr["target"], pr["weights"],
@@ -519,7 +555,7 @@ def main():
                                   "note": "host-pointer grape_eval (16 KB H2D + D2H per call included); secondary, "
                                           "not the headline metric"}
             hm.close()
-        if not args.no_cpu_baseline and world == 1:   # the CPU baseline is timed on rank 0 of the N = 1 run only
+        if args.full and not args.no_cpu_baseline and world == 1:   # timed on rank 0 of the N = 1 run only
             def hip_sample(sl, tl, xs):
                 hs = g.GrapeHip(pr["H0"][sl], pr["Hc"], tl, pr["psi0"][sl], pr["target"][sl], pr["weights"][sl],
                                 functional=g.J_T_SM, device=dev.index)

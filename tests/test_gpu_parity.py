@@ -607,7 +607,8 @@ def test_bench_contract_two_rank_rehearsal(g):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env["GRAPE_BENCH_REHEARSAL"] = "1"
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"]
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full",
+           "--no-cpu-baseline"]
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=root, env=env)
     assert res.returncode == 0, res.stderr[-2000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.strip()]
@@ -643,7 +644,7 @@ def test_bench_contract_four_rank_rehearsal_of_config_c4(g):
     env = dict(os.environ, GRAPE_BENCH_REHEARSAL="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "4", "--master-addr",
            "127.0.0.1", "--master-port", "29547", os.path.join(root, "bench.py"), "--gpus", "4", "--config", "C4",
-           "--steps", "2", "--warmup", "1", "--no-cpu-baseline"]
+           "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline"]
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=root, env=env)
     assert res.returncode == 0, res.stderr[-3000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.strip()]
@@ -658,6 +659,52 @@ def test_bench_contract_four_rank_rehearsal_of_config_c4(g):
     with g.GrapeHip(cat("H0"), prs[0]["Hc"], prs[0]["tlist"], cat("psi0"), cat("target"), cat("weights")) as h:
         J1, _, _ = h.eval(prs[0]["pulsevals"])
     assert abs(d["J"] - J1) <= 1e-14, (d["J"], J1)
+
+
+def test_bench_plain_run_and_dump_outputs(g, tmp_path):
+    """A plain `bench.py --dump-outputs DIR` (config C2, one GPU): one JSON line with the headline keys and without what
+    --full adds; DIR holds J, G, tau_re and tau_im as float64 -- what grape_eval returned for the pulses of the last timed
+    step (bench.py's seeded perturbation, regenerated here) -- and a second run with the same arguments writes the same."""
+    import json
+    import subprocess
+    import sys
+    from grape_jl_amd import synth
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    steps, warmup = 3, 2
+    dumps = []
+    for run in ("a", "b"):
+        out_dir = tmp_path / run
+        cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--config", "C2", "--steps", str(steps),
+               "--warmup", str(warmup), "--dump-outputs", str(out_dir)]
+        res = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=root, env=env)
+        assert res.returncode == 0, res.stderr[-2000:]
+        lines = [ln for ln in res.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1, res.stdout[:2000]
+        d = json.loads(lines[0])
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "roofline"):
+            assert key in d
+        assert d["steps"] == steps and d["warmup"] == warmup and d["dtype"] == "f64" and d["higher_is_better"] is True
+        assert abs(d["value"] - steps / (d["ms_per_step"] * steps * 1e-3)) <= 1e-6 * d["value"]
+        for key in ("device_resident_loop", "J", "matrix_free", "cpu_baseline", "speedup_vs_cpu_baseline"):
+            assert key not in d
+        arrs = {name: np.load(out_dir / f"{name}.npy") for name in ("J", "G", "tau_re", "tau_im")}
+        assert all(a.dtype == np.float64 for a in arrs.values())
+        dumps.append(arrs)
+    pr = synth.make_config("C2")
+    N, L, N_T, K = synth.CONFIGS["C2"]
+    rng = np.random.default_rng(12345)
+    xs = [pr["pulsevals"] + 1e-3 * (rng.random(L * N_T) - 0.5) for _ in range(warmup + steps)]
+    with g.GrapeHip(pr["H0"], pr["Hc"], pr["tlist"], pr["psi0"], pr["target"], pr["weights"], functional=g.J_T_SM,
+                    gradient_method=g.GRAD_GRADGEN, K_total=K) as h:
+        J, G, tau = h.eval(xs[-1])
+    for arrs in dumps:
+        assert arrs["J"].shape == (1,) and arrs["G"].shape == (L * N_T,) and arrs["tau_re"].shape == (K,)
+        assert abs(arrs["J"][0] - J) <= 1e-14
+        assert np.abs(arrs["G"] - G).max() <= 1e-12 * max(np.abs(G).max(), 1e-3)
+        assert np.abs(arrs["tau_re"] + 1j * arrs["tau_im"] - tau).max() <= 1e-14
+    for name in dumps[0]:
+        assert np.array_equal(dumps[0][name], dumps[1][name]), name
 
 
 @pytest.mark.parametrize("N,herm", [(33, True), (40, False), (48, True)])

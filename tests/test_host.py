@@ -250,3 +250,14 @@ def test_bench_gpus_flag_and_world_size_must_agree(tmp_path):
     res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--steps", "1"], capture_output=True,
                          text=True, timeout=60, env=env)
     assert res.returncode == 2 and not res.stdout.strip() and "WORLD_SIZE=4" in res.stderr
+
+
+def test_bench_refuses_a_run_without_timed_steps():
+    """bench.py --steps 0 is refused before torch is imported (no GPU needed): ms_per_step would have no steps to divide"""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "0"], capture_output=True,
+                         text=True, timeout=60, env=env)
+    assert res.returncode == 2 and not res.stdout.strip() and "--steps" in res.stderr
