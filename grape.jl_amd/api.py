@@ -21,7 +21,7 @@ _LIBNAME = "libgrape_hip.so"
 J_T_SM, J_T_SS, J_T_RE = 0, 1, 2
 GRAD_GRADGEN, GRAD_TAYLOR = 0, 1
 PROP_EXP, PROP_SERIES = 0, 1
-ABI_VERSION = 6
+ABI_VERSION = 7
 
 STATUS = {0: "GRAPE_OK", -1: "GRAPE_ERR_INVALID", -2: "GRAPE_ERR_HIP", -3: "GRAPE_ERR_CHI_NORM",
           -4: "GRAPE_ERR_SINGULAR", -5: "GRAPE_ERR_TAYLOR", -6: "GRAPE_ERR_NO_CONTROLS", -7: "GRAPE_ERR_AGAIN",
@@ -32,7 +32,8 @@ EXPORTS = ["grape_create", "grape_destroy", "grape_eval", "grape_forward", "grap
            "grape_forward_device", "grape_backward_device", "grape_check", "grape_get_propagator",
            "grape_get_tau_grads", "grape_get_storage", "grape_get_timings", "grape_reset_timings", "grape_get_work",
            "grape_last_error", "grape_abi_version", "grape_set_fused_sweeps", "grape_get_sums", "grape_backward_xi",
-           "grape_get_final_states", "grape_backward_chi"]
+           "grape_get_final_states", "grape_backward_chi",
+           "grape_get_time_gradient", "grape_set_tlist"]
 
 
 class GrapeHipError(RuntimeError):
@@ -96,7 +97,7 @@ def build_asm(verbose: bool = False, workdir: str | None = None) -> str:
 def _sources():
     srcs = [os.path.join(_CSRC, f) for f in ("grape_hip.hip", "grape_t18.hip", "grape_kernels.hip.h", "grape_large.hip.h",
                                              "grape_series.hip.h", "grape_cheby.hip.h", "grape_t18.hip.h", "grape_t18_coeffs.h",
-                                             "grape_deriv3.hip.h", os.path.join("asm", "gen_t16.py"), os.path.join("asm", "gen_t16p.py"), os.path.join("asm", "gen_t18g.py"), os.path.join("asm", "gen_t18gp.py"), os.path.join("asm", "gen_d3.py"), os.path.join("asm", "gen_d3s.py"), os.path.join("asm", "gen_lg.py"), os.path.join("asm", "gen_d4.py"), os.path.join("asm", "gcn.py"))]
+                                             "grape_deriv3.hip.h", "grape_timegrad.hip.h", os.path.join("asm", "gen_t16.py"), os.path.join("asm", "gen_t16p.py"), os.path.join("asm", "gen_t18g.py"), os.path.join("asm", "gen_t18gp.py"), os.path.join("asm", "gen_d3.py"), os.path.join("asm", "gen_d3s.py"), os.path.join("asm", "gen_lg.py"), os.path.join("asm", "gen_d4.py"), os.path.join("asm", "gcn.py"))]
     return srcs, os.path.join(_HERE, "..", "include", "grape_hip.h")
 
 
@@ -201,6 +202,8 @@ def load_library():
     lib.grape_get_final_states.argtypes = [vp, vp]
     lib.grape_backward_chi.argtypes = [vp, vp, vp]
     lib.grape_backward_xi.argtypes = [vp, vp, vp, vp, C.c_double, vp]
+    lib.grape_get_time_gradient.argtypes = [vp, vp]
+    lib.grape_set_tlist.argtypes = [vp, vp]
     lib.grape_last_error.argtypes = [vp]
     lib.grape_last_error.restype = C.c_char_p
     lib.grape_abi_version.restype = ip
@@ -387,6 +390,22 @@ class GrapeHip:
             fptr = f.ctypes.data
         self._chk(self._lib.grape_backward_xi(self._h, fptr, cptr, xi.ctypes.data, float(lambda_b), G.ctypes.data))
         return G
+
+    def time_gradient(self):
+        """dJ/d(dt_n) of the last evaluation with a gradient, [N_T] (grape_get_time_gradient): the partial sum over this
+        handle's trajectories for a split-phase shard.  Taken at fixed per-interval pulse and shape values; after
+        ``backward_xi`` the explicit weight term of the caller's running cost is the caller's to add."""
+        out = np.empty(self.N_T)
+        self._chk(self._lib.grape_get_time_gradient(self._h, out.ctypes.data))
+        return out
+
+    def set_tlist(self, tlist):
+        """Replace the time grid of this handle (same N_T; grape_set_tlist).  A refused grid leaves the handle unchanged."""
+        t = np.ascontiguousarray(tlist, dtype=np.float64)
+        if t.shape != (self.N_T + 1,):
+            raise ValueError(f"tlist must have N_T + 1 = {self.N_T + 1} points, got {t.shape}")
+        self._chk(self._lib.grape_set_tlist(self._h, t.ctypes.data))
+        self._tlist = t
 
     # -- device-pointer API (torch tensors on the handle's device) -----------------------------
     def forward_device(self, d_pulsevals_ptr, d_out_ptr, stream=0):

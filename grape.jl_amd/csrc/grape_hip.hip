@@ -13,6 +13,7 @@
 #include "grape_large.hip.h"
 #include "grape_series.hip.h"
 #include "grape_cheby.hip.h"
+#include "grape_timegrad.hip.h"
 
 #include <rccl/rccl.h>
 #include <dlfcn.h>
@@ -284,6 +285,14 @@ struct grape_handle {
     bool graph_fuse_on = true;     // the setting the graph was captured with
     bool graph_bw_unit = false, graph_z_valid = false, graph_credit = false;   // host-side state the captured calls leave behind
     long n_eval = 0;               // grape_eval calls on the single-wait path
+    // ABI v7, grape_get_time_gradient: what the stored states of the last evaluation can give.  0: no evaluation (or the
+    // last one failed, or the grid changed since), 1: functional only, 2: forward done, backward pending, 3: complete
+    int tg_state = 0;
+    bool tg_unit = false;          // ... d_bw holds the unit backward states (factor z_k instead of rho_k)
+    bool tg_xi_user = false;       // ... the running cost was the caller's (grape_backward_xi): no explicit weight term
+    bool graph_tg_unit = false;    // tg_unit of the captured evaluation
+    double2 *d_tq = nullptr;       // [K][N_T] per-trajectory terms of dJ/d(dt_n) (allocated on first use)
+    double *d_dJdt = nullptr;      // [N_T]
 };
 
 namespace {
@@ -1506,7 +1515,7 @@ void grape_destroy(grape_handle *h) {
     if (h->lg_ev_join) hipEventDestroy(h->lg_ev_join);
     void *bufs[] = {h->d_celldeg, h->d_xcc_sw, h->d_scanF, h->d_scan_fw, h->d_scan_bw, h->d_dte, h->d_normpart, h->d_normpart2, h->d_dinv2, h->d_scell2, h->d_colpart2, h->d_smax2, h->d_xch, h->d_xcc, h->d_batchflag, h->d_chi_in, h->d_n1, h->d_gpark, h->d_morder, h->d_inv_tnorm, h->d_ones, h->d_z, h->d_rb, h->d_cls, h->d_rep, h->d_coop, h->d_Dt, h->d_xi, h->d_wq, h->d_gb, h->d_cellflag, h->d_celllist, h->d_gram, h->d_Sf, h->d_dinv, h->d_scell, h->d_colpart, h->d_wgtab, h->d_prog, h->d_splan, h->d_xinit, h->d_H0p, h->d_Hcp, h->d_vecs, h->d_H0q, h->d_Hcq, h->d_H0q3, h->d_Hcq3, h->d_park2, h->d_park3, h->d_H0f, h->d_Hcf, h->d_H0t, h->d_Hct, h->d_dts, h->d_shape, h->d_weights, h->d_psi0,
                     h->d_target, h->d_eps, h->d_U, h->d_fw, h->d_bw, h->d_tg, h->d_ret, h->d_f,
-                    h->d_rho};
+                    h->d_rho, h->d_tq, h->d_dJdt};
     for (void *b : bufs)
         if (b) hipFree(b);
     if (h->d_H0p3 && h->d_H0p3 != h->d_H0q3) hipFree(h->d_H0p3);   // (Hermitian operators: the adjoint arrays ARE the plain ones)
@@ -1526,7 +1535,8 @@ void grape_destroy(grape_handle *h) {
 int grape_create(grape_handle **out, const grape_problem *p) try {
     if (!out || !p) { g_create_error = "null argument"; return GRAPE_ERR_INVALID; }
     *out = nullptr;
-    if (p->abi_version != GRAPE_HIP_ABI_VERSION) { g_create_error = "abi_version mismatch"; return GRAPE_ERR_INVALID; }
+    // (ABI v7 added entry points only: a grape_problem of v6 has the same layout)
+    if (p->abi_version != GRAPE_HIP_ABI_VERSION && p->abi_version != 6) { g_create_error = "abi_version mismatch"; return GRAPE_ERR_INVALID; }
     if (p->L <= 0) { g_create_error = "no controls in trajectories (workspace.jl:155-157)"; return GRAPE_ERR_NO_CONTROLS; }
     if (p->N <= 0 || p->K <= 0 || p->N_T <= 0 || !p->tlist || !p->H0 || !p->Hc || !p->psi0) {
         g_create_error = "invalid problem dimensions or null array";
@@ -2515,6 +2525,7 @@ int grape_forward_device(grape_handle *h, const double *d_pulsevals, double *d_o
     }
 #endif
     h->last_walk_fuse = walk_fuse;
+    h->tg_state = h->want_bw ? 2 : 1;
     // ---- phase 1: forward sweep + tau ----
     SweepArgs sa{};
     sa.U = h->d_U; sa.cls = h->d_cls; sa.psi0 = h->d_psi0; sa.target = h->d_target; sa.weights = h->d_weights;
@@ -2804,6 +2815,7 @@ int backward_device_impl(grape_handle *h, const double *d_f, double *d_G, hipStr
     HIPCHK(h, hipGetLastError());
     phase_end(h, 4, s);
     if (!h->capturing) h->n_bwd++;
+    h->tg_state = 3; h->tg_unit = unit; h->tg_xi_user = h->xi_user != nullptr;
     return GRAPE_OK;
 }
 }  // namespace
@@ -2929,7 +2941,7 @@ int backward_enqueue(grape_handle *h, const double f_total[2], const double *chi
 }
 int backward_finish(grape_handle *h, double *G, bool accumulate) {
     const int rc = grape_check(h, h->stream);
-    if (rc) return rc;
+    if (rc) { h->tg_state = 0; return rc; }
     if (!G) return GRAPE_OK;
     const size_t nl = (size_t)h->L * h->N_T;
     if (accumulate) for (size_t i = 0; i < nl; ++i) G[i] += h->h_pin[i];
@@ -3286,6 +3298,7 @@ int grape_eval(grape_handle *h, const double *pulsevals, double *J, double *G, d
                     if (ok) {
                         h->graph = gph; h->graph_fuse_on = h->fuse_on;
                         h->graph_bw_unit = h->bw_unit; h->graph_z_valid = h->z_valid; h->graph_credit = h->credit_pending;
+                        h->graph_tg_unit = h->tg_unit;
                     } else {
                         if (gph) hipGraphDestroy(gph);
                         h->graph_exec = nullptr;
@@ -3299,6 +3312,7 @@ int grape_eval(grape_handle *h, const double *pulsevals, double *J, double *G, d
                 HIPCHK(h, hipGraphLaunch(h->graph_exec, h->stream));
                 h->foreign_stream = false; h->have_forward = true; h->bw_done = false;
                 h->bw_unit = h->graph_bw_unit; h->z_valid = h->graph_z_valid; h->credit_pending = h->graph_credit;
+                h->tg_state = 3; h->tg_unit = h->graph_tg_unit; h->tg_xi_user = false;
                 replayed = true;
             }
         }
@@ -3318,7 +3332,7 @@ int grape_eval(grape_handle *h, const double *pulsevals, double *J, double *G, d
         }
         HIPCHK(h, hipStreamSynchronize(h->stream));
         rc = digest_flags(h, pinned_flags(h));
-        if (rc) return rc;
+        if (rc) { h->tg_state = 0; return rc; }
         if (tau) memcpy(tau, h->h_pin + (size_t)h->L * h->N_T, (size_t)2 * h->K * 8);
         *J = functional_from_sums(h, forward_sums(h));
         memcpy(G, gpin, (size_t)h->L * h->N_T * 8);
@@ -3591,6 +3605,107 @@ int grape_get_work(grape_handle *h, double *out, int n) try {
     }
     if (n > 18) out[18] = h->scan16 ? (double)h->scan_Bk : 0.0;   // block length of the scanned sweeps (N <= 16), 0: sequential sweeps
     return 4;
+}
+GRAPE_BARRIER(h ? &h->err : &g_create_error)
+
+int grape_get_time_gradient(grape_handle *h, double *dJdt) try {
+    if (!h || !dJdt) return GRAPE_ERR_INVALID;
+    const int N_T = h->N_T;
+    if (!h->shards.empty()) {   // the sum over the shards, in shard order
+        std::vector<double> part((size_t)N_T);
+        for (size_t g = 0; g < h->shards.size(); ++g) {
+            const int rc = grape_get_time_gradient(h->shards[g], g == 0 ? dJdt : part.data());
+            if (rc) return multi_fail(h, h->shards[g], rc);
+            if (g > 0) for (int n = 0; n < N_T; ++n) dJdt[n] += part[n];
+        }
+        return GRAPE_OK;
+    }
+    if (h->tg_state != 3) {
+        h->err = h->tg_state == 0 ? "grape_get_time_gradient: no complete gradient evaluation on this time grid (none yet, the last "
+                                    "one failed, or grape_set_tlist came after it)"
+               : h->tg_state == 1 ? "grape_get_time_gradient: the last evaluation had no gradient (grape_eval with G == NULL)"
+                                  : "grape_get_time_gradient called between grape_forward and the backward half";
+        return GRAPE_ERR_INVALID;
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    // (the states of a device-pointer call on the caller's stream: that stream is not ordered against the handle's)
+    if (h->foreign_stream) HIPCHK(h, hipDeviceSynchronize());
+    (void)hipGetLastError();
+    if (!h->d_tq) HIPCHK(h, dmalloc(&h->d_tq, (size_t)h->K * N_T));
+    if (!h->d_dJdt) HIPCHK(h, dmalloc(&h->d_dJdt, (size_t)N_T));
+    TimeGradArgs ta{};
+    ta.H0f = h->d_H0f; ta.Hcf = h->d_Hcf; ta.eps = h->d_eps; ta.shape = h->d_shape;
+    ta.fw = h->d_fw; ta.bw = h->d_bw; ta.rho = h->d_rho; ta.z = h->tg_unit ? h->d_z : nullptr;
+    ta.gb = (h->have_gb && !h->tg_xi_user) ? h->d_gb : nullptr; ta.lambda_q = 0.25 * h->p.lambda_b;
+    ta.out = h->d_tq;
+    ta.K = h->K; ta.L = h->L; ta.N = h->N; ta.NP = h->NP; ta.N_T = N_T; ta.hc_per_traj = h->p.hc_per_traj;
+    // columns per workgroup: the state block in the LDS stays at 64 KB (128 KB at NP = 512, one column tile)
+    const int nct = h->NP <= 64 ? 4 : h->NP <= 128 ? 2 : 1;
+    const size_t lds = (size_t)2 * h->NP * 16 * nct * sizeof(double);
+    const dim3 grid((unsigned)((N_T + 16 * nct - 1) / (16 * nct)), (unsigned)h->K);
+    int dev = 0;
+    HIPCHK(h, hipGetDevice(&dev));
+    static LdsLimit lim1, lim2, lim4;
+    if (nct == 4) {
+        HIPCHK(h, lim4.ensure((const void *)time_grad_kernel<4>, dev, lds));
+        hipLaunchKernelGGL(time_grad_kernel<4>, grid, dim3(256), lds, h->stream, ta);
+    } else if (nct == 2) {
+        HIPCHK(h, lim2.ensure((const void *)time_grad_kernel<2>, dev, lds));
+        hipLaunchKernelGGL(time_grad_kernel<2>, grid, dim3(256), lds, h->stream, ta);
+    } else {
+        HIPCHK(h, lim1.ensure((const void *)time_grad_kernel<1>, dev, lds));
+        hipLaunchKernelGGL(time_grad_kernel<1>, grid, dim3(256), lds, h->stream, ta);
+    }
+    HIPCHK(h, hipGetLastError());
+    // dJdt[n] = -2 sum_k Re out[k][n], the gradient's reduction (fixed order: bitwise repeatable)
+    hipLaunchKernelGGL(grad_reduce_kernel, dim3((N_T + 15) / 16), dim3(256), 0, h->stream, h->d_tq, h->K, N_T, h->d_dJdt,
+                       (const double2 *)nullptr);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipMemcpyAsync(dJdt, h->d_dJdt, (size_t)N_T * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return GRAPE_OK;
+}
+GRAPE_BARRIER(h ? &h->err : &g_create_error)
+
+int grape_set_tlist(grape_handle *h, const double *tlist) try {
+    if (!h || !tlist) return GRAPE_ERR_INVALID;
+    const int N_T = h->N_T;
+    for (int n = 0; n <= N_T; ++n)   // (as grape_create; nothing of the handle changes on a refused grid)
+        if (!std::isfinite(tlist[n]) || (n < N_T && !(tlist[n + 1] > tlist[n]))) {
+            h->err = "tlist must be finite and strictly increasing";
+            return GRAPE_ERR_INVALID;
+        }
+    h->tg_state = 0;
+    h->have_forward = false;
+    if (!h->shards.empty()) {
+        for (grape_handle *c : h->shards) {
+            const int rc = grape_set_tlist(c, tlist);
+            if (rc) return multi_fail(h, c, rc);
+        }
+        return GRAPE_OK;
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipDeviceSynchronize());   // work in flight reads d_dts / d_wq (on this stream or a caller's)
+    std::vector<double> dts((size_t)N_T);
+    for (int n = 0; n < N_T; ++n) dts[n] = tlist[n + 1] - tlist[n];
+    HIPCHK(h, hipMemcpy(h->d_dts, dts.data(), (size_t)N_T * 8, hipMemcpyHostToDevice));
+    if (h->d_wq) {   // trapezoid weights of the state running cost (grape_create, backward_enqueue)
+        std::vector<double> wq((size_t)N_T + 1);
+        for (int m = 0; m <= N_T; ++m)
+            wq[m] = m == 0 ? (tlist[1] - tlist[0]) / 2.0
+                           : (m < N_T ? 0.5 * (tlist[m + 1] - tlist[m - 1]) : (tlist[N_T] - tlist[N_T - 1]) / 2.0);
+        HIPCHK(h, hipMemcpy(h->d_wq, wq.data(), wq.size() * 8, hipMemcpyHostToDevice));
+    }
+    // everything else that follows the time steps is decided per evaluation on the device from d_dts (squarings, series
+    // orders, sub-steps, the four-product plan, the step table of the assembly cells) -- except two host-side leftovers:
+    // the squaring launches the blocked path learnt from the old grid (back to the start value of grape_create) and the
+    // captured graph of the single-wait evaluation (captured again by the next one)
+    h->sq_plan = 2;
+    if (h->graph_exec) { hipGraphExecDestroy(h->graph_exec); h->graph_exec = nullptr; }
+    if (h->graph) { hipGraphDestroy(h->graph); h->graph = nullptr; }
+    h->bw_done = false; h->z_valid = false;
+    HIPCHK(h, hipDeviceSynchronize());   // (copies from pageable memory return once staged)
+    return GRAPE_OK;
 }
 GRAPE_BARRIER(h ? &h->err : &g_create_error)
 

@@ -67,6 +67,18 @@ class ShardedEvaluator:
         J = functional_value(self.functional, sums.tolist(), self.K_total, getattr(self.h, "lambda_b", 0.0))
         return J, G.numpy(), tau
 
+    def time_gradient(self):
+        """dJ/d(dt_n) of the last evaluation: this shard's partial sum, all-reduced like the gradient."""
+        import torch
+        t = torch.from_numpy(np.array(self.h.time_gradient(), dtype=np.float64))
+        if self.dist is not None:
+            self.dist.all_reduce(t)
+        return t.numpy()
+
+    def set_tlist(self, tlist):
+        """A new time grid for this rank's handle (every rank passes the same one)."""
+        self.h.set_tlist(tlist)
+
     # -- device path (nccl == RCCL) ------------------------------------------------------------
     def alloc_device(self, L, N_T, K_local):
         import torch

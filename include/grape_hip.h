@@ -47,7 +47,7 @@
 extern "C" {
 #endif
 
-#define GRAPE_HIP_ABI_VERSION 6
+#define GRAPE_HIP_ABI_VERSION 7   /* v7 added entry points only: grape_create also accepts abi_version 6 */
 
 typedef struct grape_handle grape_handle;
 
@@ -274,6 +274,33 @@ int grape_reset_timings(grape_handle *h);
  * cut into blocks whose propagators are formed first; 0: sequential sweeps; GRAPE_SCAN16=0 / 1 forces)
  * (entries beyond n are not written). */
 int grape_get_work(grape_handle *h, double *out, int n);
+
+/* ABI v7.  Derivative of J with respect to the time steps dt_n = tlist[n+1] - tlist[n] (0-based n < N_T), for the duration
+ * loop around GRAPE (INTEGRATION.md "Optimising the duration").  For piecewise-constant generators dU_n/d(dt_n) = -i H_n U_n:
+ *   dJdt[n] = -2 Re sum_k f_k <chi_k(t_{n+1})| (-i H_kn) |Psi_k(t_{n+1})>  (+ lambda_b / 2 sum_k (g_b,k(t_n) + g_b,k(t_{n+1})))
+ * from the states the last evaluation stored (f_k: the factor of tau_grads), the same reduction as the gradient
+ * (optimize.jl:574-584).  Call it after anything that ran the backward half: grape_eval with G != NULL, grape_backward,
+ * grape_backward_chi, grape_backward_xi, grape_backward_device (after a device-pointer call on a foreign stream it waits
+ * for the device, as the other getters).  It launches its kernel on demand: evaluations that never call it are unchanged.
+ * GRAPE_ERR_INVALID (handle stays usable): no evaluation yet, the last one had no gradient or failed, between grape_forward
+ * and the backward half, or grape_set_tlist since.
+ *   - single handle (K == K_total): the full derivative; split-phase shard (K < K_total): the partial sum over its own
+ *     trajectories, which the caller all-reduces like G; several devices behind one handle: the sum over its shards.
+ *   - the built-in running cost (grape_problem.Dpen, lambda_b) includes the explicit derivative of its trapezoid weights
+ *     (optimize.jl:727-750).  After grape_backward_xi (the caller's g_b) the result is the propagation part ONLY: the
+ *     caller adds lambda_b / 2 sum_k (g_b,k(t_n) + g_b,k(t_{n+1})) for interval n, because only the caller has g_b.
+ *   - the derivative is taken at fixed per-interval pulse and shape values.  A shape S(t) (or pulse) sampled at the
+ *     interval midpoints moves when dt_n changes; that chain rule is the caller's.
+ *   - grid-point form: with t_0 fixed, dJ/dt_j = dJdt[j-1] - dJdt[j] (1 <= j < N_T), dJ/dt_{N_T} = dJdt[N_T-1].
+ *     Scaling a grid of duration T: dJ/dT = sum_n (dt_n / T) dJdt[n]. */
+int grape_get_time_gradient(grape_handle *h, double *dJdt /* [N_T] */);
+
+/* ABI v7.  Replaces the time grid of an existing handle (N_T unchanged): tlist [N_T+1], finite and strictly increasing as in
+ * grape_create, else GRAPE_ERR_INVALID and the handle is unchanged.  Waits for work in flight, recomputes the time steps and
+ * the trapezoid weights on every shard and device, drops the captured graph of the single-wait evaluation and resets the
+ * launch plan of the blocked path: the next evaluation gives what a handle created with this grid gives.  Results of the
+ * previous grid (stored states, the time gradient) are no longer available; the next call must be a forward evaluation. */
+int grape_set_tlist(grape_handle *h, const double *tlist /* [N_T+1] */);
 
 const char *grape_last_error(grape_handle *h); /* h may be NULL: error of the last failed create */
 int grape_abi_version(void);

@@ -1,4 +1,4 @@
-# GrapeHIP.jl -- thin `ccall` glue between GRAPE.jl and libgrape_hip.so (include/grape_hip.h, ABI v6).
+# GrapeHIP.jl -- thin `ccall` glue between GRAPE.jl and libgrape_hip.so (include/grape_hip.h, ABI v7).
 #
 # NOT EXECUTED in this repository's CI: the build image has no Julia toolchain.  It is written
 # against the C ABI and the reference's own interfaces and shows exactly what a GRAPE.jl maintainer
@@ -15,7 +15,7 @@ using QuantumControl.QuantumPropagators.Amplitudes: ShapedAmplitude
 using QuantumControl.Functionals: J_T_sm, J_T_ss, J_T_re
 
 const libgrape = get(ENV, "GRAPE_HIP_LIB", "libgrape_hip.so")
-const ABI_VERSION = 6
+const ABI_VERSION = 7
 
 # mirror of `grape_problem` (include/grape_hip.h); field order and types must match the C struct
 # (tests/test_abi.py compares the field lists)
@@ -350,6 +350,34 @@ function make_fg!(h::Handle, wrk)
         end
         return sum(wrk.J_parts)
     end
+end
+
+
+"""
+    time_gradient!(dJdt, h)
+
+`dJdt[n] = ∂J/∂Δt_n` (`length(dJdt) == N_T`) of the last evaluation with a gradient (grape_get_time_gradient, ABI v7), at
+fixed per-interval pulse and shape values.  Shapes and pulses sampled on interval midpoints move with `Δt_n`: that chain
+rule is the caller's, and so is the explicit weight term of a `g_b` handed over as data (grape_backward_xi).  Grid-point
+form: `∂J/∂t_j = dJdt[j] - dJdt[j+1]`; duration of a scaled grid: `dJ/dT = sum(Δt .* dJdt) / T`.
+"""
+function time_gradient!(dJdt::Vector{Float64}, h::Handle)
+    length(dJdt) == h.N_T || throw(DimensionMismatch("dJdt must have N_T = $(h.N_T) entries"))
+    check(h, GC.@preserve dJdt ccall((:grape_get_time_gradient, libgrape), Cint, (Ptr{Cvoid}, Ptr{Float64}), h.ptr, dJdt))
+    return dJdt
+end
+
+"""
+    set_tlist!(h, tlist)
+
+A new time grid for the handle (grape_set_tlist, ABI v7): same `N_T`, strictly increasing and finite; the next `fg!` call
+evaluates on it.  The pulses stay per interval: resampling them (and `wrk.tlist`) is the caller's.
+"""
+function set_tlist!(h::Handle, tlist::AbstractVector{Float64})
+    length(tlist) == h.N_T + 1 || throw(DimensionMismatch("tlist must have N_T + 1 = $(h.N_T + 1) points"))
+    t = collect(Float64, tlist)
+    check(h, GC.@preserve t ccall((:grape_set_tlist, libgrape), Cint, (Ptr{Cvoid}, Ptr{Float64}), h.ptr, t))
+    return h
 end
 
 end # module
