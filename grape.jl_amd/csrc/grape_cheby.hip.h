@@ -47,7 +47,6 @@ struct ChebyArgs {
     unsigned long long *stats;   // [10] += terms, [11] += (sub-)steps
     double2 *xch;         // [K][4][NP] exchange slots of the recursion vectors, armed with the sentinel at launch
     int *xcc;             // [K][32] XCC id of every sibling's CU (-1 at launch)
-    int xmode;            // XCD-local accesses: bit 0 stores, bit 1 loads (0: device scope throughout)
     double tol;           // terms below tol are dropped (1e-17: converged to rounding)
     int L, hc_per_traj, NP, herm, k0, kn;   // this launch covers the trajectories [k0, k0 + kn)
 };
@@ -86,21 +85,10 @@ __device__ inline int cheby_coefficients(double alpha, double tol, double *coef)
     return J;
 }
 
-// exchange accesses: L2-coherent inside one XCD (sc0) or device-coherent (sc1)
+// exchange stores: L2-coherent inside one XCD (sc0) or device-coherent (sc1); the polls are device-scope loads (coop_load)
 __device__ __forceinline__ void xch_store(double2 *p, double2 v, bool xcd_local) {
-    if (xcd_local) {
-        __hip_atomic_store(&p->x, v.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        __hip_atomic_store(&p->y, v.y, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    } else coop_store(p, v);
-}
-__device__ __forceinline__ double2 xch_load(const double2 *p, bool xcd_local) {
-    if (!xcd_local) return coop_load(p);
-    // the per-CU vector cache may hold the (armed) line from the previous poll: drop it, then read the XCD's L2
-    asm volatile("buffer_inv sc0" ::: "memory");
-    double2 v;
-    v.x = __hip_atomic_load(&p->x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    v.y = __hip_atomic_load(&p->y, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    return v;
+    if (xcd_local) coop_store_l2(p, v);
+    else coop_store(p, v);
 }
 
 template <bool BACKWARD>
@@ -135,7 +123,7 @@ __device__ __forceinline__ void cheby_coop_body(const ChebyArgs &a, const int k,
         xl = same;
     }
     __syncthreads();
-    const bool xcd_st = xl != 0 && (a.xmode & 1), xcd_ld = xl != 0 && (a.xmode & 2);
+    const bool xcd_st = xl != 0;
     bool dead = false;   // a sibling did not answer within the spin limit: flag 8 is up, nobody waits any more
     double *hre = hs, *him = hs + R * LDH;
     const double *h0 = a.H0 + (size_t)k * 2 * NP * NP;
@@ -222,7 +210,7 @@ __device__ __forceinline__ void cheby_coop_body(const ChebyArgs &a, const int k,
             double2 v;
             int spin = 0;
             for (;;) {
-                v = xch_load(&buf[i], xcd_ld);
+                v = coop_load(&buf[i]);
                 if (__double_as_longlong(v.x) != (long long)CHEBY_SENTINEL &&
                     __double_as_longlong(v.y) != (long long)CHEBY_SENTINEL) break;
                 if (dead || ++spin > (1 << 19)) {   // a sibling is missing: give up for good (the evaluation fails with flag 8)

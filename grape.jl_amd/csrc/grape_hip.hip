@@ -97,21 +97,10 @@ struct grape_handle {
     double *d_lg[9] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     double *d_dinv = nullptr;
     int *d_scell = nullptr;
-    double *d_colpart = nullptr;   // [chunk][2][LG_PARTS][NP] partial column sums of two powers (lg_t18_operands2_kernel)
-    bool lg_form2 = false;         // formation with the operators in registers (lg_form2_kernel; GRAPE_LG_FORM2=0: lg_form_kernel)
-    double *d_normpart = nullptr, *d_normpart2 = nullptr;   // [chunk][NP / 8][NP] partial column sums of |A| (per lane of chunks)
-    bool lg_fuse = true;           // GRAPE_LG_FUSE=0: the combinations in a pass of their own (lg_t18_operands2_kernel) instead of
-                                   // the epilogue of the launch that writes the last power
-    bool lg_pow = false;           // GRAPE_LG_POW=1 (round 6, measured, off): B4, B3, B2 formed from the powers by the launches that add them
-    bool lg_spec = true;           // GRAPE_LG_SPEC=0: the separate norm pass (lg_t18_scale_kernel) in front of the combinations
-    // second lane of the polynomial route (round 5, GRAPE_LG_LANES=2; off by default): the chunks of an evaluation are
-    // independent, so odd chunks run on a second stream with their own scratch and fill the launch tails of the even ones
-    int lg_lanes = 1;
-    double *d_lg2[9] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    double *d_dinv2 = nullptr, *d_colpart2 = nullptr;
-    int *d_scell2 = nullptr, *d_smax2 = nullptr;
-    hipStream_t lg_stream2 = nullptr;
-    hipEvent_t lg_ev_fork = nullptr, lg_ev_join = nullptr;
+    double *d_colpart = nullptr;   // [chunk][2][LG_PARTS][NP] partial column sums of two powers (polynomial route)
+    bool lg_form2 = false;         // formation with the operators in registers (lg_form2_kernel; else lg_form_kernel: controls per
+                                   // trajectory, L > 4)
+    double *d_normpart = nullptr;  // [chunk][NP / 8][NP] partial column sums of |A| (lg_form2_kernel)
     double *d_dts = nullptr, *d_shape = nullptr, *d_weights = nullptr;
     double2 *d_psi0 = nullptr, *d_target = nullptr;
     // per-evaluation
@@ -175,7 +164,6 @@ struct grape_handle {
     // diagnostic switches, read ONCE in grape_create (never in the evaluation path: getenv is not thread-safe against setenv)
     bool expm_persist = true;    // GRAPE_EXPM_PERSIST=0: one workgroup per cell instead of the persistent Pade kernel
     int expm_lds_pad_kb = 0;     // GRAPE_EXPM_LDS_PAD: extra dynamic LDS of the Pade kernels (fewer cells per CU)
-    int cheby_xmode = 1;         // GRAPE_CHEBY_XMODE
     bool test_hooks = false;     // GRAPE_TEST_HOOKS=1 at grape_create: the fault injection of the test suite (GRAPE_TEST_DROP_SIBLING)
                                  // is looked up per evaluation; without it the evaluation path never calls getenv
     bool lg_asm = true;          // GRAPE_LG_ASM=0: the compiled lg_gemm_kernel for the products of the blocked polynomial route
@@ -187,12 +175,9 @@ struct grape_handle {
     bool no_target = false;
     std::vector<int> cls;        // [K] class of trajectory k
     int *d_cls = nullptr, *d_rep = nullptr;
-    unsigned *d_coop = nullptr;  // [2][K] step counters of the cooperative sweeps (forward, backward)
     int coop_S = 0;              // workgroups per trajectory in the cooperative sweeps (0: one-workgroup kernel)
     int *d_xcc_sw = nullptr;     // [2][K][32] XCC ids of the siblings of the cooperative sweeps (forward, backward)
-    int coop_xmode = 1;          // GRAPE_COOP_XMODE=0: step counters instead of armed storage rows (SweepArgs::xmode)
     int coop_rpw = 0, coop_nw = 0;  // rows per wave and waves of a cooperative workgroup (R = nw * rpw state rows)
-    int coop_S_fw = 0, coop_rpw_fw = 0, coop_nw_fw = 0;   // the forward sweep's own split (GRAPE_COOP_S_FW; default: fewer siblings, see grape_create)
     // state running cost (g_b = <Psi|D|Psi>): transposed D, trapezoid weights, xi and g per stored state
     double2 *d_Dt = nullptr, *d_xi = nullptr;
     double *d_wq = nullptr, *d_gb = nullptr;
@@ -388,22 +373,20 @@ extern "C" void grape_t18_set_stamps(unsigned long long *d_stamps, void *stream)
 #endif
 
 template <int CPL>
-hipError_t launch_coop(const SweepArgs &a, bool backward, int S, int rpw, int nw, unsigned *cnt, hipStream_t s) {
-    hipError_t e = hipMemsetAsync(cnt, 0, (size_t)a.K * sizeof(unsigned), s);
-    if (e != hipSuccess) return e;
+hipError_t launch_coop(const SweepArgs &a, bool backward, int S, int rpw, int nw, hipStream_t s) {
+    hipError_t e;
     if (a.xcc) {
         e = hipMemsetAsync(a.xcc, 0xFF, (size_t)a.K * 32 * sizeof(int), s);
         if (e != hipSuccess) return e;
     }
-    if (a.xmode) {   // arm every row of the storage (the boundary row of a trajectory is written by sibling 0 inside the kernel and polled by nobody)
-        e = hipMemsetAsync((void *)a.store, 0xFF, (size_t)a.K * (a.N_T + 1) * 64 * CPL * sizeof(double2), s);
-        if (e != hipSuccess) return e;
-    }
+    // arm every row of the storage (the boundary row of a trajectory is written by sibling 0 inside the kernel and polled by nobody)
+    e = hipMemsetAsync((void *)a.store, 0xFF, (size_t)a.K * (a.N_T + 1) * 64 * CPL * sizeof(double2), s);
+    if (e != hipSuccess) return e;
     const dim3 grid(8 * ((a.K + 7) / 8) * S), block(64 * nw);
 #define COOP_CASE(NW_, RPW_)                                                                                          \
     if (nw == NW_ && rpw == RPW_) {                                                                                   \
-        if (backward) hipLaunchKernelGGL((sweep_coop_kernel<CPL, RPW_, NW_, true>), grid, block, 0, s, a, S, cnt);    \
-        else hipLaunchKernelGGL((sweep_coop_kernel<CPL, RPW_, NW_, false>), grid, block, 0, s, a, S, cnt);            \
+        if (backward) hipLaunchKernelGGL((sweep_coop_kernel<CPL, RPW_, NW_, true>), grid, block, 0, s, a, S);         \
+        else hipLaunchKernelGGL((sweep_coop_kernel<CPL, RPW_, NW_, false>), grid, block, 0, s, a, S);                 \
         return hipGetLastError();                                                                                     \
     }
     COOP_CASE(4, 1) COOP_CASE(8, 1) COOP_CASE(16, 1) COOP_CASE(16, 2) COOP_CASE(16, 4)
@@ -965,14 +948,6 @@ struct LgComb {
     const LgT18OperandsArgs *o;
     double *colpart;
     int q_is_a6;
-    int lite;                      // round 6: B4, B3, B2 are left to the launches that add them (LgPow)
-};
-// round 6: the epilogue terms of a launch as combinations of the powers, formed in its epilogue (asm/gen_lg.py power_adds):
-// C += c1 . (1, A, A2, A3, A6); second output C2 = C + c2 . (...).  Cells with s_cell > 0 read the launch's Add arrays.
-struct LgPow {
-    const double *A, *A2, *A3, *A6;
-    const int *s_cell;
-    double c1[5], c2[5];
 };
 bool lg_asm_eligible(const grape_handle *h, int NP, int nc, int per_cell) {
     return h->lg_asm && (NP == 128 || NP == 256) && (long)((nc + 7) / 8) * 8 * per_cell < (1L << 24);
@@ -981,8 +956,7 @@ bool lg_full_view(const LgView &v, int NP) {
     return v.p && v.rb == 0 && v.cb == 0 && v.ld == NP && v.plane == (size_t)NP * NP && v.cell_stride == (size_t)2 * NP * NP;
 }
 // true: launched (err holds the status); false: not eligible
-bool lg_try_asm(const grape_handle *h, hipStream_t s, const LgGemmArgs &a, hipError_t *err, const LgComb *comb = nullptr,
-                const LgPow *pow = nullptr) {
+bool lg_try_asm(const grape_handle *h, hipStream_t s, const LgGemmArgs &a, hipError_t *err, const LgComb *comb = nullptr) {
     if (!h->lg_asm) return false;   // (GRAPE_LG_ASM, read once in grape_create: the route of a handle never changes)
     const int NP = a.C.ld, NB = a.nbi;
     if ((NP != 128 && NP != 256) || a.nbj != NB || a.kblocks != NB || NB * 64 != NP) return false;
@@ -1009,19 +983,11 @@ bool lg_try_asm(const grape_handle *h, hipStream_t s, const LgGemmArgs &a, hipEr
     if (comb) {
         if (a.nadd || a.Uout || a.C2.p || squaring) return false;
         const LgT18OperandsArgs &o = *comb->o;
-        k.comb_mode = 1 | (comb->q_is_a6 ? 2 : 0) | (comb->lite ? 8 : 0);
+        k.comb_mode = 1 | (comb->q_is_a6 ? 2 : 0);
         k.P1 = o.A; k.P2 = o.A2; k.P3 = o.A3; k.B1 = o.B1; k.B5 = o.B5; k.B4 = o.B4; k.B3 = o.B3; k.B2 = o.B2;
         k.colpart = comb->colpart;
         memcpy(k.ca, o.a, sizeof(k.ca)); memcpy(k.ce, o.e, sizeof(k.ce)); memcpy(k.cd, o.d, sizeof(k.cd));
         memcpy(k.cc, o.c, sizeof(k.cc)); memcpy(k.cb, o.b, sizeof(k.cb));
-    }
-    if (pow) {
-        if (comb || !a.nadd || squaring || a.herm) return false;
-        k.comb_mode = 4;
-        k.P1 = pow->A; k.P2 = pow->A2; k.P3 = pow->A3;
-        k.B1 = const_cast<double *>(pow->A6);                       // (slots of the argument block: gen_lg.py power_adds)
-        k.B5 = reinterpret_cast<double *>(const_cast<int *>(pow->s_cell));
-        memcpy(k.cd, pow->c1, sizeof(k.cd)); memcpy(k.cc, pow->c2, sizeof(k.cc));
     }
     const int groups = (a.ncell + 7) / 8;
     if ((long)groups * 8 * k.per_cell >= (1L << 24)) return false;
@@ -1056,7 +1022,7 @@ hipError_t lg_gemm(const grape_handle *h, hipStream_t s, int nc, int nbi, int nb
 hipError_t lg_gemm_poly(const grape_handle *h, hipStream_t s, int nc, int NB, LgView X, LgView Y, LgView C, int herm, int nadd, const LgView *add,
                         const double *coef, const int *add_pow, double cI, const int *scale_s,
                         const LgView *C2 = nullptr, const double *coef2 = nullptr, double cI2 = 0.0,
-                        double2 *Uout = nullptr, int u_np = 0, const int *smax_ptr = nullptr, const LgPow *pow = nullptr) {
+                        double2 *Uout = nullptr, int u_np = 0, const int *smax_ptr = nullptr) {
     LgGemmArgs a{};
     a.X = X; a.Y = Y; a.C = C; a.kblocks = NB; a.alpha = 1.0; a.beta = 0.0; a.cI = cI;
     a.nadd = nadd;
@@ -1071,8 +1037,7 @@ hipError_t lg_gemm_poly(const grape_handle *h, hipStream_t s, int nc, int NB, Lg
     const int groups = (nc + 7) / 8;
     const int per_cell = a.herm ? NB * (NB + 1) / 2 : NB * NB;
     hipError_t easm;
-    if (lg_try_asm(h, s, a, &easm, nullptr, pow)) return easm;
-    if (pow) return hipErrorInvalidValue;   // (only the assembly kernel forms its terms from the powers: the caller asks lg_asm_eligible first)
+    if (lg_try_asm(h, s, a, &easm)) return easm;
     hipLaunchKernelGGL(lg_gemm_kernel, dim3(groups * 8 * per_cell), dim3(256), 0, s, a);
     return hipGetLastError();
 }
@@ -1107,7 +1072,6 @@ hipError_t expm_large_t18(grape_handle *h, hipStream_t s) {
     // nine chunk buffers: the four powers, then the five combinations; the powers are dead once those are formed and
     // their buffers take A9, B3 + A9 and the result
     const bool hm = h->herm;
-    hipStream_t const s_main = s;
     // executed matrix instructions per cell (all waves of all workgroups; a 64-block product of one output block is 4 waves
     // x 192 instructions): full products NB^3 blocks, triangular ones NB^2 (NB + 1) / 2
     const unsigned long long blk = 4ull * 192ull;
@@ -1119,45 +1083,24 @@ hipError_t expm_large_t18(grape_handle *h, hipStream_t s) {
         hipLaunchKernelGGL(ctrl_sum_kernel, dim3(h->N_T, std::max(1, ca.pp2 / 2 / 2048)), dim3(256), 0, s, ca);
         LGCHK(hipGetLastError());
     }
-    if (h->lg_lanes == 2) {   // the second lane starts behind what this stream has enqueued so far (pulses, S_n, cleared flags)
-        LGCHK(hipMemsetAsync(h->d_smax2, 0, sizeof(int), s_main));
-        LGCHK(hipEventRecord(h->lg_ev_fork, s_main));
-        LGCHK(hipStreamWaitEvent(h->lg_stream2, h->lg_ev_fork, 0));
-    }
-    long ichunk = 0;
-    for (long c0_ = 0; c0_ < ncell; c0_ += h->chunk, ++ichunk) {
+    double *const A = h->d_lg[0], *const A2 = h->d_lg[1], *const A3 = h->d_lg[2], *const A6 = h->d_lg[3];
+    double *const B1 = h->d_lg[4], *const B5 = h->d_lg[5], *const B4 = h->d_lg[6], *const B3 = h->d_lg[7], *const B2 = h->d_lg[8];
+    double *const A9 = A, *const Lm = A2, *const T = A3;
+    int *const d_smax = h->d_flags + 1;
+    for (long c0_ = 0; c0_ < ncell; c0_ += h->chunk) {
         const int nc = (int)std::min<long>(h->chunk, ncell - c0_);
-        const bool lane2 = h->lg_lanes == 2 && (ichunk & 1);
-        double *const *lg = lane2 ? h->d_lg2 : h->d_lg;
-        double *A = lg[0], *A2 = lg[1], *A3 = lg[2], *A6 = lg[3], *B1 = lg[4], *B5 = lg[5], *B4 = lg[6], *B3 = lg[7], *B2 = lg[8];
-        const int nc_ = (int)std::min<long>(h->chunk, ncell - c0_);
-        // round 6: B4, B3, B2 are formed by the launches that add them, from the powers (the launch of A6 then writes three
-        // arrays instead of six: it is HBM-bound, the two general products have bandwidth to spare).  The powers have to
-        // survive until the last product: A9 and B3 + A9 take the buffers of B4 and B3 (a cell that needed a scaling reads
-        // its B4 / B3 block and then overwrites it, in the same workgroup).  Measured at the C5 shard (GRAPE_LG_POW=1, same
-        // box): the launch of A6 1.33 -> 1.13 ms per chunk, the two general products 1.09 -> 1.22 ms each -- the epilogue's eight
-        // serial load groups cost what the HBM-bound launch saves (phase A 124.5 / 126.4 -> 126.4 / 126.3 ms).  Off by default.
-        const bool power = h->lg_pow && h->lg_spec && h->lg_fuse && lg_asm_eligible(h, NP, nc_, hm ? NB * (NB + 1) / 2 : NB * NB) &&
-                           lg_asm_eligible(h, NP, nc_, NB * NB);
-        double *A9 = power ? B4 : A, *Lm = power ? B3 : A2, *T = A3;
-        int *const d_scell = lane2 ? h->d_scell2 : h->d_scell;
-        double *const d_dinv = lane2 ? h->d_dinv2 : h->d_dinv, *const d_colpart = lane2 ? h->d_colpart2 : h->d_colpart;
-        int *const d_smax = lane2 ? h->d_smax2 : h->d_flags + 1;
-        s = lane2 ? h->lg_stream2 : s_main;
-        const size_t nel = (size_t)nc * 2 * pp;
         LgFormArgs fa{};
         fa.H0f = h->d_H0f; fa.Hcf = h->d_Hcf; fa.eps = h->d_eps; fa.shape = h->d_shape; fa.dts = h->d_dts;
-        fa.A = A; fa.s_cell = d_scell; fa.stats = h->d_stats; fa.flags = h->d_flags;
+        fa.A = A; fa.s_cell = h->d_scell; fa.stats = h->d_stats; fa.flags = h->d_flags;
         fa.NP = NP; fa.L = h->L; fa.N_T = h->N_T; fa.hc_per_traj = h->p.hc_per_traj; fa.cell0 = (int)c0_; fa.rep = h->d_rep;
-        fa.norm1 = d_dinv;   // (the inverse slots of the Pade route are idle here: ||A||_1 per cell)
+        fa.norm1 = h->d_dinv;   // (the inverse slots of the Pade route are idle here: ||A||_1 per cell)
         fa.Sf = h->d_Sf;
         if (h->lg_form2) {
-            double *np_ = lane2 ? h->d_normpart2 : h->d_normpart;
             const dim3 grid(NP / LG_FORM_ROWS, (nc + 15) / 16);
-            if (h->L <= 2) hipLaunchKernelGGL(lg_form2_kernel<2>, grid, dim3(256), 0, s, fa, nc, np_);
-            else hipLaunchKernelGGL(lg_form2_kernel<4>, grid, dim3(256), 0, s, fa, nc, np_);
+            if (h->L <= 2) hipLaunchKernelGGL(lg_form2_kernel<2>, grid, dim3(256), 0, s, fa, nc, h->d_normpart);
+            else hipLaunchKernelGGL(lg_form2_kernel<4>, grid, dim3(256), 0, s, fa, nc, h->d_normpart);
             LGCHK(hipGetLastError());
-            hipLaunchKernelGGL(lg_norm1_kernel, dim3(nc), dim3(256), 0, s, fa, (const double *)np_);
+            hipLaunchKernelGGL(lg_norm1_kernel, dim3(nc), dim3(256), 0, s, fa, (const double *)h->d_normpart);
         } else {
             hipLaunchKernelGGL(lg_form_kernel, dim3(nc), dim3(1024), 0, s, fa);
         }
@@ -1167,13 +1110,13 @@ hipError_t expm_large_t18(grape_handle *h, hipStream_t s) {
         LGCHK(lg_gemm(h, s, nc, NB, NB, vA, vA, vA2, NB, 1.0, 0.0, 0, nullptr, nullptr, 0.0, nullptr, 0, hm ? 1 : 0));     // A2 = A A
         LGCHK(lg_gemm(h, s, nc, NB, NB, vA2, vA, vA3, NB, 1.0, 0.0, 0, nullptr, nullptr, 0.0, nullptr, 0, hm ? -1 : 0));   // A3 = A2 A
         LgT18ScaleArgs sa{};
-        sa.P = A2; sa.Q = hm ? A6 : A3; sa.qpow = hm ? 6 : 3; sa.norm1 = hm ? nullptr : d_dinv;
-        sa.s_cell = d_scell; sa.flags = h->d_flags; sa.smax = d_smax; sa.stats = h->d_stats; sa.NP = NP;
+        sa.norm1 = hm ? nullptr : h->d_dinv;
+        sa.s_cell = h->d_scell; sa.flags = h->d_flags; sa.smax = d_smax; sa.stats = h->d_stats; sa.NP = NP;
         sa.theta = hm ? T18_THETA : T18T_THETA;
         sa.mfma_per_cell = (hm ? 3 * tri : 3 * gen) + 2 * gen; sa.mfma_per_sq = gen;
         LgT18OperandsArgs oa{};
         oa.A = A; oa.A2 = A2; oa.A3 = A3; oa.A6 = A6; oa.B1 = B1; oa.B5 = B5; oa.B4 = B4; oa.B3 = B3; oa.B2 = B2;
-        oa.s_cell = d_scell; oa.NP = NP; oa.per_cell = 2 * pp; oa.n = nel;
+        oa.s_cell = h->d_scell; oa.NP = NP; oa.per_cell = 2 * pp; oa.n = (size_t)nc * 2 * pp;
         if (hm) {
             const double a_[3] = {T18_A1, T18_A2, T18_A3}, e_[3] = {T18_E2, T18_E3, T18_E6}, b_[5] = {T18_B0, T18_B1, T18_B2, T18_B3, T18_B6};
             const double c_[5] = {T18_C0, T18_C1, T18_C2, T18_C3, T18_C6}, d_[5] = {T18_D0, T18_D1, T18_D2, T18_D3, T18_D6};
@@ -1187,76 +1130,56 @@ hipError_t expm_large_t18(grape_handle *h, hipStream_t s) {
         }
         // round 5: the launch of A6 forms the combinations in its epilogue, for s = 0, with the column sums of the decision
         // (Hermitian generators: a workgroup of the upper block triangle also forms those of the mirrored block)
-        const bool fused = h->lg_spec && h->lg_fuse && lg_asm_eligible(h, NP, nc, hm ? NB * (NB + 1) / 2 : NB * NB);
+        const bool fused = lg_asm_eligible(h, NP, nc, hm ? NB * (NB + 1) / 2 : NB * NB);
         {
-            const LgComb cb{&oa, d_colpart, hm ? 1 : 0, (fused && power) ? 1 : 0};
+            const LgComb cb{&oa, h->d_colpart, hm ? 1 : 0};
             LGCHK(lg_gemm(h, s, nc, NB, NB, vA3, vA3, vA6, NB, 1.0, 0.0, 0, nullptr, nullptr, 0.0, nullptr, 0, hm ? 1 : 0,    // A6 = A3 A3
                           nullptr, 0, nullptr, 0, -1, nullptr, fused ? &cb : nullptr));
         }
-        if (!h->lg_spec) {
-            hipLaunchKernelGGL(lg_t18_scale_kernel, dim3(nc), dim3(256), 0, s, sa);
-            LGCHK(hipGetLastError());
-        }
-        if (h->lg_spec) {
-            // combinations for s = 0 with the column sums of A2 and A6 / A3 on the way, the decision, and the combinations once
-            // more for the cells that need a scaling (none at the benchmark's norms: that launch leaves at once)
-            LgT18Operands2Args o2{};
-            o2.o = oa; o2.colpart = d_colpart; o2.q_is_a6 = hm ? 1 : 0; o2.redo = 0;
-            if (!fused) {
-                hipLaunchKernelGGL(lg_t18_operands2_kernel, dim3((unsigned)nc * LG_PARTS), dim3(256), 0, s, o2);
-                LGCHK(hipGetLastError());
-            }
-            LgT18DecideArgs da{};
-            da.colpart = d_colpart; da.s = sa; da.nparts = fused ? NB : LG_PARTS;
-            if (h->deriv_econ && h->d_celldeg && hm) {
-                da.cell_deg = h->d_celldeg; da.cell0 = (int)c0_; da.econ_n = 0;
-                for (int i = 0; i < ECON_NSETS && da.econ_n < 4; ++i)
-                    if (ECON_THETAS[i] <= T18_THETA) { da.econ_theta[da.econ_n] = ECON_THETAS[i]; da.econ_deg[da.econ_n++] = ECON_DEG[i]; }
-            }
-            hipLaunchKernelGGL(lg_t18_decide_kernel, dim3(nc), dim3(256), 0, s, da);
-            LGCHK(hipGetLastError());
-            o2.redo = 1;
+        // combinations for s = 0 with the column sums of A2 and A6 / A3 on the way, the decision, and the combinations once
+        // more for the cells that need a scaling (none at the benchmark's norms: that launch leaves at once)
+        LgT18Operands2Args o2{};
+        o2.o = oa; o2.colpart = h->d_colpart; o2.q_is_a6 = hm ? 1 : 0; o2.redo = 0;
+        if (!fused) {
             hipLaunchKernelGGL(lg_t18_operands2_kernel, dim3((unsigned)nc * LG_PARTS), dim3(256), 0, s, o2);
             LGCHK(hipGetLastError());
-        } else {
-            hipLaunchKernelGGL(lg_t18_operands_kernel, dim3(2048), dim3(256), 0, s, oa);
-            LGCHK(hipGetLastError());
         }
+        LgT18DecideArgs da{};
+        da.colpart = h->d_colpart; da.s = sa; da.nparts = fused ? NB : LG_PARTS;
+        if (h->deriv_econ && h->d_celldeg && hm) {
+            da.cell_deg = h->d_celldeg; da.cell0 = (int)c0_; da.econ_n = 0;
+            for (int i = 0; i < ECON_NSETS && da.econ_n < 4; ++i)
+                if (ECON_THETAS[i] <= T18_THETA) { da.econ_theta[da.econ_n] = ECON_THETAS[i]; da.econ_deg[da.econ_n++] = ECON_DEG[i]; }
+        }
+        hipLaunchKernelGGL(lg_t18_decide_kernel, dim3(nc), dim3(256), 0, s, da);
+        LGCHK(hipGetLastError());
+        o2.redo = 1;
+        hipLaunchKernelGGL(lg_t18_operands2_kernel, dim3((unsigned)nc * LG_PARTS), dim3(256), 0, s, o2);
+        LGCHK(hipGetLastError());
         const LgView vB4 = lg_full(B4, NP), vB3 = lg_full(B3, NP), vB2 = lg_full(B2, NP);
-        const int *smax_ptr = d_smax;
         {   // A9 = B1 B5 + B4 and, from the same launch, B3 + A9 (the left operand of the last product)
             const LgView add[2] = {vB4, vB3};
             const double c1[2] = {1.0, 0.0}, c2[2] = {0.0, 1.0};
             const int pw0[2] = {0, 0};
-            LgPow pw{A, A2, A3, A6, d_scell, {0}, {0}};
-            memcpy(pw.c1, oa.d, sizeof(pw.c1)); memcpy(pw.c2, oa.c, sizeof(pw.c2));
-            LGCHK(lg_gemm_poly(h, s, nc, NB, vB1, vB5, vA9, 0, 2, add, c1, pw0, 0.0, nullptr, &vL, c2, 0.0, nullptr, 0, nullptr,
-                               (fused && power) ? &pw : nullptr));
+            LGCHK(lg_gemm_poly(h, s, nc, NB, vB1, vB5, vA9, 0, 2, add, c1, pw0, 0.0, nullptr, &vL, c2, 0.0));
         }
         {   // p = B2 + (B3 + A9) A9: straight into U_kn unless a cell of this evaluation needs a squaring
             const LgView add[1] = {vB2};
             const double c1[1] = {1.0};
             const int pw0[1] = {0};
-            LgPow pw{A, A2, A3, A6, d_scell, {0}, {0}};
-            memcpy(pw.c1, oa.b, sizeof(pw.c1));
             LGCHK(lg_gemm_poly(h, s, nc, NB, vL, vA9, vT, 0, 1, add, c1, pw0, 0.0, nullptr, nullptr, nullptr, 0.0,
-                               h->d_U + (size_t)c0_ * pp, NP, smax_ptr, (fused && power) ? &pw : nullptr));
+                               h->d_U + (size_t)c0_ * pp, NP, d_smax));
         }
         // squarings by the launch plan (see expm_large): every launch exits at once when it is not needed, the last
         // needed one writes U_kn for all cells of the chunk (cells that are done are copied through)
         double *X = T, *Y = B1;
         for (int it = 0; it < h->sq_plan; ++it) {
             LGCHK(lg_gemm(h, s, nc, NB, NB, lg_full(X, NP), lg_full(X, NP), lg_full(Y, NP), NB, 1.0, 0.0, 0, nullptr, nullptr,
-                          0.0, d_scell, it, 0, nullptr, 0, h->d_U + (size_t)c0_ * pp, NP, -1, smax_ptr));
+                          0.0, h->d_scell, it, 0, nullptr, 0, h->d_U + (size_t)c0_ * pp, NP, -1, d_smax));
             std::swap(X, Y);
         }
     }
-    s = s_main;
-    if (h->lg_lanes == 2) {
-        LGCHK(hipEventRecord(h->lg_ev_join, h->lg_stream2));
-        LGCHK(hipStreamWaitEvent(s, h->lg_ev_join, 0));
-    }
-    hipLaunchKernelGGL(lg_plan_check_kernel, dim3(1), dim3(1), 0, s, h->d_flags, h->sq_plan, h->lg_lanes == 2 ? h->d_smax2 : nullptr);
+    hipLaunchKernelGGL(lg_plan_check_kernel, dim3(1), dim3(1), 0, s, h->d_flags, h->sq_plan);
     LGCHK(hipGetLastError());
     return hipSuccess;
 }
@@ -1350,7 +1273,7 @@ hipError_t expm_large(grape_handle *h, hipStream_t s) {
                            h->d_U + (size_t)c0 * pp, NP, (size_t)nc * pp, smax_ptr);
         LGCHK(hipGetLastError());
     }
-    hipLaunchKernelGGL(lg_plan_check_kernel, dim3(1), dim3(1), 0, s, h->d_flags, h->sq_plan, (const int *)nullptr);
+    hipLaunchKernelGGL(lg_plan_check_kernel, dim3(1), dim3(1), 0, s, h->d_flags, h->sq_plan);
     LGCHK(hipGetLastError());
     return hipSuccess;
 }
@@ -1389,10 +1312,6 @@ hipError_t launch_cheby(grape_handle *h, const SweepArgs *sf, const SweepArgs *s
         c.eps = h->d_eps; c.shape = h->d_shape; c.dts = h->d_dts; c.rb = h->d_rb; c.stats = h->d_stats;
         c.xch = h->d_xch + (backward ? (size_t)K * 4 * NP : 0);
         c.xcc = h->d_xcc + (backward ? (size_t)K * 32 : 0);
-        // XCD-local stores (sc0: they land in the XCD's L2, where the siblings' device-scope polls find them) are the
-        // default -- C5 shard sweeps 175 -> 141 ms; XCD-local LOADS (buffer_inv sc0 + sc0 load) never saw the data
-        // on gfx950 and are not used
-        c.xmode = h->cheby_xmode;
         c.tol = h->series_tol;
         c.L = h->L; c.hc_per_traj = h->p.hc_per_traj; c.NP = NP; c.herm = h->herm ? 1 : 0;
     };
@@ -1508,12 +1427,7 @@ void grape_destroy(grape_handle *h) {
     if (h->stream) hipStreamSynchronize(h->stream);
     for (double *b : h->d_lg)
         if (b) hipFree(b);
-    for (double *b : h->d_lg2)
-        if (b) hipFree(b);
-    if (h->lg_stream2) { hipStreamSynchronize(h->lg_stream2); hipStreamDestroy(h->lg_stream2); }
-    if (h->lg_ev_fork) hipEventDestroy(h->lg_ev_fork);
-    if (h->lg_ev_join) hipEventDestroy(h->lg_ev_join);
-    void *bufs[] = {h->d_celldeg, h->d_xcc_sw, h->d_scanF, h->d_scan_fw, h->d_scan_bw, h->d_dte, h->d_normpart, h->d_normpart2, h->d_dinv2, h->d_scell2, h->d_colpart2, h->d_smax2, h->d_xch, h->d_xcc, h->d_batchflag, h->d_chi_in, h->d_n1, h->d_gpark, h->d_morder, h->d_inv_tnorm, h->d_ones, h->d_z, h->d_rb, h->d_cls, h->d_rep, h->d_coop, h->d_Dt, h->d_xi, h->d_wq, h->d_gb, h->d_cellflag, h->d_celllist, h->d_gram, h->d_Sf, h->d_dinv, h->d_scell, h->d_colpart, h->d_wgtab, h->d_prog, h->d_splan, h->d_xinit, h->d_H0p, h->d_Hcp, h->d_vecs, h->d_H0q, h->d_Hcq, h->d_H0q3, h->d_Hcq3, h->d_park2, h->d_park3, h->d_H0f, h->d_Hcf, h->d_H0t, h->d_Hct, h->d_dts, h->d_shape, h->d_weights, h->d_psi0,
+    void *bufs[] = {h->d_celldeg, h->d_xcc_sw, h->d_scanF, h->d_scan_fw, h->d_scan_bw, h->d_dte, h->d_normpart, h->d_xch, h->d_xcc, h->d_batchflag, h->d_chi_in, h->d_n1, h->d_gpark, h->d_morder, h->d_inv_tnorm, h->d_ones, h->d_z, h->d_rb, h->d_cls, h->d_rep, h->d_Dt, h->d_xi, h->d_wq, h->d_gb, h->d_cellflag, h->d_celllist, h->d_gram, h->d_Sf, h->d_dinv, h->d_scell, h->d_colpart, h->d_wgtab, h->d_prog, h->d_splan, h->d_xinit, h->d_H0p, h->d_Hcp, h->d_vecs, h->d_H0q, h->d_Hcq, h->d_H0q3, h->d_Hcq3, h->d_park2, h->d_park3, h->d_H0f, h->d_Hcf, h->d_H0t, h->d_Hct, h->d_dts, h->d_shape, h->d_weights, h->d_psi0,
                     h->d_target, h->d_eps, h->d_U, h->d_fw, h->d_bw, h->d_tg, h->d_ret, h->d_f,
                     h->d_rho, h->d_tq, h->d_dJdt};
     for (void *b : bufs)
@@ -1722,11 +1636,10 @@ int grape_create(grape_handle **out, const grape_problem *p) try {
             h->asm18g = !(envg && !atoi(envg));
         }
         {
-            const char *envp = getenv("GRAPE_EXPM_PERSIST"), *envl = getenv("GRAPE_EXPM_LDS_PAD"), *envx = getenv("GRAPE_CHEBY_XMODE");
+            const char *envp = getenv("GRAPE_EXPM_PERSIST"), *envl = getenv("GRAPE_EXPM_LDS_PAD");
             const char *envk = getenv("GRAPE_TEST_HOOKS");
             h->expm_persist = envp ? atoi(envp) != 0 : true;
             h->expm_lds_pad_kb = envl ? std::max(0, atoi(envl)) : 0;
-            h->cheby_xmode = envx ? atoi(envx) & 1 : 1;
             h->test_hooks = envk && atoi(envk) == 1;
             const char *envgr = getenv("GRAPE_GRAPH");
             h->graph_ok = !(envgr && atoi(envgr) == 0) && !h->test_hooks;
@@ -1854,7 +1767,6 @@ int grape_create(grape_handle **out, const grape_problem *p) try {
                 const char *env4 = getenv("GRAPE_DERIV4");
                 if (h->large && !h->series && (NP == 128 || NP == 256) && !(env4 && atoi(env4) == 0)) {
                     h->deriv4_blocks = (int)std::min<long>(nbatch, h->num_cus);
-                    if (const char *envb4 = getenv("GRAPE_DERIV4_BLOCKS")) h->deriv4_blocks = (int)std::min<long>(nbatch, std::max(1, atoi(envb4)));
                     const int RT3 = NP / 16, KS3 = NP / 4;
                     auto pack3 = [&](const double *src, int nmat, std::vector<double> &dst, bool dagger) {
                         // [mat][rt][ks][64 lanes x (re, im) | 64 lanes x (re + im)]: element (row 16 rt + (lane & 15), column
@@ -1943,57 +1855,23 @@ int grape_create(grape_handle **out, const grape_problem *p) try {
     }
     if (h->large && !h->series) {
         const long ncell = (long)h->KC * N_T;
-        // chunk scratch: 6 GB (a launch of 635 cells at N = 256 has tails of ~1 % of its length).  GRAPE_LG_LANES=2: two lanes of
-        // chunks of 1 GB on two streams, each covering the other's launch tails -- phase A of the C5 shard 143.4 -> 138.6 ms before
-        // the combinations moved into the epilogue of the products, 128.8 -> 127.5 ms since; off by default (1 % for a second
-        // scratch set, and kernel statistics in which the launches of the two lanes overlap)
-        const char *envl = getenv("GRAPE_LG_LANES"), *envsp0 = getenv("GRAPE_LG_SPEC");
-        const bool want_lanes = h->t18 && !(envsp0 && atoi(envsp0) == 0) && envl && atoi(envl) >= 2;
-        double scratch_bytes = want_lanes ? 1.0e9 : 6.0e9;
-        if (const char *envg = getenv("GRAPE_LG_SCRATCH_GB")) scratch_bytes = std::max(0.1, atof(envg)) * 1e9;   // (experiments: launch tails against scratch)
-        const long cap = std::max<long>(1, (long)(scratch_bytes / (9.0 * 2.0 * pp * 8.0)));
+        // chunk scratch: 6 GB (a launch of 635 cells at N = 256 has tails of ~1 % of its length).  Measured in round 5 and
+        // removed: a second lane of 1 GB chunks on a second stream to cover those tails (phase A of the C5 shard 128.8 ->
+        // 127.5 ms, for a second scratch set and overlapping kernel statistics)
+        const long cap = std::max<long>(1, (long)(6.0e9 / (9.0 * 2.0 * pp * 8.0)));
         h->chunk = (int)std::min<long>(ncell, std::min<long>(cap, 16384));
         if (const char *envc = getenv("GRAPE_LG_CHUNK")) h->chunk = (int)std::max<long>(1, std::min<long>(h->chunk, atol(envc)));   // (experiments: working set against the Infinity Cache)
         for (auto &b : h->d_lg) CCHK(dmalloc(&b, (size_t)h->chunk * 2 * pp));
         CCHK(dmalloc(&h->d_dinv, (size_t)h->chunk * 2 * 4096));
         CCHK(dmalloc(&h->d_scell, (size_t)h->chunk + 1));
-        {
-            const char *envsp = getenv("GRAPE_LG_SPEC"), *envsn = getenv("GRAPE_LG_SN");
-            h->lg_spec = h->t18 && !(envsp && atoi(envsp) == 0);
-            if (const char *envf = getenv("GRAPE_LG_FUSE")) h->lg_fuse = atoi(envf) != 0;
-            if (const char *envp = getenv("GRAPE_LG_POW")) h->lg_pow = atoi(envp) != 0;
-            if (h->lg_spec) CCHK(dmalloc(&h->d_colpart, (size_t)h->chunk * 2 * LG_PARTS * NP));
-            // summed controls of every time step for the generator formation (polynomial route, shared control operators):
-            // N_T 2 NP^2 doubles -- 2.1 GB at C5 -- when that is a small part of what the propagators take anyway
-            {
-                const char *envf2 = getenv("GRAPE_LG_FORM2");
-                h->lg_form2 = h->t18 && !p->hc_per_traj && L <= 4 && NP % LG_FORM_ROWS == 0 && !(envf2 && atoi(envf2) == 0);
-                if (h->lg_form2) CCHK(dmalloc(&h->d_normpart, (size_t)h->chunk * (NP / LG_FORM_ROWS) * NP));
-            }
-            const double sn_bytes = (double)N_T * 2.0 * (double)pp * 8.0;
-            if (!h->lg_form2 && h->t18 && !p->hc_per_traj && !(envsn && atoi(envsn) == 0) && sn_bytes <= 0.25 * (double)h->KC * N_T * (double)pp * 16.0 + 1e9)
-                CCHK(dmalloc(&h->d_Sf, (size_t)N_T * 2 * pp));
-            // second lane: only when there is more than one chunk to overlap and the second scratch set is small against the
-            // device (the propagators themselves take K N_T pp 16 bytes)
-            size_t free_b = 0, total_b = 0;
-            CCHK(hipMemGetInfo(&free_b, &total_b));
-            const double lane_bytes = 9.0 * (double)h->chunk * 2.0 * (double)pp * 8.0;
-            if (want_lanes && h->lg_spec && ncell > h->chunk &&
-                lane_bytes + (double)h->KC * N_T * (double)pp * 16.0 + 4e9 < (double)free_b) {
-                h->lg_lanes = 2;
-                for (auto &b : h->d_lg2) CCHK(dmalloc(&b, (size_t)h->chunk * 2 * pp));
-                CCHK(dmalloc(&h->d_dinv2, (size_t)h->chunk * 2 * 4096));
-                CCHK(dmalloc(&h->d_scell2, (size_t)h->chunk + 1));
-                CCHK(dmalloc(&h->d_colpart2, (size_t)h->chunk * 2 * LG_PARTS * NP));
-                CCHK(dmalloc(&h->d_smax2, 1));
-                if (h->lg_form2) CCHK(dmalloc(&h->d_normpart2, (size_t)h->chunk * (NP / LG_FORM_ROWS) * NP));
-                if (!h->lg_stream2) {
-                    CCHK(hipStreamCreateWithFlags(&h->lg_stream2, hipStreamNonBlocking));
-                    CCHK(hipEventCreateWithFlags(&h->lg_ev_fork, hipEventDisableTiming));
-                    CCHK(hipEventCreateWithFlags(&h->lg_ev_join, hipEventDisableTiming));
-                }
-            }
-        }
+        if (h->t18) CCHK(dmalloc(&h->d_colpart, (size_t)h->chunk * 2 * LG_PARTS * NP));
+        h->lg_form2 = h->t18 && !p->hc_per_traj && L <= 4 && NP % LG_FORM_ROWS == 0;
+        if (h->lg_form2) CCHK(dmalloc(&h->d_normpart, (size_t)h->chunk * (NP / LG_FORM_ROWS) * NP));
+        // summed controls of every time step for the generator formation (polynomial route, shared control operators):
+        // N_T 2 NP^2 doubles -- 2.1 GB at C5 -- when that is a small part of what the propagators take anyway
+        const double sn_bytes = (double)N_T * 2.0 * (double)pp * 8.0;
+        if (!h->lg_form2 && h->t18 && !p->hc_per_traj && sn_bytes <= 0.25 * (double)h->KC * N_T * (double)pp * 16.0 + 1e9)
+            CCHK(dmalloc(&h->d_Sf, (size_t)N_T * 2 * pp));
     }
 
     std::vector<double> dts(N_T);
@@ -2156,7 +2034,7 @@ int grape_create(grape_handle **out, const grape_problem *p) try {
     h->asm18gp = h->asm18g && p_direct;
     {
         const char *enve = getenv("GRAPE_DERIV_ECON");
-        const bool lg_ok = h->large && h->t18 && h->herm && h->lg_spec && !h->series;
+        const bool lg_ok = h->large && h->t18 && h->herm && !h->series;
         // (the compiled four-product kernel of three and four tiles per side writes the same verdicts: expm_t18_kernel<.., T16>)
         const bool t16c_ok = h->t16 && h->t18 && h->herm && !h->large && !h->series && (h->NT >= 3 || (h->NT == 2 && h->t18_small));
         h->deriv_econ = (h->asm16 || lg_ok || t16c_ok) && p->gradient_method == GRAPE_GRAD_GRADGEN && h->taylor_tol >= 1e-16 && h->d_batchflag &&
@@ -2299,24 +2177,12 @@ int grape_create(grape_handle **out, const grape_problem *p) try {
         const int R = h->NP / S;
         const char *env = getenv("GRAPE_SWEEP_COOP");
         if (S >= 2 && R <= 64 && !(env && atoi(env) == 0)) {
+            // one split for both directions: with armed storage rows and stores into the XCD's L2 (round 6, C5 shard) the
+            // most siblings are fastest both ways -- forward 32 / 16 / 8 siblings 3.5 / 4.3 / 6.9 ms, backward 5.4 / 5.7 / 7.1 ms
+            // (round 5, step counters: 7.1 + 9.6 ms, with fewer siblings forward)
             h->coop_S = S;
-            if (const char *envx = getenv("GRAPE_COOP_XMODE")) h->coop_xmode = atoi(envx) != 0;
             h->coop_nw = R >= 16 ? 16 : R;
             h->coop_rpw = R / h->coop_nw;
-            // the two directions have different optima (round 5, C5 shard, forward / backward ms by siblings: 32: 8.5 / 9.6,
-            // 16: 7.3 / 11.1, 8: 10.2 / 11.0, 4: 15.3 / -): a step is a latency chain whose length grows with the siblings that
-            // have to meet; the forward slice is whole rows (a wave sum per row), the backward one columns (tools/coop_s.sh)
-            // round 6 (armed storage rows instead of step counters, stores into the XCD's L2): forward 32 / 16 / 8 siblings
-            // 3.5 / 4.3 / 6.9 ms, backward 32 / 16 / 8: 5.4 / 5.7 / 7.1 ms (round 5: 7.1 + 9.6 ms)
-            int Sf = h->coop_xmode ? S : (S == 32 ? 16 : S), Sb = S;
-            if (const char *e_ = getenv("GRAPE_COOP_S_FW")) Sf = atoi(e_);
-            if (const char *e_ = getenv("GRAPE_COOP_S_BW")) Sb = atoi(e_);
-            auto valid = [&](int s_) { return s_ >= 2 && s_ <= S && (s_ & (s_ - 1)) == 0 && h->NP / s_ <= 64; };
-            if (!valid(Sf)) Sf = S;
-            if (!valid(Sb)) Sb = S;
-            h->coop_S = Sb; h->coop_nw = h->NP / Sb >= 16 ? 16 : h->NP / Sb; h->coop_rpw = (h->NP / Sb) / h->coop_nw;
-            h->coop_S_fw = Sf; h->coop_nw_fw = h->NP / Sf >= 16 ? 16 : h->NP / Sf; h->coop_rpw_fw = (h->NP / Sf) / h->coop_nw_fw;
-            CCHK(dmalloc(&h->d_coop, (size_t)2 * K));
             CCHK(dmalloc(&h->d_xcc_sw, (size_t)2 * K * 32));
         }
     }
@@ -2532,7 +2398,7 @@ int grape_forward_device(grape_handle *h, const double *d_pulsevals, double *d_o
     sa.store = h->d_fw; sa.tau = (double2 *)d_out; sa.f = nullptr; sa.rho = h->d_rho; sa.flags = h->d_flags;
     sa.chi_min_norm = h->chi_min_norm;
     sa.K = h->K; sa.K_total = h->K_total; sa.N = h->N; sa.N_T = h->N_T; sa.functional = h->p.functional;
-    sa.xmode = h->coop_xmode; sa.xcc = h->d_xcc_sw;
+    sa.xcc = h->d_xcc_sw;
     if (walk_fuse & 1) sa.resume = h->d_prog;
     if (h->test_hooks) {   // fault injection (test suite only, see grape_handle::test_hooks)
         const char *envd = getenv("GRAPE_TEST_DROP_SIBLING");
@@ -2576,8 +2442,8 @@ int grape_forward_device(grape_handle *h, const double *d_pulsevals, double *d_o
         case 64: e = launch_sweep<64>(sa, false, s); break;
         default:
             if (h->coop_S)
-                e = h->NP == 128 ? launch_coop<2>(sa, false, h->coop_S_fw, h->coop_rpw_fw, h->coop_nw_fw, h->d_coop, s)
-                                 : launch_coop<4>(sa, false, h->coop_S_fw, h->coop_rpw_fw, h->coop_nw_fw, h->d_coop, s);
+                e = h->NP == 128 ? launch_coop<2>(sa, false, h->coop_S, h->coop_rpw, h->coop_nw, s)
+                                 : launch_coop<4>(sa, false, h->coop_S, h->coop_rpw, h->coop_nw, s);
             else {
                 hipLaunchKernelGGL((sweep_lg_kernel<false>), dim3(sa.K), dim3(1024), 0, s, sa, h->NP);
                 e = hipGetLastError();
@@ -2634,7 +2500,7 @@ int backward_device_impl(grape_handle *h, const double *d_f, double *d_G, hipStr
     sa.lambda_b = h->xi_user ? h->lambda_user : h->p.lambda_b;
     sa.chi_min_norm = h->chi_min_norm;
     sa.K = h->K; sa.K_total = h->K_total; sa.N = h->N; sa.N_T = h->N_T; sa.functional = h->p.functional;
-    sa.xmode = h->coop_xmode; sa.xcc = h->d_xcc_sw ? h->d_xcc_sw + (size_t)h->K * 32 : nullptr;
+    sa.xcc = h->d_xcc_sw ? h->d_xcc_sw + (size_t)h->K * 32 : nullptr;
     sa.chi_in = d_chi;
     phase_begin(h, 2, s);
     // (a caller-supplied chi or xi breaks the linearity the concurrent sweeps rely on: the backward sweep runs here)
@@ -2666,8 +2532,8 @@ int backward_device_impl(grape_handle *h, const double *d_f, double *d_G, hipStr
         case 64: e = launch_sweep<64>(sa, true, s); break;
         default:
             if (h->coop_S)
-                e = h->NP == 128 ? launch_coop<2>(sa, true, h->coop_S, h->coop_rpw, h->coop_nw, h->d_coop + h->K, s)
-                                 : launch_coop<4>(sa, true, h->coop_S, h->coop_rpw, h->coop_nw, h->d_coop + h->K, s);
+                e = h->NP == 128 ? launch_coop<2>(sa, true, h->coop_S, h->coop_rpw, h->coop_nw, s)
+                                 : launch_coop<4>(sa, true, h->coop_S, h->coop_rpw, h->coop_nw, s);
             else {
                 hipLaunchKernelGGL((sweep_lg_kernel<true>), dim3(sa.K), dim3(1024), 0, s, sa, h->NP);
                 e = hipGetLastError();

@@ -420,60 +420,18 @@ __global__ void __launch_bounds__(256) lg_norm1_kernel(LgFormArgs a, const doubl
 // ---- polynomial route of the blocked path (five products, no solve; scheme and coefficients: grape_t18_coeffs.h) ----
 // Scaling of one cell from the powers: Hermitian generators beta = min(||A2||_1^(1/2), ||A6||_1^(1/6)) against theta = 2
 // (spectral bound, see grape_t18.hip.h); general matrices alpha = min(||A||_1, max(||A2||_1^(1/2), ||A3||_1^(1/3))) against
-// theta = 1.09.  P and Q are the two powers whose column sums are needed (A2 and A6, or A2 and A3); |re| + |im| stands in
-// for the modulus (an upper bound of the norm is all the theory needs).  One 256-thread workgroup per cell, thread j
-// owns column j.
+// theta = 1.09.  The column sums of the two powers P and Q (A2 and A6, or A2 and A3) are taken by the combination pass
+// below; |re| + |im| stands in for the modulus (an upper bound of the norm is all the theory needs).
 struct LgT18ScaleArgs {
-    const double *P, *Q;   // [ncell][2][NP*NP]
     const double *norm1;   // ||A||_1 per cell (general matrices), nullptr for Hermitian generators
     int *s_cell;
     int *flags;
-    int *smax;             // the largest squaring count of the evaluation so far, per lane of chunks (flags + 1 for the first lane)
+    int *smax;             // the largest squaring count of the evaluation so far (flags + 1)
     unsigned long long *stats;
-    int NP, qpow;          // Q = A^qpow (6 or 3)
+    int NP;
     double theta;
     unsigned long long mfma_per_cell, mfma_per_sq;   // executed matrix instructions (all waves): statistics
 };
-__global__ void __launch_bounds__(256) lg_t18_scale_kernel(LgT18ScaleArgs a) {
-    __shared__ double cs[2][256];
-    const int tid = threadIdx.x, NP = a.NP;
-    const size_t pp = (size_t)NP * NP;
-    const double *P = a.P + (size_t)blockIdx.x * 2 * pp, *Q = a.Q + (size_t)blockIdx.x * 2 * pp;
-    double sp = 0., sq = 0.;
-    if (tid < NP) {
-#pragma unroll 8
-        for (int i = 0; i < NP; ++i) {
-            const size_t o = (size_t)i * NP + tid;
-            sp += fabs(P[o]) + fabs(P[pp + o]);
-            sq += fabs(Q[o]) + fabs(Q[pp + o]);
-        }
-    }
-    cs[0][tid] = sp; cs[1][tid] = sq;
-    __syncthreads();
-    if (tid == 0) {
-        double np_ = 0., nq = 0.;
-        for (int j = 0; j < NP; ++j) { np_ = fmax(np_, cs[0][j]); nq = fmax(nq, cs[1][j]); }
-        np_ *= 1.0 + 1e-9; nq *= 1.0 + 1e-9;   // rounding of the computed powers
-        int s = 0;
-        bool bad = false;
-        if (!a.norm1) {   // beta <= theta 2^s  <=>  ||A2|| <= (theta 2^s)^2  or  ||A6|| <= (theta 2^s)^6
-            double t2 = a.theta * a.theta, t6 = t2 * t2 * t2;
-            while (!(np_ <= t2 || nq <= t6) && s < 64) { ++s; t2 *= 4.0; t6 *= 64.0; }
-            bad = s >= 64;
-        } else {          // alpha <= theta 2^s  <=>  ||A|| <= theta 2^s  or  (||A2|| <= (theta 2^s)^2 and ||A3|| <= (theta 2^s)^3)
-            const double n1 = a.norm1[blockIdx.x];
-            double t1 = a.theta, t2 = t1 * t1, t3 = t2 * t1;
-            while (!(n1 <= t1 || (np_ <= t2 && nq <= t3)) && s < 64) { ++s; t1 *= 2.0; t2 *= 4.0; t3 *= 8.0; }
-            bad = s >= 64;
-        }
-        if (bad) { s = 0; atomicOr(&a.flags[0], 64); }   // NaN / overflow in the generator
-        a.s_cell[blockIdx.x] = s;
-        atomicMax(a.smax, s);
-        stat_add(a.stats, 12, a.mfma_per_cell + (unsigned long long)s * a.mfma_per_sq);
-        stat_add(a.stats, 13, (unsigned long long)s);
-        stat_add(a.stats, 14, 1ull);
-    }
-}
 
 // The five linear combinations of the scaled powers (A / 2^s)^k = A^k 2^(-k s) in ONE streaming pass (4 reads, 5 writes per
 // element at the HBM rate): B1, B5 (operands of the fourth product), B4, B3, B2 (added in the epilogues of the fourth and
@@ -489,23 +447,8 @@ struct LgT18OperandsArgs {
     size_t per_cell;   // 2 * NP * NP
     size_t n;          // per_cell * cells
 };
-__global__ void lg_t18_operands_kernel(LgT18OperandsArgs a) {
-    const size_t pp = a.per_cell / 2;
-    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < a.n; i += (size_t)gridDim.x * blockDim.x) {
-        const size_t cell = i / a.per_cell, o = i - cell * a.per_cell;
-        const int s = a.s_cell[cell];
-        const double f1 = ldexp(1.0, -s), f2 = f1 * f1, f3 = f2 * f1, f6 = f3 * f3;
-        const double x1 = f1 * a.A[i], x2 = f2 * a.A2[i], x3 = f3 * a.A3[i], x6 = f6 * a.A6[i];
-        const bool diag = o < pp && (o / a.NP) == (o % a.NP);   // real plane, row == column
-        a.B1[i] = a.a[0] * x1 + a.a[1] * x2 + a.a[2] * x3;
-        a.B5[i] = a.e[0] * x2 + a.e[1] * x3 + a.e[2] * x6;
-        a.B4[i] = a.d[1] * x1 + a.d[2] * x2 + a.d[3] * x3 + a.d[4] * x6 + (diag ? a.d[0] : 0.0);
-        a.B3[i] = a.c[1] * x1 + a.c[2] * x2 + a.c[3] * x3 + a.c[4] * x6 + (diag ? a.c[0] : 0.0);
-        a.B2[i] = a.b[1] * x1 + a.b[2] * x2 + a.b[3] * x3 + a.b[4] * x6 + (diag ? a.b[0] : 0.0);
-    }
-}
-// Round 5: the norm pass rides in the combination pass.  lg_t18_scale_kernel read two powers of every cell (33.6 GB per
-// C5-shard evaluation, 6.4 ms) only to find, at the benchmark's norms, that no cell needs a squaring.  Now the combination
+// Round 5: the norm pass rides in the combination pass.  A separate norm pass read two powers of every cell (33.6 GB per
+// C5-shard evaluation, 6.4 ms; removed) only to find, at the benchmark's norms, that no cell needs a squaring.  Now the combination
 // pass forms B1 .. B5 SPECULATIVELY for s = 0 and takes the column sums of the two powers it reads anyway on its way;
 // lg_t18_decide_kernel turns the partial sums into the squaring count of every cell (same bound, same statistics), and a
 // second launch of the combination pass redoes the cells with s > 0 from the intact powers (it leaves at once for the
@@ -557,11 +500,11 @@ __global__ void __launch_bounds__(256) lg_t18_operands2_kernel(LgT18Operands2Arg
 }
 // Round 5 (second half): the launch that writes the last power forms the combinations in its epilogue (lg_gemm_asm `comb`,
 // asm/gen_lg.py: every block, with the column sums of its 64 rows in row part bi of the column-sum scratch); the pass above
-// is then only launched for the cells that need a scaling (redo = 1) and as the twin (GRAPE_LG_FUSE=0).
-// the decision of lg_t18_scale_kernel from the partial column sums (one workgroup per cell, thread j owns column j)
+// is then only launched for the cells that need a scaling (redo = 1) and for the compiled products (GRAPE_LG_ASM=0).
+// the scaling decision from the partial column sums (one workgroup per cell, thread j owns column j)
 struct LgT18DecideArgs {
     const double *colpart;
-    LgT18ScaleArgs s;      // P, Q unused
+    LgT18ScaleArgs s;
     int nparts;            // row parts that were written: LG_PARTS (lg_t18_operands2_kernel) or NP / 64 (fused epilogue)
     // round 6 -- the economized derivative series (deriv_econ_kernel): for a Hermitian cell without scaling the smallest
     // segment theta_i with ||A^2|| <= theta_i^2 or ||A^6|| <= theta_i^6 (the spectral radius of a normal matrix is at most
@@ -797,8 +740,7 @@ __global__ void lg_store_u_kernel(const double *X, double2 *U, int NP, size_t nc
 
 // the squaring plan of the launch sequence was too short for the counts found on the device: flag the evaluation
 // (bit 5) so that the host repeats it with a longer plan
-__global__ void lg_plan_check_kernel(int *flags, int cap, const int *smax2) {
-    if (smax2 && *smax2 > flags[1]) flags[1] = *smax2;   // (second lane of chunks: the host sizes its next plan from flags[1])
+__global__ void lg_plan_check_kernel(int *flags, int cap) {
     if (flags[1] > cap) atomicOr(&flags[0], 32);
 }
 
@@ -924,8 +866,9 @@ __global__ void __launch_bounds__(1024) sweep_lg_kernel(SweepArgs a, int NP) {
 // trajectory: each owns R = NP / S rows of the state (forward: rows of U_n; backward: columns of U_n,
 // i.e. rows of U_n^dagger), reads only its 16 * R * NP bytes of U_n per step and publishes its slice of
 // the new state straight into the storage array, which is what the next step of every sibling reads.
-// One counter per trajectory orders the steps (agent-scope fences around a relaxed atomic); the U slice
-// of the next step is requested before the wait, so the exchange latency overlaps the HBM stream.
+// The published slices are the signal: the storage rows a sweep will write are armed with an all-ones
+// pattern before the launch, and a reader polls the elements it needs until none shows it (coop_poll).
+// The U slices of the next two steps are requested ahead, so the exchange latency overlaps the HBM stream.
 // Placement: block b runs on XCD b % 8 (round-robin dispatch), so all siblings of a trajectory are given
 // the same b % 8 and meet in one L2.  The grid never exceeds one workgroup per CU: all siblings are
 // resident, and the spin is bounded anyway (flag bit 8 -> GRAPE_ERR_HIP) so that the grid always drains.
@@ -933,9 +876,8 @@ __global__ void __launch_bounds__(1024) sweep_lg_kernel(SweepArgs a, int NP) {
 //   backward: chi_{n-1} = U_n^dagger chi_n   (optimize.jl:881), boundary :848-868, xi inhomogeneity :897-908
 // ---------------------------------------------------------------------------------------
 // Slice exchange without whole-cache maintenance: the slices are written and read with agent-scope relaxed
-// atomics (write-through / cache-bypassing accesses), a release is then just "my stores are acknowledged"
-// (s_waitcnt vmcnt(0)) before the barrier that precedes the counter increment.  Agent-scope FENCES would
-// write back and invalidate the whole L2 on every step.
+// atomics (write-through / cache-bypassing accesses).  Agent-scope FENCES would write back and invalidate
+// the whole L2 on every step.
 __device__ __forceinline__ void coop_store(double2 *p, double2 v) {
     __hip_atomic_store(&p->x, v.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __hip_atomic_store(&p->y, v.y, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -946,16 +888,8 @@ __device__ __forceinline__ double2 coop_load(const double2 *p) {
     v.y = __hip_atomic_load(&p->y, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     return v;
 }
-__device__ __forceinline__ bool coop_wait(unsigned *cnt, unsigned target, int *flags) {
-    for (int spin = 0; spin < (1 << 22); ++spin) {
-        if (__hip_atomic_load(cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= target) return true;
-        __builtin_amdgcn_s_sleep(2);
-    }
-    atomicOr(&flags[0], 8);
-    return false;
-}
 
-// round 6 (SweepArgs::xmode = 1): poll ONE element of the state until it no longer shows the arming pattern (all ones in
+// poll ONE element of the state until it no longer shows the arming pattern (all ones in
 // either half: a 16-byte element is published as two 8-byte stores).  Bounded: a sibling that never publishes raises bit 3.
 #define COOP_SENTINEL 0xFFFFFFFFFFFFFFFFull
 __device__ __forceinline__ double2 coop_poll(const double2 *p, int *flags, bool &gone) {
@@ -979,13 +913,12 @@ __device__ __forceinline__ void coop_store_l2(double2 *p, double2 v) {
 }
 
 template <int CPL, int RPW, int NW, bool BACKWARD>
-__global__ void __launch_bounds__(64 * NW) sweep_coop_kernel(SweepArgs a, int S, unsigned *cnt) {
+__global__ void __launch_bounds__(64 * NW) sweep_coop_kernel(SweepArgs a, int S) {
     constexpr int NP = 64 * CPL, T = 64 * NW, R = NW * RPW, E = CPL * RPW, NG = T / R;
     __shared__ double2 x[NP];
     __shared__ double2 part[T > NP ? T : NP];
     __shared__ double sc[2];
     __shared__ int xl;
-    bool gone = false;   // (thread 0) a sibling did not arrive within the spin limit
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
@@ -995,11 +928,10 @@ __global__ void __launch_bounds__(64 * NW) sweep_coop_kernel(SweepArgs a, int S,
     const int r0 = s * R;   // first row (forward) / column (backward) of this workgroup's slice
     const double2 *Uk = a.U + (size_t)(a.cls ? a.cls[k] : k) * a.N_T * NP * NP;
     double2 *st = a.store + (size_t)k * (a.N_T + 1) * NP;
-    unsigned *ck = cnt + k;
     // ---- do all siblings of this trajectory share an XCD (and with it an L2)?  Checked, not assumed. ----
     if (tid == 0) {
         int same = 0;
-        if (a.xcc && a.xmode) {
+        if (a.xcc) {
             int *xc = a.xcc + (size_t)k * 32;
             const int mine = (int)(__builtin_amdgcn_s_getreg((3 << 11) | 20) & 0xf);   // HW_REG_XCC_ID[3:0]
             __hip_atomic_store(&xc[s], mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1079,8 +1011,7 @@ __global__ void __launch_bounds__(64 * NW) sweep_coop_kernel(SweepArgs a, int S,
     };
     load_u(u2[0], BACKWARD ? a.N_T - 1 : 0);
     if (a.N_T > 1) load_u(u2[1], BACKWARD ? a.N_T - 2 : 1);
-    const bool sentinel = a.xmode != 0;
-    bool lost = false;   // (any thread, sentinel mode) an element never arrived
+    bool lost = false;   // (any thread) an element never arrived
 
     for (int step0 = 0; step0 < a.N_T; step0 += 2) {
 #pragma unroll
@@ -1092,17 +1023,9 @@ __global__ void __launch_bounds__(64 * NW) sweep_coop_kernel(SweepArgs a, int S,
         const int nout = BACKWARD ? n : n + 1;       // storage row of the new state
         if (step > 0) {
             const int nin = BACKWARD ? n + 1 : n;
-            if (sentinel) {
-                // the state of the previous step: every element is polled by the thread that needs it in the LDS copy
-                if (tid < NP) x[tid] = coop_poll(&st[(size_t)nin * NP + tid], a.flags, lost);
-                __syncthreads();
-            } else {
-                // wait until all S siblings have published step - 1, then fetch the full state
-                if (tid == 0 && !gone) gone = !coop_wait(ck, (unsigned)(S * step), a.flags);   // a time-out is final: no further waits
-                __syncthreads();
-                if (tid < NP) x[tid] = coop_load(&st[(size_t)nin * NP + tid]);
-                __syncthreads();
-            }
+            // the state of the previous step: every element is polled by the thread that needs it in the LDS copy
+            if (tid < NP) x[tid] = coop_poll(&st[(size_t)nin * NP + tid], a.flags, lost);
+            __syncthreads();
         }
         double2 y = make_double2(0., 0.);
         if (!BACKWARD) {
@@ -1145,27 +1068,17 @@ __global__ void __launch_bounds__(64 * NW) sweep_coop_kernel(SweepArgs a, int S,
             }
             (void)y;
         }
-        if (!sentinel) {
-            __builtin_amdgcn_s_waitcnt(0x0f70);   // vmcnt(0): this thread's slice elements are acknowledged ...
-            __syncthreads();
-            if (tid == 0) __hip_atomic_fetch_add(ck, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // ... before the count
-        } else {
-            __syncthreads();                      // (x is rewritten by the next step's poll)
-        }
+        __syncthreads();                          // (x is rewritten by the next step's poll)
         // request the U slice of the step after next now: it does not depend on the state and streams in during the exchanges
         if (step + 2 < a.N_T) load_u(u2[d], BACKWARD ? n - 2 : n + 2);
       }
     }
 
     if (!BACKWARD && s == 0) {   // tau_k = <target_k | Psi_k(T)>
-        if (!sentinel) {
-            if (tid == 0 && !gone) coop_wait(ck, (unsigned)(S * a.N_T), a.flags);
-            __syncthreads();
-        }
         double pr = 0., pi = 0.;
         if (tid < a.N) {
             const double2 t = a.target[(size_t)k * a.N + tid];
-            const double2 p = sentinel ? coop_poll(&st[(size_t)a.N_T * NP + tid], a.flags, lost) : coop_load(&st[(size_t)a.N_T * NP + tid]);
+            const double2 p = coop_poll(&st[(size_t)a.N_T * NP + tid], a.flags, lost);
             pr = t.x * p.x + t.y * p.y;
             pi = t.x * p.y - t.y * p.x;
         }
