@@ -33,7 +33,7 @@ EXPORTS = ["grape_create", "grape_destroy", "grape_eval", "grape_forward", "grap
            "grape_get_tau_grads", "grape_get_storage", "grape_get_timings", "grape_reset_timings", "grape_get_work",
            "grape_last_error", "grape_abi_version", "grape_set_fused_sweeps", "grape_get_sums", "grape_backward_xi",
            "grape_get_final_states", "grape_backward_chi",
-           "grape_get_time_gradient", "grape_set_tlist"]
+           "grape_get_time_gradient", "grape_set_tlist", "grape_eval_batch", "grape_get_batch_info"]
 
 
 class GrapeHipError(RuntimeError):
@@ -97,7 +97,7 @@ def build_asm(verbose: bool = False, workdir: str | None = None) -> str:
 def _sources():
     srcs = [os.path.join(_CSRC, f) for f in ("grape_hip.hip", "grape_t18.hip", "grape_kernels.hip.h", "grape_large.hip.h",
                                              "grape_series.hip.h", "grape_cheby.hip.h", "grape_t18.hip.h", "grape_t18_coeffs.h",
-                                             "grape_deriv3.hip.h", "grape_timegrad.hip.h", os.path.join("asm", "gen_t16.py"), os.path.join("asm", "gen_t16p.py"), os.path.join("asm", "gen_t18g.py"), os.path.join("asm", "gen_t18gp.py"), os.path.join("asm", "gen_d3.py"), os.path.join("asm", "gen_d3s.py"), os.path.join("asm", "gen_lg.py"), os.path.join("asm", "gen_d4.py"), os.path.join("asm", "gcn.py"))]
+                                             "grape_deriv3.hip.h", "grape_timegrad.hip.h", "grape_batch.hip.h", os.path.join("asm", "gen_t16.py"), os.path.join("asm", "gen_t16p.py"), os.path.join("asm", "gen_t18g.py"), os.path.join("asm", "gen_t18gp.py"), os.path.join("asm", "gen_d3.py"), os.path.join("asm", "gen_d3s.py"), os.path.join("asm", "gen_lg.py"), os.path.join("asm", "gen_d4.py"), os.path.join("asm", "gcn.py"))]
     return srcs, os.path.join(_HERE, "..", "include", "grape_hip.h")
 
 
@@ -204,6 +204,8 @@ def load_library():
     lib.grape_backward_xi.argtypes = [vp, vp, vp, vp, C.c_double, vp]
     lib.grape_get_time_gradient.argtypes = [vp, vp]
     lib.grape_set_tlist.argtypes = [vp, vp]
+    lib.grape_eval_batch.argtypes = [vp, ip, vp, vp, vp, vp]
+    lib.grape_get_batch_info.argtypes = [vp, vp, ip]
     lib.grape_last_error.argtypes = [vp]
     lib.grape_last_error.restype = C.c_char_p
     lib.grape_abi_version.restype = ip
@@ -337,6 +339,28 @@ class GrapeHip:
                                        None if G is None else G.ctypes.data, tau.ctypes.data,
                                        None if psiT is None else psiT.ctypes.data))
         return (J.value, G, tau, psiT) if want_psiT else (J.value, G, tau)
+
+    def eval_batch(self, pulsevals, gradient=True):
+        """P pulse vectors through this handle's problem in one call (grape_eval_batch): ``pulsevals`` [P, L*N_T] ->
+        (J [P], G [P, L*N_T] or None, tau [P, K]); row p is what ``eval(pulsevals[p])`` returns.  Small systems (N <= 16) run
+        all sets side by side on the GPU, everything else one ordinary evaluation per set (``batch_info()["route"]``)."""
+        x = np.ascontiguousarray(pulsevals, dtype=np.float64)
+        if x.ndim != 2 or x.shape[1] != self.L * self.N_T:
+            raise ValueError(f"pulsevals must be [P, L*N_T] = [P, {self.L * self.N_T}], got {x.shape}")
+        P = x.shape[0]
+        J = np.empty(P)
+        G = np.empty((P, self.L * self.N_T)) if gradient else None
+        tau = np.empty((P, self.K), dtype=np.complex128)
+        self._chk(self._lib.grape_eval_batch(self._h, P, x.ctypes.data, J.ctypes.data,
+                                             None if G is None else G.ctypes.data, tau.ctypes.data))
+        return J, G, tau
+
+    def batch_info(self):
+        """What the last ``eval_batch`` did (grape_get_batch_info): route 1 = batched kernels, 0 = one ordinary evaluation per
+        set; sets per launch group; number of groups; bytes of batch storage the handle holds."""
+        out = np.zeros(4)
+        self._lib.grape_get_batch_info(self._h, out.ctypes.data, 4)
+        return dict(route=int(out[0]), sets_per_group=int(out[1]), groups=int(out[2]), bytes=int(out[3]))
 
     def forward(self, pulsevals):
         x = np.ascontiguousarray(pulsevals, dtype=np.float64)

@@ -278,6 +278,20 @@ struct grape_handle {
     bool graph_tg_unit = false;    // tg_unit of the captured evaluation
     double2 *d_tq = nullptr;       // [K][N_T] per-trajectory terms of dJ/d(dt_n) (allocated on first use)
     double *d_dJdt = nullptr;      // [N_T]
+    // grape_eval_batch (grape_batch.hip.h): many pulse vectors through this handle's problem.  The batched
+    // route owns its buffers -- allocated by the first batch call, grown on demand, freed by grape_destroy -- and touches
+    // nothing an ordinary evaluation uses (captured graph, scan set-up, result slab).
+    bool batch_ok = false;         // the handle is inside the envelope of the batched kernels (grape_create)
+    int batch_env = -1;            // GRAPE_BATCH at grape_create: 0 one ordinary evaluation per set, 1 the batched kernels
+                                   // wherever batch_ok, unset: the route rule of grape_eval_batch
+    int batch_sets_env = 0;        // GRAPE_BATCH_SETS at grape_create: sets per launch group (tests; 0: from the memory budget)
+    int batch_cap = 0;             // sets the batch storage holds
+    size_t batch_bytes = 0;        // ... and its size on the device
+    double *d_beps = nullptr, *d_bSf = nullptr, *d_bslab = nullptr, *d_brho = nullptr;
+    double2 *d_bU = nullptr, *d_bfw = nullptr, *d_bbw = nullptr, *d_btg = nullptr, *d_bz = nullptr;
+    unsigned long long *d_bstats = nullptr;   // work statistics of the batched kernels (one block for all sets, not reported)
+    double *h_bpin = nullptr;      // pinned staging of a launch group: pulses | result slabs
+    double batch_info[4] = {0., 0., 0., 0.};   // grape_get_batch_info
 };
 
 namespace {
@@ -354,6 +368,8 @@ extern "C" int grape_t18g_asm_launch(const void *args, size_t args_size, int *ve
                                      const void *const *walk, int fuse, int K, const double *dte);
 extern "C" int grape_t16_asm_launch(const void *args, size_t args_size, int *verdict, void *stream, int blocks,
                                     const void *const *walk, int fuse, int K);
+extern "C" int grape_t18_batch_launch(int herm, const void *args, size_t args_size, const void *strides, size_t strides_size,
+                                      int sets, void *stream, int blocks);
 extern "C" void grape_t16_walks(int KC, int N_T, int nblk, int *tab);
 extern "C" int grape_t16_credit_launch(const void *args, size_t args_size, void *stream);
 // deriv3_kernel keeps the upper 16 x 16 tiles (re, im; stride 17) of H0_k and of the L control operators in LDS
@@ -773,6 +789,12 @@ double herm_norm2_bound(const double *M, int N) {
 #ifndef DERIV16_NTH
 #define DERIV16_NTH 64   // N <= 16: one wave per cell chain (4 columns per thread, quad reductions), many chains per CU
 #endif
+#include "grape_batch.hip.h"
+// route rule of grape_eval_batch (see there; DESIGN.md 12 has the measurements, 500 steps, ms for P evaluations, per-set loop ->
+// batched kernels): P = 2: 0.167 -> 0.171 (K = 1), 0.188 -> 0.202 (K = 4); P = 3: 0.239 -> 0.170, 0.270 -> 0.214; K = 32: P = 3
+// 0.633 -> 0.587, P = 16 3.49 -> 2.76; K = 64: P = 16 5.73 -> 5.54 (a tie); K = 128: P = 16 9.71 -> 10.90
+#define GRAPE_BATCH_MIN_SETS 3
+#define GRAPE_BATCH_MAX_K 32
 template <int NP>
 hipError_t launch_deriv(const DerivArgs &a, int nblocks, hipStream_t s) {
     // 512 threads (8 column chunks per row) at N = 64: half the register tile per thread, so that
@@ -1435,6 +1457,10 @@ void grape_destroy(grape_handle *h) {
     if (h->d_H0p3 && h->d_H0p3 != h->d_H0q3) hipFree(h->d_H0p3);   // (Hermitian operators: the adjoint arrays ARE the plain ones)
     if (h->d_Hcp3 && h->d_Hcp3 != h->d_Hcq3) hipFree(h->d_Hcp3);
     if (h->h_pin) hipHostFree(h->h_pin);
+    void *bbufs[] = {h->d_beps, h->d_bSf, h->d_bslab, h->d_brho, h->d_bU, h->d_bfw, h->d_bbw, h->d_btg, h->d_bz, h->d_bstats};
+    for (void *b : bbufs)
+        if (b) hipFree(b);
+    if (h->h_bpin) hipHostFree(h->h_bpin);
     for (auto &ring : h->ph)
         for (auto &p : ring) {
             if (p.e0) hipEventDestroy(p.e0);
@@ -2212,6 +2238,14 @@ int grape_create(grape_handle **out, const grape_problem *p) try {
         CCHK(hipMemcpy(h->d_wq, wq.data(), wq.size() * 8, hipMemcpyHostToDevice));
         CCHK(dmalloc(&h->d_xi, (size_t)K * (N_T + 1) * NP));
         CCHK(dmalloc(&h->d_gb, (size_t)K * (N_T + 1)));
+    }
+    {   // grape_eval_batch: the envelope of the batched kernels (grape_batch.hip.h) -- the one-wave family of N <= 16 on the
+        // polynomial exponential, exact derivative, no running cost, concurrent sweeps available (non-zero targets);
+        // everything else takes one ordinary evaluation per set
+        h->batch_ok = !h->large && !h->series && NP == 16 && h->t18 && h->t18_small && p->gradient_method == GRAPE_GRAD_GRADGEN &&
+                      !h->have_gb && h->fuse && !h->no_target && h->K == h->K_total && !h->test_hooks && L <= 8;
+        if (const char *envb = getenv("GRAPE_BATCH")) h->batch_env = atoi(envb) != 0 ? 1 : 0;
+        if (const char *envs = getenv("GRAPE_BATCH_SETS")) h->batch_sets_env = std::max(0, atoi(envs));
     }
     CCHK(hipHostMalloc((void **)&h->h_pin, h->h_pin_doubles * 8, hipHostMallocDefault));
     // Everything above went through the NULL stream (hipMemset of device memory returns before the fill has run; a copy from
@@ -3572,6 +3606,242 @@ int grape_set_tlist(grape_handle *h, const double *tlist) try {
     h->bw_done = false; h->z_valid = false;
     HIPCHK(h, hipDeviceSynchronize());   // (copies from pageable memory return once staged)
     return GRAPE_OK;
+}
+GRAPE_BARRIER(h ? &h->err : &g_create_error)
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------
+// grape_eval_batch: P pulse vectors through the problem of one handle (grape_batch.hip.h)
+// ---------------------------------------------------------------------------------------
+namespace {
+
+BatchStrides batch_strides(const grape_handle *h) {
+    BatchStrides st{};
+    const size_t LN = (size_t)h->L * h->N_T;
+    st.eps = LN;
+    st.Sf = h->d_Sf ? (size_t)h->N_T * 2 * h->NP * h->NP : 0;
+    st.U = (size_t)h->KC * h->N_T * h->NP * h->NP;
+    st.vec = (size_t)h->K * (h->N_T + 1) * h->NP;
+    st.tg = (size_t)h->K * LN;
+    st.slab = ((size_t)2 * h->K + 8 + LN + 4 + 1) & ~(size_t)1;
+    st.k = (size_t)h->K;
+    return st;
+}
+
+void batch_release(grape_handle *h) {
+    void *bufs[] = {h->d_beps, h->d_bSf, h->d_bslab, h->d_brho, h->d_bU, h->d_bfw, h->d_bbw, h->d_btg, h->d_bz, h->d_bstats};
+    for (void *b : bufs)
+        if (b) hipFree(b);
+    if (h->h_bpin) hipHostFree(h->h_bpin);
+    h->d_beps = h->d_bSf = h->d_bslab = h->d_brho = nullptr;
+    h->d_bU = h->d_bfw = h->d_bbw = h->d_btg = h->d_bz = nullptr;
+    h->d_bstats = nullptr; h->h_bpin = nullptr;
+    h->batch_cap = 0; h->batch_bytes = 0;
+}
+
+// sets per launch group for a call with P sets, and storage for that many: from a memory budget (half of what the device
+// has free -- what the storage already holds counts as free --, at most 16 GB: the propagators of a set are KC N_T 4 KB,
+// 65 MB at the C2 shape), GRAPE_BATCH_SETS overrides.  The storage only grows.
+int batch_reserve(grape_handle *h, int P, const BatchStrides &st, int *sets) {
+    const size_t per_set = 8 * (st.eps + st.Sf + st.slab + st.k) + 16 * (st.U + 2 * st.vec + st.tg + st.k);
+    int Pg = std::min(P, 65535);   // (the set is grid.y / grid.z of the launches)
+    if (h->batch_sets_env > 0) Pg = std::min(Pg, h->batch_sets_env);
+    else if (Pg > h->batch_cap) {
+        size_t free_b = 0, total_b = 0;
+        HIPCHK(h, hipMemGetInfo(&free_b, &total_b));
+        const double budget = std::min(0.5 * ((double)free_b + (double)h->batch_bytes), 16.0 * 1073741824.0);
+        Pg = (int)std::max<double>(1.0, std::min<double>((double)Pg, std::floor(budget / (double)per_set)));
+    }
+    *sets = Pg;
+    if (Pg <= h->batch_cap) return GRAPE_OK;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    batch_release(h);
+    const size_t n = (size_t)Pg;
+    int rc = GRAPE_OK;
+    auto get = [&](auto **ptr, size_t count) {
+        if (rc == GRAPE_OK && count && dmalloc(ptr, count) != hipSuccess) {
+            h->err = "grape_eval_batch: out of device memory for the storage of " + std::to_string(Pg) + " pulse sets (" +
+                     std::to_string(per_set * n >> 20) + " MB); GRAPE_BATCH_SETS=<n> makes the launch groups smaller";
+            (void)hipGetLastError();
+            rc = GRAPE_ERR_HIP;
+        }
+    };
+    get(&h->d_beps, n * st.eps); get(&h->d_bSf, n * st.Sf); get(&h->d_bslab, n * st.slab); get(&h->d_brho, n * st.k);
+    get(&h->d_bU, n * st.U); get(&h->d_bfw, n * st.vec); get(&h->d_bbw, n * st.vec); get(&h->d_btg, n * st.tg); get(&h->d_bz, n * st.k);
+    get(&h->d_bstats, (size_t)GRAPE_STAT_SHARDS * GRAPE_STAT_SLOTS);
+    if (rc == GRAPE_OK && hipHostMalloc((void **)&h->h_bpin, n * (st.eps + st.slab) * 8, hipHostMallocDefault) != hipSuccess) {
+        h->err = "grape_eval_batch: out of pinned host memory for the staging area of a launch group";
+        (void)hipGetLastError();
+        rc = GRAPE_ERR_HIP;
+    }
+    if (rc) { batch_release(h); return rc; }
+    // (the padded rows and columns of the stored states and propagators are never written: the kernels read them as zeros)
+    HIPCHK(h, hipMemsetAsync(h->d_bfw, 0, n * st.vec * 16, h->stream));
+    HIPCHK(h, hipMemsetAsync(h->d_bbw, 0, n * st.vec * 16, h->stream));
+    HIPCHK(h, hipMemsetAsync(h->d_bU, 0, n * st.U * 16, h->stream));
+    h->batch_cap = Pg;
+    h->batch_bytes = per_set * n + (size_t)GRAPE_STAT_SHARDS * GRAPE_STAT_SLOTS * 8;
+    return GRAPE_OK;
+}
+
+// one launch group: Pg sets starting at set p0 of the call.  Everything is enqueued on the handle's stream without a
+// host decision in between; ONE wait at the end reads the result slabs (tau, sums, G, flags) of all sets.
+int batch_group(grape_handle *h, const BatchStrides &st, int p0, int Pg, const double *pulsevals, double *J, double *G, double *tau) {
+    hipStream_t s = h->stream;
+    const size_t LN = (size_t)h->L * h->N_T, n = (size_t)Pg;
+    const int K = h->K, NP = h->NP, N_T = h->N_T, L = h->L;
+    int *flags0 = (int *)(h->d_bslab + 2 * (size_t)K + 8 + LN);
+    memcpy(h->h_bpin, pulsevals, n * LN * 8);
+    HIPCHK(h, hipMemcpyAsync(h->d_beps, h->h_bpin, n * LN * 8, hipMemcpyHostToDevice, s));
+    HIPCHK(h, hipMemsetAsync(h->d_bslab, 0, n * st.slab * 8, s));
+    HIPCHK(h, hipMemsetAsync(h->d_bstats, 0, (size_t)GRAPE_STAT_SHARDS * GRAPE_STAT_SLOTS * 8, s));
+    // ---- phase A: one wave per cell (p, class, n) ----
+    ExpmArgs ea{};
+    ea.H0f = h->d_H0f; ea.Hcf = h->d_Hcf; ea.eps = h->d_beps; ea.shape = h->d_shape; ea.dts = h->d_dts;
+    ea.U = h->d_bU; ea.flags = flags0; ea.stats = h->d_bstats; ea.cellflag = nullptr;
+    ea.K = h->KC; ea.rep = h->d_rep; ea.L = L; ea.N_T = N_T; ea.hc_per_traj = h->p.hc_per_traj;
+    ea.n1 = h->d_n1; ea.n1_k = K;
+    if (h->d_bSf) {
+        CtrlSumArgs ca{};
+        ca.Hcf = h->d_Hcf; ca.eps = h->d_beps; ca.shape = h->d_shape; ca.Sf = h->d_bSf;
+        ca.L = L; ca.N_T = N_T; ca.pp2 = 2 * NP * NP; ca.per_traj = 0; ca.rep = nullptr;
+        hipLaunchKernelGGL(batch_ctrl_sum_kernel, dim3((unsigned)N_T, 1, (unsigned)Pg), dim3(256), 0, s, ca, st);
+        HIPCHK(h, hipGetLastError());
+        ea.Sf = h->d_bSf;
+    }
+    {   // workgroups per set: ten one-wave workgroups per CU over the whole group (139 registers, 16 KB of LDS), in eights
+        const long ncell = (long)h->KC * N_T;
+        const long want = ((long)h->num_cus * 10 + Pg - 1) / Pg;
+        const int blocks = 8 * (int)std::max<long>(1, std::min<long>((want + 7) / 8, (ncell + 7) / 8));
+        HIPCHK(h, (hipError_t)grape_t18_batch_launch(h->herm ? 1 : 0, &ea, sizeof(ea), &st, sizeof(st), Pg, (void *)s, blocks));
+    }
+    // ---- phase B: one wave per (p, k, direction), sequential sweeps ----
+    SweepArgs sa{};
+    sa.U = h->d_bU; sa.cls = h->d_cls; sa.psi0 = h->d_psi0; sa.target = h->d_target; sa.weights = h->d_weights;
+    sa.store = h->d_bfw; sa.tau = (double2 *)h->d_bslab; sa.f = nullptr; sa.rho = h->d_brho; sa.flags = flags0;
+    sa.chi_min_norm = h->chi_min_norm;
+    sa.K = K; sa.K_total = h->K_total; sa.N = h->N; sa.N_T = N_T; sa.functional = h->p.functional;
+    if (G) {
+        SweepArgs sb = sa;
+        sb.store = h->d_bbw; sb.unit_chi = 1; sb.inv_tnorm = h->d_inv_tnorm;
+        hipLaunchKernelGGL(batch_sweep_pair_kernel, dim3((unsigned)(2 * K), (unsigned)Pg), dim3(64), 0, s, sa, sb, st);
+    } else
+        hipLaunchKernelGGL(batch_sweep_fw_kernel, dim3((unsigned)K, (unsigned)Pg), dim3(64), 0, s, sa, st);
+    HIPCHK(h, hipGetLastError());
+    hipLaunchKernelGGL(batch_tau_reduce_kernel, dim3(1, (unsigned)Pg), dim3(64), 0, s, h->d_bslab, (const double *)h->d_weights, K, st);
+    HIPCHK(h, hipGetLastError());
+    if (G) {
+        ChiCoeffArgs ca{};
+        ca.s = sa; ca.s.inv_tnorm = h->d_inv_tnorm; ca.rho = h->d_brho; ca.z = h->d_bz;
+        hipLaunchKernelGGL(batch_chi_coeff_kernel, dim3((unsigned)((K + 63) / 64), (unsigned)Pg), dim3(64), 0, s, ca, st);
+        HIPCHK(h, hipGetLastError());
+        // ---- phase C: derivative overlaps.  The cells of a workgroup follow the handle's own rule (K alone): the chain of a
+        // workgroup updates its generator incrementally, so the partition must not depend on the batch.  (Measured at the
+        // C2 shape, K = 1 .. 32, P = 4 .. 64: 1, 2, 4 or 8 cells per workgroup give the same times within 3 %.) ----
+        DerivArgs da{};
+        da.H0t = h->d_H0t; da.Hct = h->d_Hct; da.eps = h->d_beps; da.shape = h->d_shape; da.dts = h->d_dts;
+        da.fw = h->d_bfw; da.bw = h->d_bbw; da.rho = h->d_ones; da.tg = h->d_btg; da.flags = flags0; da.stats = h->d_bstats;
+        da.K = K; da.L = L; da.N_T = N_T; da.hc_per_traj = h->p.hc_per_traj;
+        da.max_order = h->taylor_max_order; da.tol = h->taylor_tol;
+        da.rb = h->d_rb; da.rb_k = K; da.sub_theta = h->sub_theta;
+        int cpb = 16;
+        while (cpb > 1 && (long)K * ((N_T + cpb - 1) / cpb) < 2048) cpb >>= 1;
+        da.cells_per_block = cpb;
+        const dim3 grid((unsigned)(K * ((N_T + cpb - 1) / cpb)), (unsigned)Pg), blk(DERIV16_NTH);
+        switch (L) {
+            case 1: hipLaunchKernelGGL(batch_deriv_kernel<1>, grid, blk, 0, s, da, st); break;
+            case 2: hipLaunchKernelGGL(batch_deriv_kernel<2>, grid, blk, 0, s, da, st); break;
+            case 3: hipLaunchKernelGGL(batch_deriv_kernel<3>, grid, blk, 0, s, da, st); break;
+            case 4: hipLaunchKernelGGL(batch_deriv_kernel<4>, grid, blk, 0, s, da, st); break;
+            case 5: case 6: hipLaunchKernelGGL(batch_deriv_kernel<6>, grid, blk, 0, s, da, st); break;
+            default: hipLaunchKernelGGL(batch_deriv_kernel<8>, grid, blk, 0, s, da, st); break;
+        }
+        HIPCHK(h, hipGetLastError());
+        hipLaunchKernelGGL(batch_grad_reduce_kernel, dim3((unsigned)((LN + 15) / 16), (unsigned)Pg), dim3(256), 0, s, h->d_btg, K, (int)LN,
+                           h->d_bslab, (const double2 *)h->d_bz, st);
+        HIPCHK(h, hipGetLastError());
+    }
+    double *hs = h->h_bpin + n * LN;
+    HIPCHK(h, hipMemcpyAsync(hs, h->d_bslab, n * st.slab * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipStreamSynchronize(s));
+    for (int q = 0; q < Pg; ++q) {
+        const double *slab = hs + (size_t)q * st.slab;
+        const int rc = status_from_flags(h, ((const int *)(slab + 2 * (size_t)K + 8 + LN))[0]);
+        if (rc) { h->err = "pulse set " + std::to_string(p0 + q) + ": " + h->err; return rc; }
+    }
+    for (int q = 0; q < Pg; ++q) {
+        const double *slab = hs + (size_t)q * st.slab;
+        J[p0 + q] = functional_from_sums(h, slab + 2 * (size_t)K);
+        if (tau) memcpy(tau + (size_t)(p0 + q) * 2 * K, slab, (size_t)2 * K * 8);
+        if (G) memcpy(G + (size_t)(p0 + q) * LN, slab + 2 * (size_t)K + 8, LN * 8);
+    }
+    return GRAPE_OK;
+}
+
+// the stored states no longer belong to "the last evaluation": grape_get_time_gradient refuses until the next ordinary one
+void batch_invalidate(grape_handle *h) {
+    h->tg_state = 0;
+    for (grape_handle *c : h->shards) c->tg_state = 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int grape_eval_batch(grape_handle *h, int P, const double *pulsevals, double *J, double *G, double *tau) try {
+    if (!h) return GRAPE_ERR_INVALID;
+    if (P <= 0 || !pulsevals || !J) { h->err = "grape_eval_batch: P must be positive, pulsevals and J must not be NULL"; return GRAPE_ERR_INVALID; }
+    if (h->K != h->K_total) {
+        h->err = "grape_eval_batch needs K == K_total; use grape_forward/grape_backward for shards";
+        return GRAPE_ERR_INVALID;
+    }
+    if (h->no_target) {
+        h->err = "this handle has no target states (grape_problem.target == NULL): J_T and chi are the caller's, per pulse vector";
+        return GRAPE_ERR_INVALID;
+    }
+    const size_t LN = (size_t)h->L * h->N_T;
+    // Route rule.  The batched kernels win by putting P latency chains side by side; one set alone is better off on the
+    // ordinary path (scanned sweeps, captured graph), and an ensemble that fills the chip by itself has nothing to gain
+    // (measured crossovers: DESIGN.md 12).  GRAPE_BATCH=0 / 1 forces either route inside the envelope.
+    const bool batched = h->shards.empty() && h->batch_ok &&
+                         (h->batch_env >= 0 ? h->batch_env == 1 : (P >= GRAPE_BATCH_MIN_SETS && h->K <= GRAPE_BATCH_MAX_K));
+    if (!batched) {
+        for (int p = 0; p < P; ++p) {
+            const int rc = grape_eval(h, pulsevals + (size_t)p * LN, J + p, G ? G + (size_t)p * LN : nullptr,
+                                      tau ? tau + (size_t)p * 2 * h->K : nullptr, nullptr);
+            if (rc) {
+                h->err = "pulse set " + std::to_string(p) + ": " + h->err;
+                batch_invalidate(h);
+                return rc;
+            }
+        }
+        batch_invalidate(h);
+        h->batch_info[0] = 0.; h->batch_info[1] = 1.; h->batch_info[2] = (double)P; h->batch_info[3] = (double)h->batch_bytes;
+        return GRAPE_OK;
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    (void)hipGetLastError();   // see grape_forward_device
+    const BatchStrides st = batch_strides(h);
+    int Pg = 0;
+    int rc = batch_reserve(h, P, st, &Pg);
+    if (rc) return rc;
+    batch_invalidate(h);
+    int groups = 0;
+    for (int p0 = 0; p0 < P; p0 += Pg, ++groups) {
+        rc = batch_group(h, st, p0, std::min(Pg, P - p0), pulsevals + (size_t)p0 * LN, J, G, tau);
+        if (rc) return rc;
+    }
+    h->batch_info[0] = 1.; h->batch_info[1] = (double)Pg; h->batch_info[2] = (double)groups; h->batch_info[3] = (double)h->batch_bytes;
+    return GRAPE_OK;
+}
+GRAPE_BARRIER(h ? &h->err : &g_create_error)
+
+int grape_get_batch_info(grape_handle *h, double *out, int n) try {
+    if (!h || !out) return GRAPE_ERR_INVALID;
+    const int m = std::max(0, std::min(n, 4));
+    for (int i = 0; i < m; ++i) out[i] = h->batch_info[i];
+    return m;
 }
 GRAPE_BARRIER(h ? &h->err : &g_create_error)
 

@@ -155,7 +155,7 @@ struct CtrlSumArgs {
 };
 // (grid: N_T x parts -- a workgroup per step walked 256 dependent-latency iterations per thread at NP = 256: 0.86 ms per
 // evaluation of a C5 shard; with one part per 2048 element pairs the launch is bound by what it writes)
-__global__ void __launch_bounds__(256) ctrl_sum_kernel(CtrlSumArgs a) {
+__device__ __forceinline__ void ctrl_sum_body(CtrlSumArgs a) {
     const int blk = blockIdx.x, kc = a.per_traj ? blk / a.N_T : 0, n = blk - kc * a.N_T;
     if (a.per_traj) a.Hcf += (size_t)(a.rep ? a.rep[kc] : kc) * a.L * a.pp2;
     double e[8];
@@ -171,6 +171,7 @@ __global__ void __launch_bounds__(256) ctrl_sum_kernel(CtrlSumArgs a) {
         dst[i] = acc;
     }
 }
+__global__ void __launch_bounds__(256) ctrl_sum_kernel(CtrlSumArgs a) { ctrl_sum_body(a); }
 
 // table of expm_t16p_asm / expm_t16p4_asm (control operators per trajectory, asm/gen_t16p.py): row n = dt_n, e_1n .. e_(slots)n,
 // zeros up to 2 * slots doubles, with e_l = eps_ln shape_ln (0 beyond the problem's controls)
@@ -2201,7 +2202,7 @@ struct ChiCoeffArgs {
     double *rho;      // [K]
     double2 *z;       // [K]
 };
-__global__ void chi_coeff_kernel(ChiCoeffArgs a) {
+__device__ __forceinline__ void chi_coeff_body(const ChiCoeffArgs &a) {
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= a.s.K) return;
     SweepArgs s = a.s;
@@ -2214,6 +2215,7 @@ __global__ void chi_coeff_kernel(ChiCoeffArgs a) {
     a.z[k] = make_double2(cr * tn, -ci * tn);
     if (rho < a.s.chi_min_norm) atomicOr(&a.s.flags[0], 2);
 }
+__global__ void chi_coeff_kernel(ChiCoeffArgs a) { chi_coeff_body(a); }
 
 __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
@@ -2406,7 +2408,7 @@ __global__ void __launch_bounds__(NP == 48 ? 192 : 256) sweep_pair_kernel(SweepA
 }
 
 // tau partial sums of this shard: out[0..1] = sum w tau, out[2] = sum w |tau|^2, out[3] = Re sum w tau
-__global__ void tau_reduce_kernel(const double2 *tau, const double *weights, int K, double *out) {
+__device__ __forceinline__ void tau_reduce_body(const double2 *tau, const double *weights, int K, double *out) {
     double fr = 0., fi = 0., ss = 0.;
     for (int k = threadIdx.x; k < K; k += 64) {
         const double w = weights ? weights[k] : 1.0;
@@ -2416,6 +2418,7 @@ __global__ void tau_reduce_kernel(const double2 *tau, const double *weights, int
     fr = wave_sum(fr); fi = wave_sum(fi); ss = wave_sum(ss);
     if (threadIdx.x == 0) { out[0] = fr; out[1] = fi; out[2] = ss; out[3] = fr; out[4] = 0.; out[5] = 0.; out[6] = 0.; out[7] = 0.; }
 }
+__global__ void tau_reduce_kernel(const double2 *tau, const double *weights, int K, double *out) { tau_reduce_body(tau, weights, K, out); }
 
 // ---------------------------------------------------------------------------------------
 // Kernel 5: per-cell derivative overlaps
@@ -2937,7 +2940,7 @@ __global__ void __launch_bounds__(NP == 48 ? 192 : 256) scan_fill_kernel(SweepAr
 
 
 template <int NP, int LMAX, int NTH>
-__global__ void __launch_bounds__(NTH) deriv_kernel(DerivArgs a) {
+__device__ __forceinline__ void deriv_body(const DerivArgs &a) {
     constexpr int NCH = NTH / NP;      // column chunks per row = adjacent lanes (<= 16)
     constexpr int CW = NP / NCH;       // columns per thread
     constexpr int NV = 1 + LMAX;       // vectors: pw = Hd^(m-1) chi, phi_1..phi_L
@@ -3139,6 +3142,8 @@ __global__ void __launch_bounds__(NTH) deriv_kernel(DerivArgs a) {
         }
     }
 }
+template <int NP, int LMAX, int NTH>
+__global__ void __launch_bounds__(NTH) deriv_kernel(DerivArgs a) { deriv_body<NP, LMAX, NTH>(a); }
 
 // ---------------------------------------------------------------------------------------
 // Kernel 5b: the same per-cell derivative overlaps on fp64 MFMA, batched over 16 cells.
@@ -4149,7 +4154,7 @@ __global__ void __launch_bounds__(256) jb_reduce_kernel(const double *gb, const 
 // ---------------------------------------------------------------------------------------
 // Kernel 6: G[l*N_T + n] = -2 Re sum_k tau_grads[k][l][n]   (_grad_J_T_via_chi!, optimize.jl:574-584)
 // ---------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) grad_reduce_kernel(double2 *tg, int K, int LN, double *G, const double2 *z) {
+__device__ __forceinline__ void grad_reduce_body(double2 *tg, int K, int LN, double *G, const double2 *z) {
     // 16 gradient entries per workgroup, 16 threads per entry over the trajectories (a thread per entry walking all K rows
     // is a chain of K dependent load latencies on a handful of CUs: 46 us at C3); partial sums meet in LDS in a fixed order
     __shared__ double part[16][17];
@@ -4178,3 +4183,4 @@ __global__ void __launch_bounds__(256) grad_reduce_kernel(double2 *tg, int K, in
         G[idx] = -2.0 * t;
     }
 }
+__global__ void __launch_bounds__(256) grad_reduce_kernel(double2 *tg, int K, int LN, double *G, const double2 *z) { grad_reduce_body(tg, K, LN, G, z); }

@@ -16,6 +16,8 @@
 #include <stdio.h>
 namespace {
 #include "grape_t18.hip.h"
+#define GRAPE_BATCH_T18_UNIT
+#include "grape_batch.hip.h"
 #include "grape_deriv3.hip.h"
 #include "grape_econ_coeffs.h"
 
@@ -626,6 +628,30 @@ extern "C" int grape_t18_launch(int NT, int herm, int t16, const void *args, siz
         case 3: return (int)(herm ? (t16 ? launch<3, true, true, true>(a, s, blocks) : launch<3, true, true>(a, s, blocks)) : launch<3, false, false>(a, s, blocks));
         default: return (int)(herm ? (t16 ? launch<4, true, true, true>(a, s, blocks) : launch<4, true, true>(a, s, blocks)) : launch<4, false, false>(a, s, blocks));
     }
+}
+// grape_eval_batch, N <= 16: the cells of `sets` pulse sets in one launch (grape_batch.hip.h); args: the ExpmArgs of set 0,
+// strides: a BatchStrides, blocks: workgroups (one wave each) per set, a multiple of 8
+extern "C" int grape_t18_batch_launch(int herm, const void *args, size_t args_size, const void *strides, size_t strides_size,
+                                      int sets, void *stream, int blocks) {
+    if (args_size != sizeof(ExpmArgs) || strides_size != sizeof(BatchStrides) || sets < 1 || blocks < 8 || (blocks & 7)) return (int)hipErrorInvalidValue;
+    ExpmArgs a;
+    BatchStrides st;
+    memcpy(&a, args, sizeof(a));
+    memcpy(&st, strides, sizeof(st));
+    if (a.cell_list || a.listed) return (int)hipErrorInvalidValue;
+    static size_t lds_set[64] = {0};
+    const size_t lds = sizeof(double) * (size_t)T18Lds<1>::TOTAL;
+    int dev = 0;
+    hipGetDevice(&dev);
+    if (lds_set[dev & 63] < lds) {
+        hipError_t e = hipFuncSetAttribute((const void *)batch_expm_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e == hipSuccess) e = hipFuncSetAttribute((const void *)batch_expm_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return (int)e;
+        lds_set[dev & 63] = lds;
+    }
+    if (herm) hipLaunchKernelGGL(batch_expm_kernel<true>, dim3((unsigned)blocks, (unsigned)sets), dim3(64), lds, (hipStream_t)stream, a, st);
+    else hipLaunchKernelGGL(batch_expm_kernel<false>, dim3((unsigned)blocks, (unsigned)sets), dim3(64), lds, (hipStream_t)stream, a, st);
+    return (int)hipGetLastError();
 }
 #ifdef GRAPE_DIAG
 extern "C" void grape_t18_set_stamps(unsigned long long *d_stamps, void *stream) {

@@ -859,7 +859,7 @@ __device__ __forceinline__ void t18_store_u_slot(const ExpmArgs &a, const int ce
 // Three tiles per side, four-product route: 256 registers and 72 KB, TWO workgroups per CU -- three waves leave a SIMD idle
 // and a lone wave cannot hide its own vector and LDS phases; with six waves on four SIMDs two of them are matrix-bound.
 template <int NT, bool SYM, bool CHEB, bool T16 = false>
-__global__ void __launch_bounds__(NT * 64, (T16 && NT == 3) ? 2 : 1) expm_t18_kernel(ExpmArgs a) {
+__device__ __forceinline__ void expm_t18_body(const ExpmArgs &a) {
     static_assert(!T16 || CHEB, "the four-product route is a Hermitian-generator route");
     using LY = T18Lds<NT>;
     extern __shared__ __attribute__((aligned(16))) double smem[];
@@ -1002,3 +1002,5 @@ __global__ void __launch_bounds__(NT * 64, (T16 && NT == 3) ? 2 : 1) expm_t18_ke
         if (any_bad) atomicOr(&a.flags[0], 64);
     }
 }
+template <int NT, bool SYM, bool CHEB, bool T16 = false>
+__global__ void __launch_bounds__(NT * 64, (T16 && NT == 3) ? 2 : 1) expm_t18_kernel(ExpmArgs a) { expm_t18_body<NT, SYM, CHEB, T16>(a); }

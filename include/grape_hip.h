@@ -302,6 +302,41 @@ int grape_get_time_gradient(grape_handle *h, double *dJdt /* [N_T] */);
  * previous grid (stored states, the time gradient) are no longer available; the next call must be a forward evaluation. */
 int grape_set_tlist(grape_handle *h, const double *tlist /* [N_T+1] */);
 
+/* Many pulse vectors at once (entry points only: the ABI version stays 7).  P pulse vectors through the problem of ONE
+ * handle -- the starts of a multi-start optimisation, a population of optimisers, the trial points of a line search, a scan
+ * over amplitudes: the same fg!(F, G, x) (optimize.jl:105-111) at P different x.  Element p of every output is what
+ * grape_eval(h, pulsevals + p*L*N_T, &J[p], G + p*L*N_T, tau + 2*p*K, NULL) returns:
+ *   pulsevals [P][L*N_T] control-major per set (a column-major Julia matrix L*N_T x P);  J [P];
+ *   G NULL or [P][L*N_T] (NULL: functional only, no backward half);  tau NULL or [P][K] complex.
+ * Valid only when K == K_total (as grape_eval).  One in-flight call per handle, host pointers are not retained.
+ *   - Routes.  Inside the envelope of the batched kernels -- one device, N <= 16, GRAPE_PROP_EXP with propagators that fit,
+ *     GRAPE_GRAD_GRADGEN, no built-in running cost (Dpen); Hermitian and general generators, shape, non-uniform grids,
+ *     hc_per_traj 0 and 1, the three functionals, weights, L <= 8 -- the pulse set is one more grid axis of the kernels
+ *     (csrc/grape_batch.hip.h): all sets of a launch group run side by side, a set's result does not depend on its
+ *     neighbours or on the grouping (bit for bit), and agrees with grape_eval to rounding.  Everything else (N > 16,
+ *     GRAPE_GRAD_TAYLOR, GRAPE_PROP_SERIES, Dpen, ndev > 1, the matrix-free fallback of grape_get_work[12]) takes one ordinary
+ *     evaluation per set inside the library: bit for bit the results of P grape_eval calls.  Inside the envelope a route
+ *     rule chooses (a single set, or an ensemble that fills the chip by itself, is better off on the ordinary path);
+ *     environment GRAPE_BATCH=0 / 1, read by grape_create, forces the loop / the batched kernels (outside the envelope
+ *     always the loop).  The batched route cuts P into launch groups that fit a memory budget (GRAPE_BATCH_SETS=<n>,
+ *     read by grape_create, sets the group size); its storage is allocated by the first batch call, grows on demand and is
+ *     freed by grape_destroy.  It reads the current time grid (grape_set_tlist) and always runs the concurrent sweeps
+ *     (grape_set_fused_sweeps does not enter: the results are identical to rounding).
+ *   - Errors.  h == NULL, P <= 0, pulsevals == NULL, J == NULL, a split-phase shard (K < K_total), a handle without targets:
+ *     GRAPE_ERR_INVALID, handle unchanged and usable.  If the evaluation of a set raises a device-side status
+ *     (GRAPE_ERR_CHI_NORM, GRAPE_ERR_TAYLOR, GRAPE_ERR_SINGULAR) the call returns the status of the lowest such p,
+ *     grape_last_error names that p ("pulse set p: ..."), the outputs are unspecified and the handle stays usable.
+ *   - State afterwards.  The "last evaluation" that grape_get_storage, _tau_grads, _propagator, _final_states and _sums refer
+ *     to is NOT defined after a batch call; grape_get_time_gradient returns GRAPE_ERR_INVALID until the next ordinary
+ *     evaluation with a gradient.  An ordinary grape_eval after a batch call gives exactly what it gave before it: the
+ *     batched route owns its buffers and touches neither the captured graph nor the scan set-up nor the launch plans. */
+int grape_eval_batch(grape_handle *h, int P, const double *pulsevals, double *J, double *G, double *tau);
+
+/* What the last grape_eval_batch of this handle did: [0] 1 = batched kernels, 0 = one ordinary evaluation per set;
+ * [1] sets per launch group;  [2] number of groups;  [3] bytes of batch storage the handle holds on the device.
+ * Returns the number of entries written (at most n). */
+int grape_get_batch_info(grape_handle *h, double *out, int n);
+
 const char *grape_last_error(grape_handle *h); /* h may be NULL: error of the last failed create */
 int grape_abi_version(void);
 

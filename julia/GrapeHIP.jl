@@ -380,4 +380,43 @@ function set_tlist!(h::Handle, tlist::AbstractVector{Float64})
     return h
 end
 
+"""
+    eval_batch!(h, J, G, tau, pulsevals)
+
+`P = size(pulsevals, 2)` pulse vectors through the problem of `h` in ONE call (grape_eval_batch): column `p` of the
+`L*N_T × P` matrix `pulsevals` is one `wrk.pulsevals`; `J[p]`, `G[:, p]` (`G === nothing`: functional only) and
+`tau[:, p]` (`K × P`, or `nothing`) are what `fg!` on that column returns.  For the multi-start loop of INTEGRATION.md 3c:
+P optimiser states, one call per round.  Small systems (N ≤ 16) run all sets side by side on the GPU (`batch_info(h).route
+== 1`); everything else takes one ordinary evaluation per set inside the library.  The outputs of `h`'s getters
+(`time_gradient!`, stored states) are not defined after a batch call.
+"""
+function eval_batch!(h::Handle, J::Vector{Float64}, G::Union{Nothing,Matrix{Float64}}, tau::Union{Nothing,Matrix{ComplexF64}},
+                     pulsevals::Matrix{Float64})
+    P = size(pulsevals, 2)
+    # (pseudo-controls -- time-dependent drift terms carried as fixed controls, see problem_arrays -- would have to be
+    # appended to every column: not offered here)
+    isempty(h.fixed) || error("GrapeHIP.eval_batch!: handles with pseudo-controls evaluate one pulse vector at a time (fg!)")
+    size(pulsevals, 1) == h.L * h.N_T || throw(DimensionMismatch("pulsevals must be L*N_T = $(h.L * h.N_T) × P"))
+    length(J) == P || throw(DimensionMismatch("J must have one entry per pulse vector ($P)"))
+    isnothing(G) || size(G) == size(pulsevals) || throw(DimensionMismatch("G must have the size of pulsevals"))
+    isnothing(tau) || size(tau, 2) == P || throw(DimensionMismatch("tau must be K × $P"))
+    Gp = isnothing(G) ? Ptr{Float64}(C_NULL) : pointer(G)
+    tp = isnothing(tau) ? Ptr{ComplexF64}(C_NULL) : pointer(tau)
+    check(h, GC.@preserve J G tau pulsevals ccall((:grape_eval_batch, libgrape), Cint,
+        (Ptr{Cvoid}, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{ComplexF64}), h.ptr, P, pulsevals, J, Gp, tp))
+    return J
+end
+
+"""
+    batch_info(h)
+
+What the last `eval_batch!` did (grape_get_batch_info): `route` (1: batched kernels, 0: one ordinary evaluation per set),
+`sets_per_group`, `groups`, `bytes` of batch storage held by the handle.
+"""
+function batch_info(h::Handle)
+    out = zeros(Float64, 4)
+    GC.@preserve out ccall((:grape_get_batch_info, libgrape), Cint, (Ptr{Cvoid}, Ptr{Float64}, Cint), h.ptr, out, 4)
+    return (route = Int(out[1]), sets_per_group = Int(out[2]), groups = Int(out[3]), bytes = Int(out[4]))
+end
+
 end # module
