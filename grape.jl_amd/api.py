@@ -33,7 +33,7 @@ EXPORTS = ["grape_create", "grape_destroy", "grape_eval", "grape_forward", "grap
            "grape_get_tau_grads", "grape_get_storage", "grape_get_timings", "grape_reset_timings", "grape_get_work",
            "grape_last_error", "grape_abi_version", "grape_set_fused_sweeps", "grape_get_sums", "grape_backward_xi",
            "grape_get_final_states", "grape_backward_chi",
-           "grape_get_time_gradient", "grape_set_tlist", "grape_eval_batch", "grape_get_batch_info"]
+           "grape_get_time_gradient", "grape_set_tlist", "grape_eval_batch", "grape_get_batch_info", "grape_create_open"]
 
 
 class GrapeHipError(RuntimeError):
@@ -53,6 +53,10 @@ class _Problem(C.Structure):
                 ("Dpen", C.c_void_p), ("dpen_per_traj", C.c_int32), ("lambda_b", C.c_double),
                 ("prop_method", C.c_int32), ("prop_tolerance", C.c_double),
                 ("ndev", C.c_int32), ("devices", C.c_void_p), ("taylor_no_check", C.c_int32)]
+
+
+class _Lindblad(C.Structure):
+    _fields_ = [("J", C.c_int32), ("cops_per_traj", C.c_int32), ("cops", C.c_void_p)]
 
 
 def library_path() -> str:
@@ -97,7 +101,7 @@ def build_asm(verbose: bool = False, workdir: str | None = None) -> str:
 def _sources():
     srcs = [os.path.join(_CSRC, f) for f in ("grape_hip.hip", "grape_t18.hip", "grape_kernels.hip.h", "grape_large.hip.h",
                                              "grape_series.hip.h", "grape_cheby.hip.h", "grape_t18.hip.h", "grape_t18_coeffs.h",
-                                             "grape_deriv3.hip.h", "grape_timegrad.hip.h", "grape_batch.hip.h", os.path.join("asm", "gen_t16.py"), os.path.join("asm", "gen_t16p.py"), os.path.join("asm", "gen_t18g.py"), os.path.join("asm", "gen_t18gp.py"), os.path.join("asm", "gen_d3.py"), os.path.join("asm", "gen_d3s.py"), os.path.join("asm", "gen_lg.py"), os.path.join("asm", "gen_d4.py"), os.path.join("asm", "gcn.py"))]
+                                             "grape_deriv3.hip.h", "grape_timegrad.hip.h", "grape_batch.hip.h", "grape_lindblad.hip.h", os.path.join("asm", "gen_t16.py"), os.path.join("asm", "gen_t16p.py"), os.path.join("asm", "gen_t18g.py"), os.path.join("asm", "gen_t18gp.py"), os.path.join("asm", "gen_d3.py"), os.path.join("asm", "gen_d3s.py"), os.path.join("asm", "gen_lg.py"), os.path.join("asm", "gen_d4.py"), os.path.join("asm", "gcn.py"))]
     return srcs, os.path.join(_HERE, "..", "include", "grape_hip.h")
 
 
@@ -183,6 +187,7 @@ def load_library():
     lib = C.CDLL(path)
     vp, dp, ip = C.c_void_p, C.POINTER(C.c_double), C.c_int
     lib.grape_create.argtypes = [C.POINTER(vp), C.POINTER(_Problem)]
+    lib.grape_create_open.argtypes = [C.POINTER(vp), C.POINTER(_Problem), C.POINTER(_Lindblad)]
     lib.grape_destroy.argtypes = [vp]
     lib.grape_destroy.restype = None
     lib.grape_eval.argtypes = [vp, vp, dp, vp, vp, vp]
@@ -482,3 +487,140 @@ class GrapeHip:
                     t18_mfma_flop=w[9], t18_squarings=w[10], t18_cells=w[11], matrix_free_fallback=w[12], t16_cells=w[13],
                     asm_kernel=w[14], asm_deriv_kernel=w[15], asm_blocked_products=w[16],
                     walk_steps=w[17], scan_block=w[18])
+
+
+def liouvillian(H, cops=()):
+    """The d^2 x d^2 generator of the vectorised route for ``GrapeHip``: ``-1j * liouvillian(H, cops) @ vec(rho) == vec(L(rho))``
+    with L(rho) = -i (H_eff rho - rho H_eff^dagger) + sum_j A_j rho A_j^dagger, H_eff = H - (i/2) sum_j A_j^dagger A_j, and
+    ``vec`` stacking COLUMNS (``rho.reshape(-1, order="F")``; vec(A rho B) = (B^T (x) A) vec rho) -- the convention of
+    ``GrapeHipOpen``.  H: [d, d], any complex matrix (pass a control operator with ``cops=()`` for the control part of the
+    generator: it is linear in H); cops: sequence of [d, d] with the rates folded in.  Host helper, numpy only."""
+    H = np.asarray(H, dtype=np.complex128)
+    d = H.shape[0]
+    if H.shape != (d, d):
+        raise ValueError(f"H must be [d, d], got {H.shape}")
+    eye = np.eye(d)
+    heff = H.copy()
+    for A in cops:
+        A = np.asarray(A, dtype=np.complex128)
+        heff = heff - 0.5j * (A.conj().T @ A)
+    # i L: vec(-i (Heff rho - rho Heff^dagger)) = -i (1 (x) Heff - conj(Heff) (x) 1) vec rho
+    out = np.kron(eye, heff) - np.kron(heff.conj(), eye)
+    for A in cops:
+        A = np.asarray(A, dtype=np.complex128)
+        out = out + 1j * np.kron(A.conj(), A)
+    return out
+
+
+class GrapeHipOpen(GrapeHip):
+    """Open-system handle (grape_create_open): d x d density matrices under a Lindblad generator, propagated in matrix form.
+
+    H0: [K, d, d];  Hc: [L, d, d] or [K, L, d, d];  cops: None / empty (unitary evolution of a density matrix), [J, d, d] shared
+    or [K, J, d, d] per trajectory, rates folded in;  rho0 / target: [K, d, d] (target=None: only forward + final_states +
+    backward_chi);  row-major numpy in, transposed on the way as ``GrapeHip`` does.  ``final_states()`` returns [K, d, d],
+    ``storage()`` [K, N_T+1, d, d], ``backward_chi`` takes [K, d, d].  tau_k = tr(target_k^dagger rho_k(T)).
+    Not available (GrapeHipError, the handle stays usable): propagator, storage(1), backward_xi, time_gradient, the
+    device-pointer calls."""
+
+    def __init__(self, H0, Hc, cops, tlist, rho0, target, weights=None, functional=J_T_SM, shape=None, K_total=None,
+                 device=0, chi_min_norm=0.0, prop_tolerance=0.0):
+        self._lib = load_library()
+        H0 = np.asarray(H0)
+        if H0.ndim != 3 or H0.shape[1] != H0.shape[2]:
+            raise ValueError(f"H0 must be [K, d, d], got {H0.shape}")
+        K, N = H0.shape[0], H0.shape[1]
+        Hc = np.asarray(Hc)
+        per_traj = Hc.ndim == 4
+        if Hc.ndim not in (3, 4) or Hc.shape[-2:] != (N, N) or (per_traj and Hc.shape[0] != K):
+            raise ValueError(f"Hc must be [L, d, d] or [K, L, d, d] with d = {N}, K = {K}, got {Hc.shape}")
+        L = Hc.shape[1] if per_traj else Hc.shape[0]
+        tlist = np.ascontiguousarray(tlist, dtype=np.float64)
+        if tlist.ndim != 1 or len(tlist) < 2:
+            raise ValueError("tlist must hold at least two time points")
+        N_T = len(tlist) - 1
+        if weights is not None and np.shape(weights) != (K,):
+            raise ValueError(f"weights must be [K] = [{K}], got {np.shape(weights)}")
+        cops = None if cops is None or np.size(cops) == 0 else np.asarray(cops)
+        cops_per_traj = cops is not None and cops.ndim == 4
+        if cops is not None and (cops.ndim not in (3, 4) or cops.shape[-2:] != (N, N) or (cops_per_traj and cops.shape[0] != K)):
+            raise ValueError(f"cops must be [J, d, d] or [K, J, d, d] with d = {N}, K = {K}, got {cops.shape}")
+        self.N, self.L, self.K, self.N_T = N, L, K, N_T
+        self.J = 0 if cops is None else cops.shape[-3]
+        self.K_total = K if K_total is None else int(K_total)
+        self.functional = functional
+        self.prop_method = PROP_EXP
+        self.lambda_b = 0.0
+        self._H0 = _c128(np.swapaxes(H0, -1, -2), (K, N, N))
+        self._Hc = _c128(np.swapaxes(Hc, -1, -2))
+        self._cops = None if cops is None else _c128(np.swapaxes(cops, -1, -2))
+        self._psi0 = _c128(np.swapaxes(np.asarray(rho0), -1, -2), (K, N, N))
+        self._target = None if target is None else _c128(np.swapaxes(np.asarray(target), -1, -2), (K, N, N))
+        self._tlist = tlist
+        self._weights = None if weights is None else np.ascontiguousarray(weights, dtype=np.float64)
+        self._shape = None if shape is None else np.ascontiguousarray(shape, dtype=np.float64).reshape(L, N_T)
+        p = _Problem()
+        p.abi_version = ABI_VERSION
+        p.N, p.L, p.K, p.K_total, p.N_T = N, L, K, self.K_total, N_T
+        p.functional, p.gradient_method, p.hc_per_traj, p.device = functional, GRAD_GRADGEN, int(per_traj), device
+        p.tlist = self._tlist.ctypes.data
+        p.H0 = self._H0.ctypes.data
+        p.Hc = self._Hc.ctypes.data
+        p.shape = None if self._shape is None else self._shape.ctypes.data
+        p.psi0 = self._psi0.ctypes.data
+        p.target = None if self._target is None else self._target.ctypes.data
+        p.weights = None if self._weights is None else self._weights.ctypes.data
+        p.chi_min_norm = chi_min_norm
+        p.prop_method, p.prop_tolerance = PROP_EXP, float(prop_tolerance)
+        d = _Lindblad()
+        d.J, d.cops_per_traj = self.J, int(cops_per_traj)
+        d.cops = None if self._cops is None else self._cops.ctypes.data
+        self._h = C.c_void_p()
+        rc = self._lib.grape_create_open(C.byref(self._h), C.byref(p), C.byref(d))
+        if rc:
+            msg = self._lib.grape_last_error(None).decode()
+            self._h = None
+            raise GrapeHipError(rc, msg)
+
+    def eval(self, pulsevals, gradient=True, want_psiT=False):
+        """fg!(F, G, x): returns (J, G or None, tau[, rho(T) as [K, d, d]])."""
+        x = np.ascontiguousarray(pulsevals, dtype=np.float64)
+        assert x.size == self.L * self.N_T
+        J = C.c_double(0.0)
+        G = np.empty(self.L * self.N_T) if gradient else None
+        tau = np.empty(self.K, dtype=np.complex128)
+        psiT = np.empty((self.K, self.N, self.N), dtype=np.complex128) if want_psiT else None
+        self._chk(self._lib.grape_eval(self._h, x.ctypes.data, C.byref(J), None if G is None else G.ctypes.data,
+                                       tau.ctypes.data, None if psiT is None else psiT.ctypes.data))
+        return (J.value, G, tau, np.swapaxes(psiT, -1, -2).copy()) if want_psiT else (J.value, G, tau)
+
+    def final_states(self):
+        """rho_k(T) of the last forward sweep, [K, d, d]."""
+        out = np.empty((self.K, self.N, self.N), dtype=np.complex128)
+        self._chk(self._lib.grape_get_final_states(self._h, out.ctypes.data))
+        return np.swapaxes(out, -1, -2).copy()
+
+    def backward_chi(self, chi):
+        """Backward half from caller-supplied boundary matrices chi_k(T) = -dJ_T/d<<rho_k(T)| ([K, d, d], not normalised)."""
+        chi = _c128(np.swapaxes(np.asarray(chi), -1, -2), (self.K, self.N, self.N))
+        G = np.empty(self.L * self.N_T)
+        self._chk(self._lib.grape_backward_chi(self._h, chi.ctypes.data, G.ctypes.data))
+        return G
+
+    def storage(self, which=0):
+        """rho_k(t_n) of the last forward sweep, [K, N_T+1, d, d] (which = 1, the backward states, is not stored)."""
+        out = np.empty((self.K, self.N_T + 1, self.N, self.N), dtype=np.complex128)
+        self._chk(self._lib.grape_get_storage(self._h, which, out.ctypes.data))
+        return np.swapaxes(out, -1, -2).copy()
+
+    def backward_xi(self, xi, lambda_b, f_total=None, chi=None):
+        dummy = np.zeros(2)
+        self._chk(self._lib.grape_backward_xi(self._h, dummy.ctypes.data, None, dummy.ctypes.data, float(lambda_b), dummy.ctypes.data))
+
+    def propagator(self, k, n):
+        dummy = np.zeros(2)
+        self._chk(self._lib.grape_get_propagator(self._h, k, n, dummy.ctypes.data))
+
+    def work(self):
+        w = np.zeros(19)
+        self._lib.grape_get_work(self._h, w.ctypes.data, 19)
+        return dict(cells=w[0], mfma_flop_forward=w[2], mfma_flop_backward=w[3], series_terms=w[7], series_steps=w[8])

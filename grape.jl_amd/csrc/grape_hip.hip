@@ -14,6 +14,7 @@
 #include "grape_series.hip.h"
 #include "grape_cheby.hip.h"
 #include "grape_timegrad.hip.h"
+#include "grape_lindblad.hip.h"
 
 #include <rccl/rccl.h>
 #include <dlfcn.h>
@@ -68,6 +69,8 @@ constexpr int kPhases = 6;
 struct Phase { hipEvent_t e0, e1; bool used; };
 
 }  // namespace
+
+struct OpenCtx;   // open-system handles (grape_create_open)
 
 struct grape_handle {
     grape_problem p{};
@@ -292,6 +295,10 @@ struct grape_handle {
     unsigned long long *d_bstats = nullptr;   // work statistics of the batched kernels (one block for all sets, not reported)
     double *h_bpin = nullptr;      // pinned staging of a launch group: pulses | result slabs
     double batch_info[4] = {0., 0., 0., 0.};   // grape_get_batch_info
+    // grape_create_open (grape_lindblad.hip.h): the states are d x d density matrices under a Lindblad
+    // generator.  Such a handle owns none of the buffers above: everything it holds hangs off this pointer, and the entry
+    // points dispatch on it.
+    OpenCtx *open = nullptr;
 };
 
 namespace {
@@ -1419,6 +1426,262 @@ double functional_from_sums(const grape_handle *h, const double *sums) {
     return J;
 }
 
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Open-system handles (grape_create_open): host side of grape_lindblad.hip.h.  An evaluation is two launches and two
+// reductions; every call waits for its own work (the sweeps take milliseconds to seconds, a host round trip is noise).
+// ---------------------------------------------------------------------------------------------------------------------
+}  // namespace
+
+struct OpenCtx {
+    int J = 0, cops_per_traj = 0, Kj = 1, Kc = 1;
+    double *d_H0 = nullptr, *d_Hc = nullptr, *d_Dc = nullptr, *d_A = nullptr, *d_AdA = nullptr, *d_rho0 = nullptr, *d_target = nullptr,
+           *d_chi = nullptr, *d_weights = nullptr, *d_eps = nullptr, *d_shape = nullptr, *d_dts = nullptr, *d_rb = nullptr,
+           *d_store = nullptr, *d_ws = nullptr, *d_out = nullptr, *d_f = nullptr, *d_rho = nullptr, *d_G = nullptr;
+    double2 *d_tg = nullptr;
+    int *d_flags = nullptr;
+    unsigned long long *d_stats = nullptr;
+    std::vector<void *> bufs;
+    size_t bytes = 0;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    double ms_fwd = 0.0, ms_bwd = 0.0;
+    long n_fwd = 0, n_bwd = 0;
+    std::vector<double> out;      // host copy of tau [2K] | sums [8] of the last forward sweep
+    std::vector<double> stage;    // host staging of matrices in the device layout
+    bool have_bwd = false;
+};
+
+namespace {
+
+template <typename T>
+hipError_t open_alloc(OpenCtx *o, T **p, size_t n) {
+    const hipError_t e = hipMalloc((void **)p, std::max<size_t>(n, 1) * sizeof(T));
+    if (e == hipSuccess) { o->bufs.push_back((void *)*p); o->bytes += std::max<size_t>(n, 1) * sizeof(T); }
+    return e;
+}
+
+void open_destroy(grape_handle *h) {
+    OpenCtx *o = h->open;
+    hipSetDevice(h->device);
+    if (h->stream) hipStreamSynchronize(h->stream);
+    for (void *b : o->bufs) hipFree(b);
+    for (hipEvent_t e : o->ev)
+        if (e) hipEventDestroy(e);
+    if (h->stream) hipStreamDestroy(h->stream);
+    delete o;
+    delete h;
+}
+
+// column-major interleaved N x N (the ABI) -> planar row-major NP x NP, zero padded (the kernels)
+void open_to_planar(const double *src, int N, int NP, double *dst) {
+    std::fill(dst, dst + 2 * (size_t)NP * NP, 0.0);
+    for (int j = 0; j < N; ++j)
+        for (int i = 0; i < N; ++i) {
+            dst[(size_t)i * NP + j] = src[2 * ((size_t)j * N + i)];
+            dst[(size_t)NP * NP + (size_t)i * NP + j] = src[2 * ((size_t)j * N + i) + 1];
+        }
+}
+void open_from_planar(const double *src, int N, int NP, double *dst) {
+    for (int j = 0; j < N; ++j)
+        for (int i = 0; i < N; ++i) {
+            dst[2 * ((size_t)j * N + i)] = src[(size_t)i * NP + j];
+            dst[2 * ((size_t)j * N + i) + 1] = src[(size_t)NP * NP + (size_t)i * NP + j];
+        }
+}
+void open_planar_adjoint(const double *src, int NP, double *dst) {
+    const size_t np2 = (size_t)NP * NP;
+    for (int i = 0; i < NP; ++i)
+        for (int j = 0; j < NP; ++j) {
+            dst[(size_t)i * NP + j] = src[(size_t)j * NP + i];
+            dst[np2 + (size_t)i * NP + j] = -src[np2 + (size_t)j * NP + i];
+        }
+}
+
+LindArgs open_args(const grape_handle *h) {
+    const OpenCtx *o = h->open;
+    LindArgs a{};
+    a.H0 = o->d_H0; a.Hc = o->d_Hc; a.Dc = o->d_Dc; a.A = o->d_A; a.AdA = o->d_AdA; a.rho0 = o->d_rho0; a.target = o->d_target;
+    a.chi_in = nullptr; a.weights = o->d_weights; a.eps = o->d_eps; a.shape = o->d_shape; a.dts = o->d_dts; a.rb = o->d_rb;
+    a.store = o->d_store; a.ws = o->d_ws; a.tau = (double2 *)o->d_out; a.f = o->d_f; a.rho = o->d_rho; a.tg = o->d_tg;
+    a.flags = o->d_flags; a.stats = o->d_stats;
+    a.tol = h->series_tol; a.theta = h->series_theta; a.chi_min_norm = h->chi_min_norm;
+    a.K = h->K; a.K_total = h->K_total; a.L = h->L; a.J = o->J; a.N_T = h->N_T; a.functional = h->p.functional;
+    a.hc_per_traj = h->p.hc_per_traj; a.cops_per_traj = o->cops_per_traj;
+    return a;
+}
+
+int open_status(grape_handle *h, int flags) {
+    if (flags & 2) {
+        h->err = "The chi state of at least one trajectory has norm < chi_min_norm (optimize.jl:1021-1025)";
+        return GRAPE_ERR_CHI_NORM;
+    }
+    if (flags & 16) {
+        h->err = "Lindblad propagator: a series of exp(L dt) did not converge within 200 terms (non-finite generator or pulse?)";
+        return GRAPE_ERR_TAYLOR;
+    }
+    return GRAPE_OK;
+}
+
+int open_refuse(grape_handle *h, const char *what) {
+    h->err = std::string(what) + " is not available on an open-system handle (grape_create_open): see DESIGN.md 13 for the entry points "
+             "such a handle supports";
+    return GRAPE_ERR_INVALID;
+}
+
+#define OPEN_LAUNCH(kernel, grid, threads_of, args)                                                          \
+    switch (h->NP) {                                                                                         \
+    case 16: hipLaunchKernelGGL(kernel<16>, grid, dim3(threads_of(16)), 0, h->stream, args); break;          \
+    case 32: hipLaunchKernelGGL(kernel<32>, grid, dim3(threads_of(32)), 0, h->stream, args); break;          \
+    case 48: hipLaunchKernelGGL(kernel<48>, grid, dim3(threads_of(48)), 0, h->stream, args); break;          \
+    default: hipLaunchKernelGGL(kernel<64>, grid, dim3(threads_of(64)), 0, h->stream, args); break;          \
+    }
+#define OPEN_FWD_THREADS(np) ((np) * (np) / 4)
+#define OPEN_BWD_THREADS(np) LindBwd<np>::NTH
+
+int open_forward(grape_handle *h, const double *pulsevals, double *tau) {
+    OpenCtx *o = h->open;
+    HIPCHK(h, hipSetDevice(h->device));
+    (void)hipGetLastError();   // see grape_forward_device
+    const size_t nl = (size_t)h->L * h->N_T, K = (size_t)h->K;
+    h->have_forward = false;
+    o->have_bwd = false;
+    HIPCHK(h, hipMemcpyAsync(o->d_eps, pulsevals, nl * 8, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemsetAsync(o->d_flags, 0, 8 * sizeof(int), h->stream));
+    HIPCHK(h, hipMemsetAsync(o->d_stats, 0, 2 * (K + K * h->L) * sizeof(unsigned long long), h->stream));
+    const LindArgs a = open_args(h);
+    HIPCHK(h, hipEventRecord(o->ev[0], h->stream));
+    OPEN_LAUNCH(lind_forward_kernel, dim3((unsigned)K), OPEN_FWD_THREADS, a)
+    hipLaunchKernelGGL(tau_reduce_kernel, dim3(1), dim3(64), 0, h->stream, (const double2 *)o->d_out, (const double *)o->d_weights, h->K,
+                       o->d_out + 2 * K);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipEventRecord(o->ev[1], h->stream));
+    int flags[8] = {0};
+    HIPCHK(h, hipMemcpyAsync(o->out.data(), o->d_out, (2 * K + 8) * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(flags, o->d_flags, sizeof(flags), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, o->ev[0], o->ev[1]) == hipSuccess) { o->ms_fwd += ms; o->n_fwd++; }
+    const int rc = open_status(h, flags[0]);
+    if (rc) return rc;
+    h->have_forward = true;
+    if (tau) memcpy(tau, o->out.data(), 2 * K * 8);
+    return GRAPE_OK;
+}
+
+// backward sweep + gradient from f = sum_k w_k tau_k (built-in functionals) or from the caller's chi_k(T) ([K][N*N] column-major)
+int open_backward(grape_handle *h, const double f_total[2], const double *chi, double *G) {
+    OpenCtx *o = h->open;
+    HIPCHK(h, hipSetDevice(h->device));
+    (void)hipGetLastError();
+    const size_t nl = (size_t)h->L * h->N_T, K = (size_t)h->K, np2 = (size_t)h->NP * h->NP;
+    o->have_bwd = false;
+    LindArgs a = open_args(h);
+    if (chi) {
+        if (!o->d_chi) HIPCHK(h, open_alloc(o, &o->d_chi, K * 2 * np2));
+        o->stage.resize(K * 2 * np2);
+        for (size_t k = 0; k < K; ++k) open_to_planar(chi + 2 * k * h->N * h->N, h->N, h->NP, o->stage.data() + k * 2 * np2);
+        HIPCHK(h, hipMemcpyAsync(o->d_chi, o->stage.data(), K * 2 * np2 * 8, hipMemcpyHostToDevice, h->stream));
+        a.chi_in = o->d_chi;
+    } else {
+        HIPCHK(h, hipMemcpyAsync(o->d_f, f_total, 16, hipMemcpyHostToDevice, h->stream));
+    }
+    HIPCHK(h, hipMemsetAsync(o->d_flags, 0, 8 * sizeof(int), h->stream));
+    HIPCHK(h, hipEventRecord(o->ev[0], h->stream));
+    OPEN_LAUNCH(lind_backward_kernel, dim3((unsigned)K, (unsigned)h->L), OPEN_BWD_THREADS, a)
+    hipLaunchKernelGGL(grad_reduce_kernel, dim3((unsigned)((nl + 15) / 16)), dim3(256), 0, h->stream, o->d_tg, h->K, (int)nl, o->d_G,
+                       (const double2 *)nullptr);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipEventRecord(o->ev[1], h->stream));
+    int flags[8] = {0};
+    HIPCHK(h, hipMemcpyAsync(G, o->d_G, nl * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(flags, o->d_flags, sizeof(flags), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, o->ev[0], o->ev[1]) == hipSuccess) { o->ms_bwd += ms; o->n_bwd++; }
+    const int rc = open_status(h, flags[0]);
+    if (rc) return rc;
+    o->have_bwd = true;
+    return GRAPE_OK;
+}
+
+int open_final_states(grape_handle *h, double *psiT) {
+    OpenCtx *o = h->open;
+    HIPCHK(h, hipSetDevice(h->device));
+    const size_t np2 = (size_t)h->NP * h->NP, nn = (size_t)h->N * h->N;
+    o->stage.resize(2 * np2);
+    for (int k = 0; k < h->K; ++k) {
+        HIPCHK(h, hipMemcpy(o->stage.data(), o->d_store + ((size_t)k * (h->N_T + 1) + h->N_T) * 2 * np2, 2 * np2 * 8, hipMemcpyDeviceToHost));
+        open_from_planar(o->stage.data(), h->N, h->NP, psiT + 2 * (size_t)k * nn);
+    }
+    return GRAPE_OK;
+}
+
+int open_eval(grape_handle *h, const double *pulsevals, double *J, double *G, double *tau, double *psiT) {
+    int rc = open_forward(h, pulsevals, tau);
+    if (rc) return rc;
+    const double *sums = h->open->out.data() + 2 * (size_t)h->K;
+    *J = functional_from_sums(h, sums);
+    if (G) {
+        const double f[2] = {sums[0], sums[1]};
+        rc = open_backward(h, f, nullptr, G);
+        if (rc) return rc;
+    }
+    if (psiT) return open_final_states(h, psiT);
+    return GRAPE_OK;
+}
+
+int open_storage(grape_handle *h, double *out) {
+    OpenCtx *o = h->open;
+    HIPCHK(h, hipSetDevice(h->device));
+    const size_t np2 = (size_t)h->NP * h->NP, nn = (size_t)h->N * h->N, per_k = (size_t)(h->N_T + 1);
+    o->stage.resize(per_k * 2 * np2);
+    for (int k = 0; k < h->K; ++k) {   // (one trajectory at a time: 65 MB of staging at d = 64, 1000 steps)
+        HIPCHK(h, hipMemcpy(o->stage.data(), o->d_store + (size_t)k * per_k * 2 * np2, per_k * 2 * np2 * 8, hipMemcpyDeviceToHost));
+        for (size_t n = 0; n < per_k; ++n) open_from_planar(o->stage.data() + n * 2 * np2, h->N, h->NP, out + 2 * ((size_t)k * per_k + n) * nn);
+    }
+    o->stage.clear(); o->stage.shrink_to_fit();
+    return GRAPE_OK;
+}
+
+int open_work(grape_handle *h, double *out, int n) {
+    OpenCtx *o = h->open;
+    const int m = n < 19 ? n : 19;
+    std::fill(out, out + m, 0.0);
+    HIPCHK(h, hipSetDevice(h->device));
+    const size_t K = (size_t)h->K, nb = K + K * h->L;
+    std::vector<unsigned long long> st(2 * nb);
+    HIPCHK(h, hipMemcpy(st.data(), o->d_stats, st.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    // [7] / [8]: series terms and (sub-)steps of the sweeps -- the forward sweep of every trajectory plus the backward c chain
+    // of every trajectory (once: the L workgroups of a trajectory repeat it).  [2] / [3]: flop of the matrix instructions
+    // the forward / the backward launch executed (8 NP^3 per complex product; 2 + 2J products per forward term, 6 + 4J per
+    // backward term of every (k, l) workgroup).  [0]: cells.  Every other entry has no meaning here and is zero.
+    double tf = 0., sf = 0., tb = 0., sb = 0., tball = 0.;
+    for (size_t k = 0; k < K; ++k) { tf += (double)st[2 * k]; sf += (double)st[2 * k + 1]; }
+    for (size_t b = 0; b < K * h->L; ++b) {
+        if (b < K) { tb += (double)st[2 * (K + b)]; sb += (double)st[2 * (K + b) + 1]; }
+        tball += (double)st[2 * (K + b)];
+    }
+    const double np3 = (double)h->NP * h->NP * h->NP;
+    out[0] = (double)K * h->N_T;
+    if (m > 2) out[2] = tf * (2.0 + 2.0 * o->J) * 8.0 * np3;
+    if (m > 3) out[3] = tball * (6.0 + 4.0 * o->J) * 8.0 * np3;
+    if (m > 7) out[7] = tf + tb;
+    if (m > 8) out[8] = sf + sb;
+    return 4;
+}
+
+int open_set_tlist(grape_handle *h, const double *tlist) {
+    OpenCtx *o = h->open;
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    std::vector<double> dts(h->N_T);
+    for (int n = 0; n < h->N_T; ++n) dts[n] = tlist[n + 1] - tlist[n];
+    HIPCHK(h, hipMemcpy(o->d_dts, dts.data(), dts.size() * 8, hipMemcpyHostToDevice));
+    h->have_forward = false;
+    o->have_bwd = false;
+    return GRAPE_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1429,6 +1692,7 @@ const char *grape_last_error(grape_handle *h) { return h ? h->err.c_str() : g_cr
 
 void grape_destroy(grape_handle *h) {
     if (!h) return;
+    if (h->open) { open_destroy(h); return; }
     if (!h->shards.empty() || h->comm_set || !h->d_red.empty()) {
         // (collectives of this handle may still be in flight on the shard streams: wait before the buffers go)
         for (grape_handle *c : h->shards)
@@ -1471,6 +1735,157 @@ void grape_destroy(grape_handle *h) {
     if (h->stream) hipStreamDestroy(h->stream);
     delete h;
 }
+
+#define CCHK(expr)                                                                              \
+    do {                                                                                        \
+        hipError_t _e = (expr);                                                                 \
+        if (_e != hipSuccess) { h->err = std::string(#expr) + ": " + hipGetErrorString(_e); return fail(GRAPE_ERR_HIP); } \
+    } while (0)
+
+int grape_create_open(grape_handle **out, const grape_problem *p, const grape_lindblad *diss) try {
+    if (!out || !p) { g_create_error = "null argument"; return GRAPE_ERR_INVALID; }
+    *out = nullptr;
+    if (!diss) { g_create_error = "grape_create_open: diss == NULL (J = 0 with cops = NULL describes unitary evolution of a density matrix)"; return GRAPE_ERR_INVALID; }
+    if (p->abi_version != GRAPE_HIP_ABI_VERSION && p->abi_version != 6) { g_create_error = "abi_version mismatch"; return GRAPE_ERR_INVALID; }
+    if (p->L <= 0) { g_create_error = "no controls in trajectories (workspace.jl:155-157)"; return GRAPE_ERR_NO_CONTROLS; }
+    if (p->N <= 0 || p->K <= 0 || p->N_T <= 0 || !p->tlist || !p->H0 || !p->Hc || !p->psi0) {
+        g_create_error = "invalid problem dimensions or null array";
+        return GRAPE_ERR_INVALID;
+    }
+    test_throw_point("early");
+    if (p->N > 64) { g_create_error = "grape_create_open: N > 64 is not supported (density matrices of d <= 64; DESIGN.md 13)"; return GRAPE_ERR_INVALID; }
+    if (p->L > 8) { g_create_error = "L > 8 is not supported by this build"; return GRAPE_ERR_INVALID; }
+    if (p->functional < 0 || p->functional > 2) { g_create_error = "unknown functional"; return GRAPE_ERR_INVALID; }
+    if (diss->J < 0) { g_create_error = "grape_create_open: J < 0"; return GRAPE_ERR_INVALID; }
+    if (diss->J > LIND_MAX_J) { g_create_error = "grape_create_open: J > 8 collapse operators are not supported"; return GRAPE_ERR_INVALID; }
+    if (diss->J > 0 && !diss->cops) { g_create_error = "grape_create_open: cops == NULL with J > 0"; return GRAPE_ERR_INVALID; }
+    if (p->gradient_method != GRAPE_GRAD_GRADGEN) {
+        g_create_error = "grape_create_open: gradient_method must be GRAPE_GRAD_GRADGEN (the block recursion is summed to convergence; "
+                         ":taylor with its cut-off semantics is not offered on open-system handles)";
+        return GRAPE_ERR_INVALID;
+    }
+    if (p->prop_method != GRAPE_PROP_EXP) { g_create_error = "grape_create_open: prop_method must be GRAPE_PROP_EXP"; return GRAPE_ERR_INVALID; }
+    if (p->Dpen) { g_create_error = "grape_create_open: the state running cost (Dpen) is not supported on open-system handles"; return GRAPE_ERR_INVALID; }
+    if (p->ndev > 1) {
+        g_create_error = "grape_create_open: ndev > 1 is not supported (one open-system handle per GPU with K_total, through the split-phase calls)";
+        return GRAPE_ERR_INVALID;
+    }
+    for (int n = 0; n <= p->N_T; ++n)
+        if (!std::isfinite(p->tlist[n]) || (n < p->N_T && !(p->tlist[n + 1] > p->tlist[n]))) {
+            g_create_error = "tlist must be finite and strictly increasing";
+            return GRAPE_ERR_INVALID;
+        }
+
+    grape_handle *h = new grape_handle();
+    HandleGuard guard(h);
+    OpenCtx *o = new OpenCtx();
+    h->open = o;
+    h->p = *p;
+    h->p.Dpen = nullptr;
+    h->no_target = p->target == nullptr;
+    h->N = p->N; h->L = p->L; h->K = p->K; h->N_T = p->N_T;
+    h->K_total = p->K_total > 0 ? p->K_total : p->K;
+    h->NT = (p->N + 15) / 16; h->NP = 16 * h->NT;
+    h->device = p->ndev == 1 && p->devices ? p->devices[0] : p->device;
+    if (p->chi_min_norm > 0) h->chi_min_norm = p->chi_min_norm;
+    if (p->prop_tolerance > 0) h->series_tol = p->prop_tolerance;
+    o->J = diss->J; o->cops_per_traj = diss->cops_per_traj ? 1 : 0;
+    o->Kj = o->cops_per_traj ? p->K : 1; o->Kc = p->hc_per_traj ? p->K : 1;
+
+    auto fail = [&](int code) { g_create_error = h->err; return code; };   // (the guard releases the handle)
+    CCHK(hipSetDevice(h->device));
+    CCHK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+    CCHK(hipEventCreate(&o->ev[0]));
+    CCHK(hipEventCreate(&o->ev[1]));
+
+    const int N = h->N, NP = h->NP, K = h->K, L = h->L, N_T = h->N_T, J = o->J, Kc = o->Kc, Kj = o->Kj;
+    const size_t nn = (size_t)N * N, np2 = (size_t)NP * NP, m2 = 2 * np2;
+    auto upload = [&](double **dst, const std::vector<double> &src) -> hipError_t {
+        hipError_t e = open_alloc(o, dst, src.size());
+        if (e == hipSuccess && !src.empty()) e = hipMemcpy(*dst, src.data(), src.size() * 8, hipMemcpyHostToDevice);
+        return e;
+    };
+    std::vector<double> buf;
+    // drift, control operators, D_l = -i H_l and D_l^dagger
+    buf.assign((size_t)K * m2, 0.0);
+    for (int k = 0; k < K; ++k) open_to_planar(p->H0 + 2 * (size_t)k * nn, N, NP, buf.data() + (size_t)k * m2);
+    CCHK(upload(&o->d_H0, buf));
+    buf.assign((size_t)Kc * L * m2, 0.0);
+    std::vector<double> dbuf((size_t)Kc * L * 2 * m2, 0.0);
+    for (int q = 0; q < Kc * L; ++q) {
+        double *hl = buf.data() + (size_t)q * m2, *d = dbuf.data() + (size_t)q * 2 * m2;
+        open_to_planar(p->Hc + 2 * (size_t)q * nn, N, NP, hl);
+        for (size_t e = 0; e < np2; ++e) { d[e] = hl[np2 + e]; d[np2 + e] = -hl[e]; }   // -i (a + i b) = b - i a
+        open_planar_adjoint(d, NP, d + m2);
+    }
+    CCHK(upload(&o->d_Hc, buf));
+    CCHK(upload(&o->d_Dc, dbuf));
+    // collapse operators, their adjoints, sum_j A_j^dagger A_j
+    buf.assign((size_t)std::max(Kj * J, 1) * 2 * m2, 0.0);
+    std::vector<double> ada((size_t)Kj * m2, 0.0);
+    for (int kj = 0; kj < Kj; ++kj)
+        for (int j = 0; j < J; ++j) {
+            double *aj = buf.data() + ((size_t)kj * J + j) * 2 * m2, *ad = aj + m2, *s = ada.data() + (size_t)kj * m2;
+            open_to_planar(diss->cops + 2 * ((size_t)kj * J + j) * nn, N, NP, aj);
+            open_planar_adjoint(aj, NP, ad);
+            for (int r = 0; r < N; ++r)
+                for (int q = 0; q < N; ++q) {
+                    const double br = aj[(size_t)q * NP + r], bi = -aj[np2 + (size_t)q * NP + r];   // (A^dagger)[r][q]
+                    if (br == 0.0 && bi == 0.0) continue;
+                    for (int c = 0; c < N; ++c) {
+                        const double xr = aj[(size_t)q * NP + c], xi = aj[np2 + (size_t)q * NP + c];
+                        s[(size_t)r * NP + c] += br * xr - bi * xi;
+                        s[np2 + (size_t)r * NP + c] += br * xi + bi * xr;
+                    }
+                }
+        }
+    CCHK(upload(&o->d_A, buf));
+    CCHK(upload(&o->d_AdA, ada));
+    // states
+    buf.assign((size_t)K * m2, 0.0);
+    for (int k = 0; k < K; ++k) open_to_planar(p->psi0 + 2 * (size_t)k * nn, N, NP, buf.data() + (size_t)k * m2);
+    CCHK(upload(&o->d_rho0, buf));
+    buf.assign((size_t)K * m2, 0.0);
+    if (p->target)
+        for (int k = 0; k < K; ++k) open_to_planar(p->target + 2 * (size_t)k * nn, N, NP, buf.data() + (size_t)k * m2);
+    CCHK(upload(&o->d_target, buf));
+    if (p->weights) CCHK(upload(&o->d_weights, std::vector<double>(p->weights, p->weights + K)));
+    if (p->shape) CCHK(upload(&o->d_shape, std::vector<double>(p->shape, p->shape + (size_t)L * N_T)));
+    {
+        std::vector<double> dts(N_T);
+        for (int n = 0; n < N_T; ++n) dts[n] = p->tlist[n + 1] - p->tlist[n];
+        CCHK(upload(&o->d_dts, dts));
+    }
+    {   // 2-norm estimates for the number of sub-steps: r0_k | r_(kc,l) | sum_j ||A_j||^2
+        std::vector<double> rb((size_t)K + (size_t)Kc * L + Kj, 0.0);
+        for (int k = 0; k < K; ++k) rb[k] = norm2_estimate(p->H0 + 2 * (size_t)k * nn, N);
+        for (int q = 0; q < Kc * L; ++q) rb[(size_t)K + q] = norm2_estimate(p->Hc + 2 * (size_t)q * nn, N);
+        for (int kj = 0; kj < Kj; ++kj)
+            for (int j = 0; j < J; ++j) {
+                const double r = norm2_estimate(diss->cops + 2 * ((size_t)kj * J + j) * nn, N);
+                rb[(size_t)K + (size_t)Kc * L + kj] += r * r;
+            }
+        CCHK(upload(&o->d_rb, rb));
+    }
+    test_throw_point("late");
+    // per-evaluation buffers: every rho_k(t_n), the workspaces of the (K, L) backward workgroups (the K forward ones fit inside)
+    const size_t LN = (size_t)L * N_T;
+    CCHK(open_alloc(o, &o->d_eps, LN));
+    CCHK(open_alloc(o, &o->d_store, (size_t)K * (N_T + 1) * m2));
+    CCHK(open_alloc(o, &o->d_ws, std::max((size_t)K * L * (8 + 2 * J), (size_t)K * (4 + J)) * m2));
+    CCHK(open_alloc(o, &o->d_out, 2 * (size_t)K + 8));
+    CCHK(open_alloc(o, &o->d_f, 2));
+    CCHK(open_alloc(o, &o->d_rho, (size_t)K));
+    CCHK(open_alloc(o, &o->d_G, LN));
+    CCHK(open_alloc(o, &o->d_tg, (size_t)K * LN));
+    CCHK(open_alloc(o, &o->d_flags, 8));
+    CCHK(open_alloc(o, &o->d_stats, 2 * ((size_t)K + (size_t)K * L)));
+    CCHK(hipMemset(o->d_stats, 0, 2 * ((size_t)K + (size_t)K * L) * sizeof(unsigned long long)));
+    o->out.assign(2 * (size_t)K + 8, 0.0);
+    *out = guard.release();
+    return GRAPE_OK;
+}
+GRAPE_BARRIER(&g_create_error)
 
 int grape_create(grape_handle **out, const grape_problem *p) try {
     if (!out || !p) { g_create_error = "null argument"; return GRAPE_ERR_INVALID; }
@@ -1582,11 +1997,6 @@ int grape_create(grape_handle **out, const grape_problem *p) try {
     if (p->prop_tolerance > 0) h->series_tol = p->prop_tolerance;
 
     auto fail = [&](int code) { g_create_error = h->err; return code; };   // (the guard releases the handle)
-#define CCHK(expr)                                                                              \
-    do {                                                                                        \
-        hipError_t _e = (expr);                                                                 \
-        if (_e != hipSuccess) { h->err = std::string(#expr) + ": " + hipGetErrorString(_e); return fail(GRAPE_ERR_HIP); } \
-    } while (0)
 
     CCHK(hipSetDevice(h->device));
     if (const char *envcu = getenv("GRAPE_STREAM_CUS")) {
@@ -2262,6 +2672,7 @@ int grape_create(grape_handle **out, const grape_problem *p) try {
 GRAPE_BARRIER(&g_create_error)
 
 int grape_forward_device(grape_handle *h, const double *d_pulsevals, double *d_out, void *stream_) try {
+    if (h && h->open) return open_refuse(h, "grape_forward_device");
     if (!h || !d_pulsevals || !d_out) return GRAPE_ERR_INVALID;
     if (!h->shards.empty()) { h->err = "device-pointer entry points need a single-device handle (ndev <= 1)"; return GRAPE_ERR_INVALID; }
     hipStream_t s = (hipStream_t)stream_;
@@ -2509,6 +2920,7 @@ int grape_forward_device(grape_handle *h, const double *d_pulsevals, double *d_o
 GRAPE_BARRIER(h ? &h->err : &g_create_error)
 
 int grape_backward_device(grape_handle *h, const double *d_f, double *d_G, void *stream_) try {
+    if (h && h->open) return open_refuse(h, "grape_backward_device");
     if (!h || !d_f || !d_G) return GRAPE_ERR_INVALID;
     if (h->no_target) { h->err = "this handle has no target states (grape_problem.target == NULL): the built-in chi does not exist, use grape_backward_chi"; return GRAPE_ERR_INVALID; }
     if (!h->shards.empty()) { h->err = "device-pointer entry points need a single-device handle (ndev <= 1)"; return GRAPE_ERR_INVALID; }
@@ -2739,6 +3151,7 @@ extern "C" {
 
 int grape_set_fused_sweeps(grape_handle *h, int on) try {
     if (!h) return GRAPE_ERR_INVALID;
+    if (h->open) return 0;   // (one launch per sweep; nothing to fuse)
     if (!h->shards.empty()) {
         int r = 1;
         for (grape_handle *c : h->shards) r &= grape_set_fused_sweeps(c, on);
@@ -2751,6 +3164,11 @@ GRAPE_BARRIER(h ? &h->err : &g_create_error)
 
 int grape_check(grape_handle *h, void *stream_) try {
     if (!h) return GRAPE_ERR_INVALID;
+    if (h->open) {   // (every call on an open-system handle has waited for its work and reported its flags)
+        HIPCHK(h, hipSetDevice(h->device));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        return GRAPE_OK;
+    }
     if (!h->shards.empty()) {
         for (grape_handle *c : h->shards) {
             const int rc = grape_check(c, c->stream);
@@ -3062,6 +3480,7 @@ extern "C" {
 
 int grape_forward(grape_handle *h, const double *pulsevals, double *tau) try {
     if (!h || !pulsevals) return GRAPE_ERR_INVALID;
+    if (h->open) return open_forward(h, pulsevals, tau);
     if (!h->shards.empty()) {
         int rc = multi_forward(h, pulsevals, tau);
         if (rc == GRAPE_ERR_AGAIN) rc = multi_forward(h, pulsevals, tau);   // launch plan adapted: once more
@@ -3083,6 +3502,7 @@ int grape_backward(grape_handle *h, const double f_total[2], double *G_partial) 
     if (!h || !f_total || !G_partial) return GRAPE_ERR_INVALID;
     if (!h->have_forward) { h->err = "grape_backward called before grape_forward"; return GRAPE_ERR_INVALID; }
     if (h->no_target) { h->err = "this handle has no target states (grape_problem.target == NULL): the built-in chi does not exist, use grape_backward_chi"; return GRAPE_ERR_INVALID; }
+    if (h->open) return open_backward(h, f_total, nullptr, G_partial);
     if (!h->shards.empty()) return multi_backward(h, f_total, nullptr, G_partial);
     int rc = backward_enqueue(h, f_total, nullptr);
     if (rc) return rc;
@@ -3093,6 +3513,7 @@ GRAPE_BARRIER(h ? &h->err : &g_create_error)
 int grape_backward_chi(grape_handle *h, const double *chi, double *G) try {
     if (!h || !chi || !G) return GRAPE_ERR_INVALID;
     if (!h->have_forward) { h->err = "grape_backward_chi called before grape_forward"; return GRAPE_ERR_INVALID; }
+    if (h->open) return open_backward(h, nullptr, chi, G);
     if (!h->shards.empty()) return multi_backward(h, nullptr, chi, G);
     int rc = backward_enqueue(h, nullptr, chi);
     if (rc) return rc;
@@ -3102,6 +3523,7 @@ GRAPE_BARRIER(h ? &h->err : &g_create_error)
 
 int grape_backward_xi(grape_handle *h, const double f_total[2], const double *chi, const double *xi, double lambda_b,
                       double *G) try {
+    if (h && h->open) return open_refuse(h, "grape_backward_xi (state running costs)");
     if (!h || !xi || !G || (!chi && !f_total)) return GRAPE_ERR_INVALID;
     if (!h->have_forward) { h->err = "grape_backward_xi called before grape_forward"; return GRAPE_ERR_INVALID; }
     if (h->no_target && !chi) { h->err = "this handle has no target states (grape_problem.target == NULL): grape_backward_xi needs the caller's chi"; return GRAPE_ERR_INVALID; }
@@ -3115,6 +3537,7 @@ GRAPE_BARRIER(h ? &h->err : &g_create_error)
 int grape_get_sums(grape_handle *h, double sums[8]) try {
     if (!h || !sums) return GRAPE_ERR_INVALID;
     if (!h->have_forward) { h->err = "grape_get_sums called before grape_forward"; return GRAPE_ERR_INVALID; }
+    if (h->open) { memcpy(sums, h->open->out.data() + 2 * (size_t)h->K, 8 * sizeof(double)); return GRAPE_OK; }
     if (!h->shards.empty()) {
         std::fill(sums, sums + 8, 0.0);
         for (grape_handle *c : h->shards) {
@@ -3137,6 +3560,7 @@ GRAPE_BARRIER(h ? &h->err : &g_create_error)
 int grape_get_final_states(grape_handle *h, double *psiT) try {
     if (!h || !psiT) return GRAPE_ERR_INVALID;
     if (!h->have_forward) { h->err = "grape_get_final_states called before grape_forward"; return GRAPE_ERR_INVALID; }
+    if (h->open) return open_final_states(h, psiT);
     if (!h->shards.empty()) {
         for (size_t g = 0; g < h->shards.size(); ++g) {
             const int rc = grape_get_final_states(h->shards[g], psiT + 2 * (size_t)h->shard_lo[g] * h->N);
@@ -3166,6 +3590,7 @@ int grape_eval(grape_handle *h, const double *pulsevals, double *J, double *G, d
                  "grape_forward + grape_get_final_states + grape_backward_chi";
         return GRAPE_ERR_INVALID;
     }
+    if (h->open) return open_eval(h, pulsevals, J, G, tau, psiT);
     const bool multi = !h->shards.empty();
     if (!multi && G && !h->large) {
         // One device, functional and gradient: the whole evaluation is enqueued without a host round trip in the middle --
@@ -3265,6 +3690,12 @@ GRAPE_BARRIER(h ? &h->err : &g_create_error)
 
 int grape_get_tau_grads(grape_handle *h, double *out) try {
     if (!h || !out) return GRAPE_ERR_INVALID;
+    if (h->open) {
+        if (!h->open->have_bwd) { h->err = "grape_get_tau_grads: the last evaluation of this handle had no (successful) backward half"; return GRAPE_ERR_INVALID; }
+        HIPCHK(h, hipSetDevice(h->device));
+        HIPCHK(h, hipMemcpy(out, h->open->d_tg, (size_t)h->K * h->L * h->N_T * 16, hipMemcpyDeviceToHost));
+        return GRAPE_OK;
+    }
     if (!h->shards.empty()) {   // [k][l][n]: the shards are contiguous blocks of k
         for (size_t g = 0; g < h->shards.size(); ++g) {
             const int rc = grape_get_tau_grads(h->shards[g], out + 2 * (size_t)h->shard_lo[g] * h->L * h->N_T);
@@ -3281,6 +3712,11 @@ GRAPE_BARRIER(h ? &h->err : &g_create_error)
 
 int grape_get_storage(grape_handle *h, int which, double *out) try {
     if (!h || !out || which < 0 || which > 1) return GRAPE_ERR_INVALID;
+    if (h->open) {
+        if (which == 1) return open_refuse(h, "grape_get_storage(which = 1): the backward states are not stored;");
+        if (!h->have_forward) { h->err = "grape_get_storage called before a forward evaluation"; return GRAPE_ERR_INVALID; }
+        return open_storage(h, out);
+    }
     if (!h->shards.empty()) {
         for (size_t g = 0; g < h->shards.size(); ++g) {
             const int rc = grape_get_storage(h->shards[g], which, out + 2 * (size_t)h->shard_lo[g] * (h->N_T + 1) * h->N);
@@ -3338,6 +3774,7 @@ GRAPE_BARRIER(h ? &h->err : &g_create_error)
 
 int grape_get_propagator(grape_handle *h, int k, int n, double *out) try {
     // U_kn as N x N column-major complex (debug / parity of the expm kernel)
+    if (h && h->open) return open_refuse(h, "grape_get_propagator (no propagator is materialised)");
     if (!h || !out || k < 0 || k >= h->K || n < 0 || n >= h->N_T) return GRAPE_ERR_INVALID;
     if (!h->shards.empty()) {
         size_t g = 0;
@@ -3367,6 +3804,14 @@ GRAPE_BARRIER(h ? &h->err : &g_create_error)
 
 int grape_get_timings(grape_handle *h, double *ms, int n) try {
     if (!h || !ms) return GRAPE_ERR_INVALID;
+    if (h->open) {   // [1] forward launch, [2] backward launch (sweep and derivatives are one kernel), [5] both; -1: not measured
+        const OpenCtx *o = h->open;
+        const double f = o->n_fwd ? o->ms_fwd / o->n_fwd : -1.0, b = o->n_bwd ? o->ms_bwd / o->n_bwd : -1.0;
+        const double v[kPhases] = {0.0, f, b, 0.0, 0.0, f < 0.0 ? -1.0 : f + std::max(b, 0.0)};
+        int cnt = 0;
+        for (; cnt < kPhases && cnt < n; ++cnt) ms[cnt] = v[cnt];
+        return cnt;
+    }
     if (!h->shards.empty()) {   // the devices work side by side: a phase takes as long as its slowest shard
         int cnt = 0;
         for (size_t g = 0; g < h->shards.size(); ++g) {
@@ -3402,6 +3847,7 @@ GRAPE_BARRIER(h ? &h->err : &g_create_error)
 
 int grape_reset_timings(grape_handle *h) try {
     if (!h) return GRAPE_ERR_INVALID;
+    if (h->open) { h->open->ms_fwd = h->open->ms_bwd = 0.0; h->open->n_fwd = h->open->n_bwd = 0; return GRAPE_OK; }
     if (!h->shards.empty()) {
         for (grape_handle *c : h->shards) {
             const int rc = grape_reset_timings(c);
@@ -3424,6 +3870,7 @@ GRAPE_BARRIER(h ? &h->err : &g_create_error)
 
 int grape_get_work(grape_handle *h, double *out, int n) try {
     if (!h || !out || n < 4) return GRAPE_ERR_INVALID;
+    if (h->open) return open_work(h, out, n);
     if (!h->shards.empty()) {   // every entry is a count: the shards add up
         const int m = n < 19 ? n : 19;
         std::fill(out, out + m, 0.0);
@@ -3509,6 +3956,7 @@ int grape_get_work(grape_handle *h, double *out, int n) try {
 GRAPE_BARRIER(h ? &h->err : &g_create_error)
 
 int grape_get_time_gradient(grape_handle *h, double *dJdt) try {
+    if (h && h->open) return open_refuse(h, "grape_get_time_gradient");
     if (!h || !dJdt) return GRAPE_ERR_INVALID;
     const int N_T = h->N_T;
     if (!h->shards.empty()) {   // the sum over the shards, in shard order
@@ -3575,6 +4023,7 @@ int grape_set_tlist(grape_handle *h, const double *tlist) try {
             h->err = "tlist must be finite and strictly increasing";
             return GRAPE_ERR_INVALID;
         }
+    if (h->open) return open_set_tlist(h, tlist);
     h->tg_state = 0;
     h->have_forward = false;
     if (!h->shards.empty()) {

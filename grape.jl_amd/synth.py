@@ -110,6 +110,40 @@ def make_config(cid: str, K: int | None = None, k_offset: int = 0, hermitian: bo
     return make_problem(N, L, N_T, K0 if K is None else K, seed=BASE_SEED ^ tag, k_offset=k_offset, hermitian=hermitian)
 
 
+# open-system shapes (GrapeHipOpen; tools/open_ab.py, tests): name -> (d, L, N_T, K, J)
+OPEN_CONFIGS = {f"O{d}K{K}": (d, 2, 500, K, 2) for d in (4, 8, 12, 16, 32, 48, 64) for K in (1, 8)}
+OPEN_CONFIGS["O64R"] = (64, 2, 1000, 3, 2)   # the reach case: d = 64, 1000 steps
+
+
+def density_matrices(seed: int, K: int, d: int) -> np.ndarray:
+    """K random full-rank density matrices X X^dagger / tr(X X^dagger), X complex Ginibre."""
+    z = normal(seed, 2 * K * d * d)
+    X = (z[0::2] + 1j * z[1::2]).reshape(K, d, d)
+    rho = X @ np.conj(np.swapaxes(X, -1, -2))
+    return rho / np.trace(rho, axis1=-2, axis2=-1).real[:, None, None]
+
+
+def make_open_problem(d: int, L: int, N_T: int, K: int, J: int, seed: int = BASE_SEED, dt: float = 1.0, gamma: float = 0.05,
+                      cops_per_traj: bool = False, hermitian: bool = True):
+    """Synthetic open-system ensemble: drift and controls of ``make_problem`` (spectral radius ~ 1), J collapse operators
+    A_j = sqrt(gamma) * Ginibre / sqrt(d) (||A_j||^2 ~ 4 gamma), random density matrices as initial states and targets."""
+    pr = make_problem(d, L, N_T, K, seed=seed, dt=dt, hermitian=hermitian)
+    nc = (K if cops_per_traj else 1) * J
+    z = normal(subseed(seed, 5000), 2 * max(nc, 1) * d * d)
+    A = np.sqrt(gamma / d) * (z[0::2] + 1j * z[1::2]).reshape(max(nc, 1), d, d)[:nc]
+    cops = A.reshape((K, J, d, d) if cops_per_traj else (J, d, d))
+    out = dict(pr)
+    del out["psi0"]
+    out.update(d=d, J=J, cops=cops, rho0=density_matrices(subseed(seed, 6000), K, d),
+               target=density_matrices(subseed(seed, 7000), K, d))
+    return out
+
+
+def make_open_config(name: str):
+    d, L, N_T, K, J = OPEN_CONFIGS[name]
+    return make_open_problem(d, L, N_T, K, J, seed=BASE_SEED ^ (1000 + d))
+
+
 def readme_tls(eps0: float = 0.2, T: float = 5.0, nt: int = 501):
     """The README problem (/root/reference/README.md:37-43): H = sigma_z + eps(t) sigma_x, |0> -> |1>."""
     sz = np.array([[1, 0], [0, -1]], dtype=np.complex128)

@@ -151,6 +151,39 @@ typedef struct {
 int grape_create(grape_handle **out, const grape_problem *problem);
 void grape_destroy(grape_handle *h);
 
+/* Open quantum systems (entry points only: the ABI version stays 7).  The reference treats them as first class: the state is a
+ * vectorised density matrix, the generator a Liouvillian super-operator (docs/src/background.md:46, :240-242).  Handing the
+ * d^2 x d^2 Liouvillian to grape_create follows that recipe literally and ends at d = 22; a handle made by
+ * grape_create_open propagates the d x d density matrices IN MATRIX FORM under a Lindblad generator, 2 <= d <= 64, with the
+ * exact gradient (csrc/grape_lindblad.hip.h). */
+typedef struct {
+    int32_t J;              /* collapse operators, 0 <= J <= 8 (J = 0: unitary evolution of a density matrix)      */
+    int32_t cops_per_traj;  /* 0: cops is [J][N*N], shared; 1: [K][J][N*N]                                         */
+    const double *cops;     /* complex, column-major, rates folded in (A_j = sqrt(gamma_j) a_j); NULL iff J == 0   */
+} grape_lindblad;
+/* Meaning of grape_problem for such a handle: N = d; H0 [K][N*N], Hc, shape, tlist, weights, functional, K_total,
+ * chi_min_norm, device as for grape_create; psi0 and target are [K][N*N] complex column-major MATRICES rho_k(0), sigma_k
+ * (not required to be Hermitian or normalised: the evolution is linear).  On interval n
+ *     H_kn   = H0_k + sum_l shape_ln eps_nl H_l                    (any complex matrices, as on the closed path)
+ *     H_eff  = H_kn - (i/2) sum_j A_j^dagger A_j
+ *     d rho / dt = L_kn(rho) = -i (H_eff rho - rho H_eff^dagger) + sum_j A_j rho A_j^dagger
+ * tau_k = <<sigma_k|rho_k(T)>> = tr(sigma_k^dagger rho_k(T)); J_T_sm / ss / re, chi_k(T) = c_k sigma_k and the norm guard
+ * (Frobenius norm) are the formulas above applied to that tau -- by construction what the vectorised problem gives (column
+ * stacking, vec(A rho B) = (B^T (x) A) vec rho, generator i L in the role of H).  prop_tolerance: a series stops at
+ * ||term||_F <= tol ||sum||_F (<= 0 selects 1e-17); the gradient is the exact derivative of the step (GRAPE_GRAD_GRADGEN).
+ * Entry points that work on an open handle, with states [N*N] wherever this header says [N]: grape_eval, grape_forward,
+ * grape_backward, grape_get_sums, grape_get_final_states, grape_backward_chi (chi [K][N*N]), grape_get_storage(which = 0)
+ * ([K][N_T+1][N*N]), grape_get_tau_grads, grape_set_tlist, grape_eval_batch (one ordinary evaluation per set),
+ * grape_get_timings ([1] forward launch, [2] backward launch, [5] both), grape_reset_timings, grape_get_work ([0] cells,
+ * [2] / [3] flop of the matrix instructions the forward / backward launch executed, [7] series terms and [8] (sub-)steps of
+ * the forward sweeps plus the backward chi chains; every other entry zero), grape_check, grape_last_error, grape_destroy.
+ * target == NULL is legal exactly as for grape_create (forward + final states + grape_backward_chi).
+ * GRAPE_ERR_INVALID with a message that names the reason, before the first HIP call: at create -- N > 64, J < 0, J > 8,
+ * cops == NULL with J > 0, diss == NULL, gradient_method != GRAPE_GRAD_GRADGEN, prop_method != GRAPE_PROP_EXP, Dpen != NULL,
+ * ndev > 1; later (the handle stays usable) -- grape_get_propagator, grape_get_storage(which = 1), grape_backward_xi,
+ * grape_get_time_gradient, grape_forward_device, grape_backward_device. */
+int grape_create_open(grape_handle **out, const grape_problem *problem, const grape_lindblad *diss);
+
 /*
  * Replaces fg!(F, G, x): /root/reference/src/optimize.jl:105-111.
  *   G == NULL  -> evaluate_functional only (forward sweep, optimize.jl:696-768)

@@ -419,4 +419,54 @@ function batch_info(h::Handle)
     return (route = Int(out[1]), sets_per_group = Int(out[2]), groups = Int(out[3]), bytes = Int(out[4]))
 end
 
+
+# ---- open quantum systems (include/grape_hip.h: grape_create_open; INTEGRATION.md 3d) ---------------------------------------
+
+# mirror of `grape_lindblad`
+struct GrapeLindblad
+    J::Int32                 # collapse operators, 0 <= J <= 8
+    cops_per_traj::Int32     # 0: cops is [J] matrices shared by all trajectories; 1: [K][J]
+    cops::Ptr{ComplexF64}    # column-major, rates folded in; C_NULL iff J == 0
+end
+
+"""
+    h = create_open(H0, Hc, cops, tlist, rho0, target; functional = 0, weights = nothing, shape = nothing, K_total = 0, device = 0)
+
+A handle whose states are `d × d` density matrices propagated in matrix form under the Lindblad generator
+`𝓛(ρ) = −i(H_eff ρ − ρ H_eff†) + Σ_j A_j ρ A_j†`, `H_eff = H − (i/2) Σ_j A_j†A_j`.  `H0`: vector of `K` matrices; `Hc`: vector of `L`
+matrices (shared) or vector of `K` such vectors; `cops`: vector of `J` matrices `A_j = √γ_j a_j` (shared), vector of `K` such
+vectors, or empty; `rho0`, `target`: vectors of `K` matrices (`target = nothing`: only `grape_forward` +
+`grape_get_final_states` + `grape_backward_chi`).  The returned `Handle` works with `make_fg!`-style calls of `grape_eval`;
+states come back as `d*d` column-major blocks, i.e. `reshape(·, d, d)`.
+"""
+function create_open(H0, Hc, cops, tlist, rho0, target; functional = 0, weights = nothing, shape = nothing, K_total = 0, device = 0)
+    K, N = length(H0), size(H0[1], 1)
+    hc_per_traj = !(Hc[1] isa AbstractMatrix)
+    L = hc_per_traj ? length(Hc[1]) : length(Hc)
+    cops_per_traj = !isempty(cops) && !(cops[1] isa AbstractMatrix)
+    J = isempty(cops) ? 0 : (cops_per_traj ? length(cops[1]) : length(cops))
+    t = Vector{Float64}(tlist)
+    N_T = length(t) - 1
+    cat(ms) = reduce(hcat, [vec(Matrix{ComplexF64}(m)) for m in ms])
+    H0f = cat(H0)
+    Hcf = hc_per_traj ? reduce(hcat, [cat(Hc[k]) for k = 1:K]) : cat(Hc)
+    Af = J == 0 ? nothing : (cops_per_traj ? reduce(hcat, [cat(cops[k]) for k = 1:K]) : cat(cops))
+    r0 = cat(rho0)
+    tg = isnothing(target) ? nothing : cat(target)
+    w = isnothing(weights) ? nothing : Vector{Float64}(weights)
+    shp = isnothing(shape) ? nothing : Matrix{Float64}(shape)               # [N_T, L] column-major == [l][n]
+    keep = Any[H0f, Hcf, Af, r0, tg, t, w, shp]
+    prob = Ref(GrapeProblem(
+        ABI_VERSION, N, L, K, K_total, N_T, functional, 0, hc_per_traj ? 1 : 0, device,
+        pointer(t), pointer(H0f), pointer(Hcf), isnothing(shp) ? C_NULL : pointer(shp), pointer(r0), isnothing(tg) ? C_NULL : pointer(tg),
+        isnothing(w) ? C_NULL : pointer(w), 0.0, 0, 0.0, C_NULL, 0, 0.0, 0, 0.0, 0, C_NULL, 0))
+    diss = Ref(GrapeLindblad(J, cops_per_traj ? 1 : 0, isnothing(Af) ? C_NULL : pointer(Af)))
+    out = Ref{Ptr{Cvoid}}(C_NULL)
+    rc = GC.@preserve keep ccall((:grape_create_open, libgrape), Cint, (Ref{Ptr{Cvoid}}, Ref{GrapeProblem}, Ref{GrapeLindblad}), out, prob, diss)
+    rc == 0 || error(last_error(C_NULL))
+    h = Handle(out[], keep, K, N * N, functional, isnothing(target) ? collect(1:K) : Int[], L, N_T, Float64[], zeros(Float64, L * N_T), zeros(Float64, L * N_T))
+    finalizer(x -> ccall((:grape_destroy, libgrape), Cvoid, (Ptr{Cvoid},), x.ptr), h)
+    return h
+end
+
 end # module
