@@ -15,6 +15,7 @@
 #include "grape_cheby.hip.h"
 #include "grape_timegrad.hip.h"
 #include "grape_lindblad.hip.h"
+#include "grape_hvp.hip.h"
 
 #include <rccl/rccl.h>
 #include <dlfcn.h>
@@ -295,6 +296,16 @@ struct grape_handle {
     unsigned long long *d_bstats = nullptr;   // work statistics of the batched kernels (one block for all sets, not reported)
     double *h_bpin = nullptr;      // pinned staging of a launch group: pulses | result slabs
     double batch_info[4] = {0., 0., 0., 0.};   // grape_get_batch_info
+    // grape_hvp (grape_hvp.hip.h): Hessian-vector products on the stored forward states.  Its storage is
+    // allocated by the first call, grows with the directions of a launch group and is freed by grape_destroy; nothing an
+    // evaluation uses is touched.
+    int hvp_dirs_env = 0;          // GRAPE_HVP_DIRS at grape_create: directions per launch group (tests; 0: from the memory budget)
+    int hvp_cap = 0;               // directions the storage holds
+    size_t hvp_bytes = 0;          // ... and its size on the device
+    double *d_hvV = nullptr, *d_hvws = nullptr, *d_hvout = nullptr;
+    double2 *d_hvdpsi = nullptr, *d_hvdtau = nullptr, *d_hvdcoef = nullptr, *d_hvtg = nullptr;
+    unsigned long long *d_hvstats = nullptr;   // [4 hvp_cap K] statistics of the workgroups, then the flag word
+    double hvp_info[7] = {0., 0., 0., 0., 0., 0., 0.};   // grape_get_hvp_info
     // grape_create_open (grape_lindblad.hip.h): the states are d x d density matrices under a Lindblad
     // generator.  Such a handle owns none of the buffers above: everything it holds hangs off this pointer, and the entry
     // points dispatch on it.
@@ -1725,6 +1736,9 @@ void grape_destroy(grape_handle *h) {
     for (void *b : bbufs)
         if (b) hipFree(b);
     if (h->h_bpin) hipHostFree(h->h_bpin);
+    void *hbufs[] = {h->d_hvV, h->d_hvws, h->d_hvout, h->d_hvdpsi, h->d_hvdtau, h->d_hvdcoef, h->d_hvtg, h->d_hvstats};
+    for (void *b : hbufs)
+        if (b) hipFree(b);
     for (auto &ring : h->ph)
         for (auto &p : ring) {
             if (p.e0) hipEventDestroy(p.e0);
@@ -2656,6 +2670,7 @@ int grape_create(grape_handle **out, const grape_problem *p) try {
                       !h->have_gb && h->fuse && !h->no_target && h->K == h->K_total && !h->test_hooks && L <= 8;
         if (const char *envb = getenv("GRAPE_BATCH")) h->batch_env = atoi(envb) != 0 ? 1 : 0;
         if (const char *envs = getenv("GRAPE_BATCH_SETS")) h->batch_sets_env = std::max(0, atoi(envs));
+        if (const char *envh = getenv("GRAPE_HVP_DIRS")) h->hvp_dirs_env = std::max(0, atoi(envh));
     }
     CCHK(hipHostMalloc((void **)&h->h_pin, h->h_pin_doubles * 8, hipHostMallocDefault));
     // Everything above went through the NULL stream (hipMemset of device memory returns before the fill has run; a copy from
@@ -3494,6 +3509,7 @@ int grape_forward(grape_handle *h, const double *pulsevals, double *tau) try {
         if (rc) return rc;
         rc = forward_finish(h, tau);
     }
+    if (rc) h->tg_state = 0;   // (the stored states of a failed sweep are nobody's input)
     return rc;
 }
 GRAPE_BARRIER(h ? &h->err : &g_create_error)
@@ -4290,6 +4306,164 @@ int grape_get_batch_info(grape_handle *h, double *out, int n) try {
     if (!h || !out) return GRAPE_ERR_INVALID;
     const int m = std::max(0, std::min(n, 4));
     for (int i = 0; i < m; ++i) out[i] = h->batch_info[i];
+    return m;
+}
+GRAPE_BARRIER(h ? &h->err : &g_create_error)
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------
+// grape_hvp: exact Hessian-vector products on the stored forward states (grape_hvp.hip.h)
+// ---------------------------------------------------------------------------------------
+namespace {
+
+void hvp_release(grape_handle *h) {
+    void *bufs[] = {h->d_hvV, h->d_hvws, h->d_hvout, h->d_hvdpsi, h->d_hvdtau, h->d_hvdcoef, h->d_hvtg, h->d_hvstats};
+    for (void *b : bufs)
+        if (b) hipFree(b);
+    h->d_hvV = h->d_hvws = h->d_hvout = nullptr;
+    h->d_hvdpsi = h->d_hvdtau = h->d_hvdcoef = h->d_hvtg = nullptr;
+    h->d_hvstats = nullptr;
+    h->hvp_cap = 0; h->hvp_bytes = 0;
+}
+
+// bytes of storage one direction needs: step matrices of K workgroups, Psi', the per-trajectory terms, V and H v
+size_t hvp_bytes_per_direction(const grape_handle *h) {
+    const size_t K = (size_t)h->K, LN = (size_t)h->L * h->N_T, pp = (size_t)h->NP * h->NP;
+    return K * (4 * pp * 8 + (size_t)(h->N_T + 1) * h->NP * 16 + LN * 16 + 32 + 32) + 2 * LN * 8;
+}
+
+// directions per launch group for a call with nv directions, and storage for that many: from a memory budget (half of what
+// the device has free -- what the storage already holds counts as free --, at most 8 GB), GRAPE_HVP_DIRS overrides.
+// The storage only grows.
+int hvp_reserve(grape_handle *h, int nv, int *dirs) {
+    const size_t per = hvp_bytes_per_direction(h);
+    int nd = std::min(nv, 65535);   // (the direction is grid.y of the launches)
+    if (h->hvp_dirs_env > 0) nd = std::min(nd, h->hvp_dirs_env);
+    else if (nd > h->hvp_cap) {
+        size_t free_b = 0, total_b = 0;
+        HIPCHK(h, hipMemGetInfo(&free_b, &total_b));
+        const double budget = std::min(0.5 * ((double)free_b + (double)h->hvp_bytes), 8.0 * 1073741824.0);
+        nd = (int)std::max<double>(1.0, std::min<double>((double)nd, std::floor(budget / (double)per)));
+    }
+    *dirs = nd;
+    if (nd <= h->hvp_cap) return GRAPE_OK;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    hvp_release(h);
+    const size_t n = (size_t)nd, K = (size_t)h->K, LN = (size_t)h->L * h->N_T, pp = (size_t)h->NP * h->NP;
+    int rc = GRAPE_OK;
+    auto get = [&](auto **ptr, size_t count) {
+        if (rc == GRAPE_OK && dmalloc(ptr, count) != hipSuccess) {
+            h->err = "grape_hvp: out of device memory for the storage of " + std::to_string(nd) + " directions (" +
+                     std::to_string(per * n >> 20) + " MB); GRAPE_HVP_DIRS=<n> makes the launch groups smaller";
+            (void)hipGetLastError();
+            rc = GRAPE_ERR_HIP;
+        }
+    };
+    get(&h->d_hvV, n * LN); get(&h->d_hvws, n * K * 4 * pp); get(&h->d_hvout, n * LN);
+    get(&h->d_hvdpsi, n * K * (size_t)(h->N_T + 1) * h->NP); get(&h->d_hvdtau, n * K); get(&h->d_hvdcoef, n * K);
+    get(&h->d_hvtg, n * K * LN); get(&h->d_hvstats, 4 * n * K + 1);
+    if (rc) { hvp_release(h); return rc; }
+    h->hvp_cap = nd;
+    h->hvp_bytes = per * n + 8;
+    return GRAPE_OK;
+}
+
+template <int NP>
+void hvp_launch(const HvpArgs &a, int nd, int nct, hipStream_t s) {
+    const dim3 grid((unsigned)a.K, (unsigned)nd), blk(4 * NP);
+    hipLaunchKernelGGL(hvp_forward_kernel<NP>, grid, blk, 0, s, a);
+    hipLaunchKernelGGL(hvp_boundary_kernel, dim3((unsigned)nd), dim3(64), 0, s, a);
+    if (nct == 1) hipLaunchKernelGGL((hvp_backward_kernel<NP, 1>), grid, blk, 0, s, a);
+    else hipLaunchKernelGGL((hvp_backward_kernel<NP, 2>), grid, blk, 0, s, a);
+}
+
+// why this handle cannot give H v (nullptr: it can); every test precedes the first HIP call
+const char *hvp_refusal(const grape_handle *h) {
+    if (h->open) return "open-system handles are out of scope (DESIGN.md 14)";
+    if (!h->shards.empty() || h->p.ndev > 1) return "several devices behind one handle (ndev > 1) are out of scope";
+    if (h->N > 64) return "N > 64 is out of scope (the kernels work on at most four 16-wide tiles)";
+    if (h->K != h->K_total) return "a split-phase shard (K < K_total) is out of scope: f' would need an all-reduce of its own";
+    if (h->no_target) return "this handle has no target states (grape_problem.target == NULL): chi'(T) would be the caller's";
+    if (h->have_gb || (h->p.Dpen && h->p.lambda_b != 0.0)) return "the built-in running cost (Dpen, lambda_b != 0) is out of scope";
+    if (h->tg_state < 1)
+        return "no valid forward state on this time grid (no evaluation yet, the last one failed, grape_set_tlist came since, "
+               "or the last call was grape_eval_batch)";
+    return nullptr;
+}
+
+}  // namespace
+
+extern "C" {
+
+int grape_hvp(grape_handle *h, int nv, const double *V, double *HV) try {
+    if (!h) { g_create_error = "grape_hvp: h == NULL"; return GRAPE_ERR_INVALID; }
+    if (nv <= 0 || !V || !HV) { h->err = "grape_hvp: nv must be positive, V and HV must not be NULL"; return GRAPE_ERR_INVALID; }
+    if (const char *why = hvp_refusal(h)) { h->err = std::string("grape_hvp: ") + why; return GRAPE_ERR_INVALID; }
+    const auto t0 = std::chrono::steady_clock::now();
+    HIPCHK(h, hipSetDevice(h->device));
+    if (h->foreign_stream) HIPCHK(h, hipDeviceSynchronize());   // (see grape_get_time_gradient)
+    (void)hipGetLastError();
+    int nd = 0;
+    int rc = hvp_reserve(h, nv, &nd);
+    if (rc) return rc;
+    const size_t LN = (size_t)h->L * h->N_T, K = (size_t)h->K;
+    hipStream_t s = h->stream;
+    int *d_flag = (int *)(h->d_hvstats + 4 * (size_t)h->hvp_cap * K);
+    HvpArgs a{};
+    a.H0f = h->d_H0f; a.Hcf = h->d_Hcf; a.eps = h->d_eps; a.shape = h->d_shape; a.dts = h->d_dts; a.rb = h->d_rb;
+    a.V = h->d_hvV; a.fw = h->d_fw; a.target = h->d_target; a.weights = h->d_weights;
+    a.tau = (const double2 *)h->d_out; a.f = h->d_out + 2 * K;
+    a.dpsi = h->d_hvdpsi; a.dtau = h->d_hvdtau; a.dcoef = h->d_hvdcoef; a.tg = h->d_hvtg; a.ws = h->d_hvws;
+    a.flags = d_flag; a.stats = h->d_hvstats;
+    a.tol = h->series_tol; a.theta = h->series_theta;
+    a.K = h->K; a.K_total = h->K_total; a.L = h->L; a.N = h->N; a.N_T = h->N_T; a.functional = h->p.functional;
+    a.hc_per_traj = h->p.hc_per_traj;
+    const int nct = 2 + 2 * h->L > 16 ? 2 : 1;
+    std::vector<unsigned long long> st;
+    double terms = 0., substeps = 0., terms_fw = 0.;
+    for (int j0 = 0; j0 < nv; j0 += nd) {
+        const int ng = std::min(nd, nv - j0);
+        HIPCHK(h, hipMemcpyAsync(h->d_hvV, V + (size_t)j0 * LN, (size_t)ng * LN * 8, hipMemcpyHostToDevice, s));
+        HIPCHK(h, hipMemsetAsync(h->d_hvstats, 0, (4 * (size_t)h->hvp_cap * K + 1) * 8, s));
+        switch (h->NP) {
+            case 16: hvp_launch<16>(a, ng, nct, s); break;
+            case 32: hvp_launch<32>(a, ng, nct, s); break;
+            case 48: hvp_launch<48>(a, ng, nct, s); break;
+            default: hvp_launch<64>(a, ng, nct, s); break;
+        }
+        HIPCHK(h, hipGetLastError());
+        // (H v)_j = -2 Re sum_k of the per-trajectory terms: the gradient's reduction, fixed order
+        for (int j = 0; j < ng; ++j)
+            hipLaunchKernelGGL(grad_reduce_kernel, dim3((unsigned)((LN + 15) / 16)), dim3(256), 0, s, h->d_hvtg + (size_t)j * K * LN, h->K,
+                               (int)LN, h->d_hvout + (size_t)j * LN, (const double2 *)nullptr);
+        HIPCHK(h, hipGetLastError());
+        HIPCHK(h, hipMemcpyAsync(HV + (size_t)j0 * LN, h->d_hvout, (size_t)ng * LN * 8, hipMemcpyDeviceToHost, s));
+        st.assign(4 * (size_t)ng * K + 1, 0ull);
+        // (the statistics of this group: forward workgroups, then backward workgroups; the flag word sits behind the capacity)
+        HIPCHK(h, hipMemcpyAsync(st.data(), h->d_hvstats, 4 * (size_t)ng * K * 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(h, hipMemcpyAsync(&st[4 * (size_t)ng * K], d_flag, 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(h, hipStreamSynchronize(s));
+        for (size_t q = 0; q < 2 * (size_t)ng * K; ++q) {
+            terms += (double)st[2 * q]; substeps += (double)st[2 * q + 1];
+            if (q < (size_t)ng * K) terms_fw += (double)st[2 * q];
+        }
+        if ((int)(st[4 * (size_t)ng * K] & 0xffffffffull) & 16) {
+            h->err = "grape_hvp: a series did not converge within 200 terms (direction group starting at " + std::to_string(j0) + ")";
+            return GRAPE_ERR_TAYLOR;
+        }
+    }
+    h->hvp_info[0] = terms; h->hvp_info[1] = substeps; h->hvp_info[2] = (double)nd; h->hvp_info[3] = (double)h->hvp_bytes;
+    h->hvp_info[4] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    h->hvp_info[5] = terms_fw; h->hvp_info[6] = terms - terms_fw;
+    return GRAPE_OK;
+}
+GRAPE_BARRIER(h ? &h->err : &g_create_error)
+
+int grape_get_hvp_info(grape_handle *h, double *out, int n) try {
+    if (!h || !out) return GRAPE_ERR_INVALID;
+    const int m = std::max(0, std::min(n, 7));
+    for (int i = 0; i < m; ++i) out[i] = h->hvp_info[i];
     return m;
 }
 GRAPE_BARRIER(h ? &h->err : &g_create_error)

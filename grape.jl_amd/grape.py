@@ -661,6 +661,33 @@ class _Stop(Exception):
     pass
 
 
+def _make_hessp(wrk, bounds, state):
+    """``hessp(x, p)`` for scipy's second-order solvers: H p from the backend's exact Hessian-vector products at the pulses of
+    its last evaluation.  The solvers ask for H p at the current iterate, which is not always the point evaluated last (a
+    rejected trust-region step): then the forward half is run again at x first, without counting it as a call of fg!.
+    Refused where the product would not be the Hessian of what is minimised: a wrapped backend (nonlinear amplitudes, a
+    user-defined J_T or running cost, fixed pseudo-controls), a pulse running cost J_a, bounds."""
+    backend = wrk.backend
+    if not callable(getattr(type(backend), "hvp", None)):
+        raise ValueError("method=trust-ncg / newton-cg needs a backend with exact Hessian-vector products (`hvp`): the built-in "
+                         f"functionals on the plain HIP handle, not {type(backend).__name__}")
+    if wrk.kwargs.get("J_a") is not None:
+        raise ValueError("method=trust-ncg / newton-cg cannot be combined with a pulse running cost J_a (its Hessian is not known)")
+    if bounds is not None:
+        raise ValueError("method=trust-ncg / newton-cg cannot be combined with pulse bounds")
+    state["hessp_calls"] = 0
+
+    def hessp(x, p):
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        if state.get("x_eval") is None or not np.array_equal(x, state["x_eval"]):
+            backend.eval(x, gradient=False)
+            state["x_eval"] = x.copy()
+        state["hessp_calls"] += 1
+        return np.asarray(backend.hvp(np.ascontiguousarray(p, dtype=np.float64)), dtype=np.float64).reshape(-1)
+
+    return hessp
+
+
 def optimize(trajectories, tlist, backend=None, **kwargs):
     """``GRAPE.optimize(trajectories, tlist; kwargs...)`` -- src/optimize.jl:73-144."""
     from scipy.optimize import minimize
@@ -694,6 +721,7 @@ def optimize(trajectories, tlist, backend=None, **kwargs):
 
     def fg(x):
         J = evaluate_gradient_b(G, x, wrk)
+        state["x_eval"] = np.array(x, dtype=np.float64)   # (where the backend's stored states belong: hessp)
         if state["first"]:  # FG_START: iteration 0 (ext/GRAPELBFGSBExt.jl:100-109)
             state["first"] = False
             wrk.gradient[:] = G
@@ -721,11 +749,25 @@ def optimize(trajectories, tlist, backend=None, **kwargs):
     if np.any(np.isfinite(wrk.lower_bounds)) or np.any(np.isfinite(wrk.upper_bounds)):
         bounds = list(zip(np.where(np.isfinite(wrk.lower_bounds), wrk.lower_bounds, None),
                           np.where(np.isfinite(wrk.upper_bounds), wrk.upper_bounds, None)))
+    # method="trust-ncg" / "newton-cg": second-order solvers of scipy.optimize.minimize on the exact Hessian-vector products of
+    # the backend (grape_hvp; the reference names a true Hessian as future work, paper/paper.md:42).  Default: L-BFGS-B, the
+    # reference's optimizer.
+    solver = str(kwargs.get("method", "L-BFGS-B"))
+    second_order = {"trust-ncg": "trust-ncg", "newton-cg": "Newton-CG"}.get(solver.lower())
+    if second_order is None and solver.upper().replace("_", "-") not in ("L-BFGS-B", "LBFGSB", "GRAPE"):
+        raise ValueError(f"method={solver!r} not in (L-BFGS-B, trust-ncg, newton-cg)")
+    hessp = None
+    if second_order:
+        hessp = _make_hessp(wrk, bounds, state)
     try:
-        res = minimize(fg, wrk.pulsevals.copy(), jac=True, method="L-BFGS-B", bounds=bounds, callback=new_x,
-                       options=dict(maxcor=kwargs.get("lbfgsb_m", 10), ftol=kwargs.get("lbfgsb_factr", 1e1) * 2.2e-16,
-                                    gtol=kwargs.get("lbfgsb_pgtol", 1e-15), maxiter=wrk.result.iter_stop + 1,
-                                    maxfun=10 * (wrk.result.iter_stop + 1) + 100, maxls=50))
+        if second_order:
+            res = minimize(fg, wrk.pulsevals.copy(), jac=True, hessp=hessp, method=second_order, callback=new_x,
+                           options=dict(maxiter=wrk.result.iter_stop + 1, **kwargs.get("solver_options", {})))
+        else:
+            res = minimize(fg, wrk.pulsevals.copy(), jac=True, method="L-BFGS-B", bounds=bounds, callback=new_x,
+                           options=dict(maxcor=kwargs.get("lbfgsb_m", 10), ftol=kwargs.get("lbfgsb_factr", 1e1) * 2.2e-16,
+                                        gtol=kwargs.get("lbfgsb_pgtol", 1e-15), maxiter=wrk.result.iter_stop + 1,
+                                        maxfun=10 * (wrk.result.iter_stop + 1) + 100, maxls=50))
         if wrk.result.message == "in progress":
             wrk.result.message = str(res.message)
     except _Stop:

@@ -370,6 +370,41 @@ int grape_eval_batch(grape_handle *h, int P, const double *pulsevals, double *J,
  * Returns the number of entries written (at most n). */
 int grape_get_batch_info(grape_handle *h, double *out, int n);
 
+/* Exact Hessian-vector products of J (entry points only: the ABI version stays 7).  What a Newton-CG or trust-region solver
+ * needs near convergence, where the gradient alone stalls (the reference names "a true Hessian of the optimization
+ * functional" as future work, paper/paper.md:42; Goodwin & Kuprov 2016):
+ *   HV[j] = (d^2 J / d eps^2) V[j],  j < nv,  at the pulses of the last evaluation;  V, HV: [nv][L*N_T], control-major.
+ * J is the handle's built-in functional (J_T_sm / ss / re with weights, K == K_total).  The product is the derivative of
+ * the gradient along V[j], taken term by term through the series of every step (csrc/grape_hvp.hip.h): exact
+ * to rounding like the gradient itself, not a difference of two gradients.
+ *   - Valid after any successful evaluation that ran the forward half on the current time grid: grape_eval with or without
+ *     G, grape_forward with or without its backward half.  It reads only the stored forward states, tau, f and the device
+ *     copy of the pulses and recomputes the backward chain itself: the result does not depend on the backward storage, on
+ *     the concurrent sweeps, or on which exponential / derivative kernel ran (GRAPE_PROP_EXP, GRAPE_PROP_SERIES and the
+ *     matrix-free fallback alike).  General generators, hc_per_traj, shape and non-uniform grids as grape_eval.
+ *   - The directions are a grid axis of the kernels; a direction's result does not depend on nv or on the launch groups
+ *     (bit for bit), and results are bitwise repeatable.  The storage is allocated by the first call, grows with nv in
+ *     launch groups under a memory budget (GRAPE_HVP_DIRS=<n>, read by grape_create, sets the group size) and is freed
+ *     by grape_destroy.  The call touches neither the captured graph nor the scan set-up nor the launch plans: a
+ *     grape_eval after it returns bit for bit what it returned before, and grape_get_time_gradient still works.
+ *   - Series: m = ceil(beta_n dt_n / theta) sub-steps from the create-time norm estimates; a series stops when every chain
+ *     has ||term|| <= prop_tolerance ||sum|| (default 1e-17), after at most 200 terms -- beyond that GRAPE_ERR_TAYLOR, the
+ *     handle stays usable.
+ *   - GRAPE_ERR_INVALID with a message that names the reason, the handle stays usable: h == NULL, nv <= 0, V == NULL,
+ *     HV == NULL; N > 64; ndev > 1; a split-phase shard (K < K_total); an open-system handle; a handle without targets; the
+ *     built-in running cost (Dpen, lambda_b != 0); no valid forward state (no evaluation yet, the last one failed,
+ *     grape_set_tlist came since, or the last call was grape_eval_batch).  A caller-supplied chi (grape_backward_chi)
+ *     is out of scope: it would need the caller's chi'(T).  The full Hessian is nv = L*N_T unit directions. */
+int grape_hvp(grape_handle *h, int nv, const double *V, double *HV);
+
+/* What the last grape_hvp of this handle did: [0] series terms and [1] (sub-)steps summed over the workgroups of both
+ * sweeps (every (trajectory, direction) pair walks N_T intervals forwards and N_T backwards: 2 K nv N_T steps when no
+ * interval is cut);  [2] directions per launch group;  [3] bytes of HVP storage the handle holds;  [4] milliseconds of the
+ * last call (host wall time, copies included);  diagnostics behind them: [5] the series terms of the tangent forward sweeps,
+ * [6] of the backward sweeps ([0] = [5] + [6]; tools/hvp_ab.py counts the executed matrix instructions from them).
+ * Returns the number of entries written (at most n). */
+int grape_get_hvp_info(grape_handle *h, double *out, int n);
+
 const char *grape_last_error(grape_handle *h); /* h may be NULL: error of the last failed create */
 int grape_abi_version(void);
 

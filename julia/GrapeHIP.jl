@@ -419,6 +419,37 @@ function batch_info(h::Handle)
     return (route = Int(out[1]), sets_per_group = Int(out[2]), groups = Int(out[3]), bytes = Int(out[4]))
 end
 
+"""
+    hvp!(HV, h, V)
+
+Exact Hessian-vector products of `J` at the pulses of the last evaluation of `h` (grape_hvp): `HV[:, j] = (∂²J/∂ϵ²) V[:, j]` for
+the columns of the `L*N_T × nv` matrix `V` (vectors: one direction), all directions in one call.  What a Newton-CG or
+trust-region solver passes as its Hessian operator (`Optim.TwiceDifferentiableHV`, `hv!(Hv, x, v)`: call `fg!` at `x` first).
+Valid after `fg!` (with or without gradient) or `grape_forward` on the current time grid, for the built-in functionals on one
+device, `N ≤ 64`; everything else is refused with a message (include/grape_hip.h).
+"""
+function hvp!(HV::VecOrMat{Float64}, h::Handle, V::VecOrMat{Float64})
+    isempty(h.fixed) || error("GrapeHIP.hvp!: handles with pseudo-controls are not supported (the directions have no entries for them)")
+    size(V, 1) == h.L * h.N_T || throw(DimensionMismatch("V must be L*N_T = $(h.L * h.N_T) × nv"))
+    size(HV) == size(V) || throw(DimensionMismatch("HV must have the size of V"))
+    nv = size(V, 2)
+    nv >= 1 || throw(DimensionMismatch("V must hold at least one direction"))
+    check(h, GC.@preserve HV V ccall((:grape_hvp, libgrape), Cint, (Ptr{Cvoid}, Cint, Ptr{Float64}, Ptr{Float64}), h.ptr, nv, V, HV))
+    return HV
+end
+
+"""
+    hvp_info(h)
+
+What the last `hvp!` did (grape_get_hvp_info): series `terms` and (sub-)`steps` summed over the workgroups of both sweeps,
+directions per launch group, `bytes` of storage held by the handle, milliseconds of the call.
+"""
+function hvp_info(h::Handle)
+    out = zeros(Float64, 5)
+    GC.@preserve out ccall((:grape_get_hvp_info, libgrape), Cint, (Ptr{Cvoid}, Ptr{Float64}, Cint), h.ptr, out, 5)
+    return (terms = Int(out[1]), steps = Int(out[2]), dirs_per_group = Int(out[3]), bytes = Int(out[4]), ms = out[5])
+end
+
 
 # ---- open quantum systems (include/grape_hip.h: grape_create_open; INTEGRATION.md 3d) ---------------------------------------
 
