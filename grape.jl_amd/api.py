@@ -34,7 +34,7 @@ EXPORTS = ["grape_create", "grape_destroy", "grape_eval", "grape_forward", "grap
            "grape_last_error", "grape_abi_version", "grape_set_fused_sweeps", "grape_get_sums", "grape_backward_xi",
            "grape_get_final_states", "grape_backward_chi",
            "grape_get_time_gradient", "grape_set_tlist", "grape_eval_batch", "grape_get_batch_info", "grape_create_open",
-           "grape_hvp", "grape_get_hvp_info"]
+           "grape_hvp", "grape_get_hvp_info", "grape_open_time_gradient"]
 
 
 class GrapeHipError(RuntimeError):
@@ -102,7 +102,7 @@ def build_asm(verbose: bool = False, workdir: str | None = None) -> str:
 def _sources():
     srcs = [os.path.join(_CSRC, f) for f in ("grape_hip.hip", "grape_t18.hip", "grape_kernels.hip.h", "grape_large.hip.h",
                                              "grape_series.hip.h", "grape_cheby.hip.h", "grape_t18.hip.h", "grape_t18_coeffs.h",
-                                             "grape_deriv3.hip.h", "grape_timegrad.hip.h", "grape_batch.hip.h", "grape_lindblad.hip.h", "grape_hvp.hip.h", os.path.join("asm", "gen_t16.py"), os.path.join("asm", "gen_t16p.py"), os.path.join("asm", "gen_t18g.py"), os.path.join("asm", "gen_t18gp.py"), os.path.join("asm", "gen_d3.py"), os.path.join("asm", "gen_d3s.py"), os.path.join("asm", "gen_lg.py"), os.path.join("asm", "gen_d4.py"), os.path.join("asm", "gcn.py"))]
+                                             "grape_deriv3.hip.h", "grape_timegrad.hip.h", "grape_batch.hip.h", "grape_lindblad.hip.h", "grape_lindblad_tg.hip.h", "grape_hvp.hip.h", os.path.join("asm", "gen_t16.py"), os.path.join("asm", "gen_t16p.py"), os.path.join("asm", "gen_t18g.py"), os.path.join("asm", "gen_t18gp.py"), os.path.join("asm", "gen_d3.py"), os.path.join("asm", "gen_d3s.py"), os.path.join("asm", "gen_lg.py"), os.path.join("asm", "gen_d4.py"), os.path.join("asm", "gcn.py"))]
     return srcs, os.path.join(_HERE, "..", "include", "grape_hip.h")
 
 
@@ -209,6 +209,7 @@ def load_library():
     lib.grape_backward_chi.argtypes = [vp, vp, vp]
     lib.grape_backward_xi.argtypes = [vp, vp, vp, vp, C.c_double, vp]
     lib.grape_get_time_gradient.argtypes = [vp, vp]
+    lib.grape_open_time_gradient.argtypes = [vp, vp]
     lib.grape_set_tlist.argtypes = [vp, vp]
     lib.grape_eval_batch.argtypes = [vp, ip, vp, vp, vp, vp]
     lib.grape_get_batch_info.argtypes = [vp, vp, ip]
@@ -543,8 +544,8 @@ class GrapeHipOpen(GrapeHip):
     or [K, J, d, d] per trajectory, rates folded in;  rho0 / target: [K, d, d] (target=None: only forward + final_states +
     backward_chi);  row-major numpy in, transposed on the way as ``GrapeHip`` does.  ``final_states()`` returns [K, d, d],
     ``storage()`` [K, N_T+1, d, d], ``backward_chi`` takes [K, d, d].  tau_k = tr(target_k^dagger rho_k(T)).
-    Not available (GrapeHipError, the handle stays usable): propagator, storage(1), backward_xi, time_gradient, the
-    device-pointer calls."""
+    ``time_gradient()`` is grape_open_time_gradient.  Not available (GrapeHipError, the handle stays usable): propagator,
+    storage(1), backward_xi, the device-pointer calls."""
 
     def __init__(self, H0, Hc, cops, tlist, rho0, target, weights=None, functional=J_T_SM, shape=None, K_total=None,
                  device=0, chi_min_norm=0.0, prop_tolerance=0.0):
@@ -635,6 +636,14 @@ class GrapeHipOpen(GrapeHip):
         out = np.empty((self.K, self.N_T + 1, self.N, self.N), dtype=np.complex128)
         self._chk(self._lib.grape_get_storage(self._h, which, out.ctypes.data))
         return np.swapaxes(out, -1, -2).copy()
+
+    def time_gradient(self):
+        """dJ/d(dt_n) of the last evaluation with a gradient, [N_T] (grape_open_time_gradient): after ``eval`` with a gradient,
+        ``backward`` or ``backward_chi`` (then with the caller's chi) on the current grid; the partial sum over this handle's
+        trajectories for a split-phase shard.  Taken at fixed per-interval pulse and shape values."""
+        out = np.empty(self.N_T)
+        self._chk(self._lib.grape_open_time_gradient(self._h, out.ctypes.data))
+        return out
 
     def backward_xi(self, xi, lambda_b, f_total=None, chi=None):
         dummy = np.zeros(2)

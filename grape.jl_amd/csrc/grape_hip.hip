@@ -15,6 +15,7 @@
 #include "grape_cheby.hip.h"
 #include "grape_timegrad.hip.h"
 #include "grape_lindblad.hip.h"
+#include "grape_lindblad_tg.hip.h"
 #include "grape_hvp.hip.h"
 
 #include <rccl/rccl.h>
@@ -1460,6 +1461,14 @@ struct OpenCtx {
     std::vector<double> out;      // host copy of tau [2K] | sums [8] of the last forward sweep
     std::vector<double> stage;    // host staging of matrices in the device layout
     bool have_bwd = false;
+    // grape_open_time_gradient (grape_lindblad_tg.hip.h): what the stored states and the boundary data on the
+    // device can give.  Validity is a flag of its own (have_bwd belongs to grape_get_tau_grads).
+    enum { TG_NONE, TG_NO_GRADIENT, TG_FORWARD_ONLY, TG_READY, TG_FAILED, TG_NEW_GRID, TG_BATCH };
+    int tg_state = TG_NONE;
+    bool tg_chi_user = false;     // ... the last backward half took the caller's chi_k(T) (still in d_chi)
+    size_t ws_mats = 0;           // matrices (2 NP^2 doubles) d_ws holds
+    double2 *d_tq = nullptr;      // [K][N_T] per-trajectory terms of dJ/d(dt_n) (allocated on first use)
+    double *d_dJdt = nullptr;     // [N_T]
 };
 
 namespace {
@@ -1556,6 +1565,7 @@ int open_forward(grape_handle *h, const double *pulsevals, double *tau) {
     const size_t nl = (size_t)h->L * h->N_T, K = (size_t)h->K;
     h->have_forward = false;
     o->have_bwd = false;
+    o->tg_state = OpenCtx::TG_FAILED;   // (until this sweep has succeeded)
     HIPCHK(h, hipMemcpyAsync(o->d_eps, pulsevals, nl * 8, hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemsetAsync(o->d_flags, 0, 8 * sizeof(int), h->stream));
     HIPCHK(h, hipMemsetAsync(o->d_stats, 0, 2 * (K + K * h->L) * sizeof(unsigned long long), h->stream));
@@ -1575,6 +1585,7 @@ int open_forward(grape_handle *h, const double *pulsevals, double *tau) {
     const int rc = open_status(h, flags[0]);
     if (rc) return rc;
     h->have_forward = true;
+    o->tg_state = OpenCtx::TG_FORWARD_ONLY;
     if (tau) memcpy(tau, o->out.data(), 2 * K * 8);
     return GRAPE_OK;
 }
@@ -1586,6 +1597,7 @@ int open_backward(grape_handle *h, const double f_total[2], const double *chi, d
     (void)hipGetLastError();
     const size_t nl = (size_t)h->L * h->N_T, K = (size_t)h->K, np2 = (size_t)h->NP * h->NP;
     o->have_bwd = false;
+    o->tg_state = OpenCtx::TG_FAILED;   // (until this half has succeeded)
     LindArgs a = open_args(h);
     if (chi) {
         if (!o->d_chi) HIPCHK(h, open_alloc(o, &o->d_chi, K * 2 * np2));
@@ -1612,6 +1624,7 @@ int open_backward(grape_handle *h, const double f_total[2], const double *chi, d
     const int rc = open_status(h, flags[0]);
     if (rc) return rc;
     o->have_bwd = true;
+    o->tg_state = OpenCtx::TG_READY; o->tg_chi_user = chi != nullptr;
     return GRAPE_OK;
 }
 
@@ -1636,6 +1649,8 @@ int open_eval(grape_handle *h, const double *pulsevals, double *J, double *G, do
         const double f[2] = {sums[0], sums[1]};
         rc = open_backward(h, f, nullptr, G);
         if (rc) return rc;
+    } else {
+        h->open->tg_state = OpenCtx::TG_NO_GRADIENT;
     }
     if (psiT) return open_final_states(h, psiT);
     return GRAPE_OK;
@@ -1690,7 +1705,46 @@ int open_set_tlist(grape_handle *h, const double *tlist) {
     HIPCHK(h, hipMemcpy(o->d_dts, dts.data(), dts.size() * 8, hipMemcpyHostToDevice));
     h->have_forward = false;
     o->have_bwd = false;
+    o->tg_state = OpenCtx::TG_NEW_GRID;
     return GRAPE_OK;
+}
+
+#define OPEN_TG_REFUSE(text) do { h->err = "grape_open_time_gradient: " text; return GRAPE_ERR_INVALID; } while (0)
+
+// dJdt[n] = -2 Re sum_k <<L_kn^dagger chi_k(t_{n+1}) | rho_k(t_{n+1})>> from the stored states and the boundary data of the last
+// backward half (grape_lindblad_tg.hip.h).  Touches nothing an evaluation or a getter reads: terms and result are buffers of
+// its own, the workspace is free between calls (every call on an open handle waits for its work), the timing events and the
+// statistics are left alone.
+int open_time_gradient(grape_handle *h, double *dJdt) {
+    OpenCtx *o = h->open;
+    switch (o->tg_state) {
+    case OpenCtx::TG_READY: break;
+    case OpenCtx::TG_NONE: OPEN_TG_REFUSE("no evaluation on this handle yet");
+    case OpenCtx::TG_NO_GRADIENT: OPEN_TG_REFUSE("the last evaluation had no gradient (grape_eval with G == NULL)");
+    case OpenCtx::TG_FORWARD_ONLY: OPEN_TG_REFUSE("called between grape_forward and the backward half");
+    case OpenCtx::TG_NEW_GRID: OPEN_TG_REFUSE("grape_set_tlist came after the last evaluation: the stored states belong to the previous grid");
+    case OpenCtx::TG_BATCH: OPEN_TG_REFUSE("the last call was grape_eval_batch: the stored states are not those of one defined evaluation");
+    default: OPEN_TG_REFUSE("the last evaluation failed");
+    }
+    const size_t K = (size_t)h->K, N_T = (size_t)h->N_T;
+    if (K * (4 + (size_t)o->J) > o->ws_mats) OPEN_TG_REFUSE("internal: the workspace of this handle is smaller than K (4 + J) matrices");
+    HIPCHK(h, hipSetDevice(h->device));
+    (void)hipGetLastError();
+    if (!o->d_tq) HIPCHK(h, open_alloc(o, &o->d_tq, K * N_T));
+    if (!o->d_dJdt) HIPCHK(h, open_alloc(o, &o->d_dJdt, N_T));
+    LindArgs a = open_args(h);
+    a.tg = o->d_tq;
+    a.chi_in = o->tg_chi_user ? o->d_chi : nullptr;
+    HIPCHK(h, hipMemsetAsync(o->d_flags, 0, 8 * sizeof(int), h->stream));
+    OPEN_LAUNCH(lind_timegrad_kernel, dim3((unsigned)K), OPEN_FWD_THREADS, a)
+    hipLaunchKernelGGL(grad_reduce_kernel, dim3((unsigned)((N_T + 15) / 16)), dim3(256), 0, h->stream, o->d_tq, h->K, (int)N_T, o->d_dJdt,
+                       (const double2 *)nullptr);
+    HIPCHK(h, hipGetLastError());
+    int flags[8] = {0};
+    HIPCHK(h, hipMemcpyAsync(dJdt, o->d_dJdt, N_T * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(flags, o->d_flags, sizeof(flags), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return open_status(h, flags[0]);
 }
 
 }  // namespace
@@ -1886,7 +1940,8 @@ int grape_create_open(grape_handle **out, const grape_problem *p, const grape_li
     const size_t LN = (size_t)L * N_T;
     CCHK(open_alloc(o, &o->d_eps, LN));
     CCHK(open_alloc(o, &o->d_store, (size_t)K * (N_T + 1) * m2));
-    CCHK(open_alloc(o, &o->d_ws, std::max((size_t)K * L * (8 + 2 * J), (size_t)K * (4 + J)) * m2));
+    o->ws_mats = std::max((size_t)K * L * (8 + 2 * J), (size_t)K * (4 + J));
+    CCHK(open_alloc(o, &o->d_ws, o->ws_mats * m2));
     CCHK(open_alloc(o, &o->d_out, 2 * (size_t)K + 8));
     CCHK(open_alloc(o, &o->d_f, 2));
     CCHK(open_alloc(o, &o->d_rho, (size_t)K));
@@ -4031,6 +4086,17 @@ int grape_get_time_gradient(grape_handle *h, double *dJdt) try {
 }
 GRAPE_BARRIER(h ? &h->err : &g_create_error)
 
+int grape_open_time_gradient(grape_handle *h, double *dJdt) try {
+    if (!h) { g_create_error = "grape_open_time_gradient: h == NULL"; return GRAPE_ERR_INVALID; }
+    if (!dJdt) { h->err = "grape_open_time_gradient: dJdt == NULL"; return GRAPE_ERR_INVALID; }
+    if (!h->open) {
+        h->err = "grape_open_time_gradient: not an open-system handle (grape_create_open); grape_get_time_gradient is the call for a closed one";
+        return GRAPE_ERR_INVALID;
+    }
+    return open_time_gradient(h, dJdt);
+}
+GRAPE_BARRIER(h ? &h->err : &g_create_error)
+
 int grape_set_tlist(grape_handle *h, const double *tlist) try {
     if (!h || !tlist) return GRAPE_ERR_INVALID;
     const int N_T = h->N_T;
@@ -4248,6 +4314,7 @@ int batch_group(grape_handle *h, const BatchStrides &st, int p0, int Pg, const d
 void batch_invalidate(grape_handle *h) {
     h->tg_state = 0;
     for (grape_handle *c : h->shards) c->tg_state = 0;
+    if (h->open) h->open->tg_state = OpenCtx::TG_BATCH;
 }
 
 }  // namespace

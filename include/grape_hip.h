@@ -181,7 +181,8 @@ typedef struct {
  * GRAPE_ERR_INVALID with a message that names the reason, before the first HIP call: at create -- N > 64, J < 0, J > 8,
  * cops == NULL with J > 0, diss == NULL, gradient_method != GRAPE_GRAD_GRADGEN, prop_method != GRAPE_PROP_EXP, Dpen != NULL,
  * ndev > 1; later (the handle stays usable) -- grape_get_propagator, grape_get_storage(which = 1), grape_backward_xi,
- * grape_get_time_gradient, grape_forward_device, grape_backward_device. */
+ * grape_get_time_gradient (the time gradient of an open handle is grape_open_time_gradient, below), grape_forward_device,
+ * grape_backward_device. */
 int grape_create_open(grape_handle **out, const grape_problem *problem, const grape_lindblad *diss);
 
 /*
@@ -327,6 +328,25 @@ int grape_get_work(grape_handle *h, double *out, int n);
  *   - grid-point form: with t_0 fixed, dJ/dt_j = dJdt[j-1] - dJdt[j] (1 <= j < N_T), dJ/dt_{N_T} = dJdt[N_T-1].
  *     Scaling a grid of duration T: dJ/dT = sum_n (dt_n / T) dJdt[n]. */
 int grape_get_time_gradient(grape_handle *h, double *dJdt /* [N_T] */);
+
+/* The same derivative for an open-system handle (grape_create_open; an entry point only, the ABI version stays 7;
+ * csrc/grape_lindblad_tg.hip.h).  exp(L_n dt_n) commutes with L_n, so
+ *   dJdt[n] = dJ/d(dt_n) = -2 Re sum_k <<chi_k(t_{n+1}) | L_kn rho_k(t_{n+1})>> = -2 Re sum_k <<L_kn^dagger chi_k(t_{n+1}) | rho_k(t_{n+1})>>
+ * with the stored forward states and the chi chain stepped back from chi_k(T): exact to rounding whatever the number of
+ * sub-steps, and at the cost of about one forward launch.  Under a Lindblad generator every extra moment costs fidelity, so
+ * the optimal duration is an interior optimum and this derivative locates it.
+ * Valid after a successful backward half on the current grid: grape_eval with G != NULL, grape_backward (chi_k(T) = c_k
+ * sigma_k with the f that call received, tau_k under J_T_ss), or grape_backward_chi (the caller's chi_k(T), which the handle
+ * still holds on the device).  A split-phase shard (K < K_total) returns the partial sum over its own trajectories, to be
+ * all-reduced like G.  Fixed per-interval pulse and shape values, grid-point form and dJ/dT as for grape_get_time_gradient.
+ * It launches its kernel on demand and owns its buffers (allocated by the first call, freed by grape_destroy): evaluations
+ * that never call it are unchanged; after it grape_get_tau_grads, grape_get_work, grape_get_timings and grape_get_storage
+ * return what they returned before and a grape_eval is bit for bit what it was.  Two calls give the same bits.
+ * GRAPE_ERR_INVALID with a message that names the reason (the handle stays usable): h == NULL (message: grape_last_error(NULL)),
+ * dJdt == NULL, a closed handle (use grape_get_time_gradient), no evaluation yet, the last evaluation had no gradient or
+ * failed, between grape_forward and the backward half, grape_set_tlist since, grape_eval_batch since.  GRAPE_ERR_TAYLOR: a
+ * series of the chi chain did not converge (cannot happen after a successful backward half, but is never silent). */
+int grape_open_time_gradient(grape_handle *h, double *dJdt /* [N_T] */);
 
 /* ABI v7.  Replaces the time grid of an existing handle (N_T unchanged): tlist [N_T+1], finite and strictly increasing as in
  * grape_create, else GRAPE_ERR_INVALID and the handle is unchanged.  Waits for work in flight, recomputes the time steps and

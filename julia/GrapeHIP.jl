@@ -500,4 +500,20 @@ function create_open(H0, Hc, cops, tlist, rho0, target; functional = 0, weights 
     return h
 end
 
+"""
+    open_time_gradient!(dJdt, h)
+
+`dJdt[n] = ∂J/∂Δt_n` (`length(dJdt) == N_T`) for a handle made by `create_open` (grape_open_time_gradient): the call of the
+duration loop of INTEGRATION.md 3b on an open system, where the optimal duration is an interior optimum.  A function of its
+own, not a method of `time_gradient!`: `Handle` does not record which constructor made it, and the library refuses
+`grape_get_time_gradient` on such a handle (and this call on a closed one) with a message.  Valid after `fg!` with a gradient,
+`grape_backward` or `grape_backward_chi` (then with the caller's `χ_k(T)`) on the current grid; fixed per-interval pulse and
+shape values, grid-point form and `dJ/dT` as for `time_gradient!`.
+"""
+function open_time_gradient!(dJdt::Vector{Float64}, h::Handle)
+    length(dJdt) == h.N_T || throw(DimensionMismatch("dJdt must have N_T = $(h.N_T) entries"))
+    check(h, GC.@preserve dJdt ccall((:grape_open_time_gradient, libgrape), Cint, (Ptr{Cvoid}, Ptr{Float64}), h.ptr, dJdt))
+    return dJdt
+end
+
 end # module
