@@ -34,7 +34,7 @@ EXPORTS = ["grape_create", "grape_destroy", "grape_eval", "grape_forward", "grap
            "grape_last_error", "grape_abi_version", "grape_set_fused_sweeps", "grape_get_sums", "grape_backward_xi",
            "grape_get_final_states", "grape_backward_chi",
            "grape_get_time_gradient", "grape_set_tlist", "grape_eval_batch", "grape_get_batch_info", "grape_create_open",
-           "grape_hvp", "grape_get_hvp_info", "grape_open_time_gradient"]
+           "grape_hvp", "grape_get_hvp_info", "grape_open_time_gradient", "grape_open_hvp", "grape_get_open_hvp_info"]
 
 
 class GrapeHipError(RuntimeError):
@@ -102,7 +102,7 @@ def build_asm(verbose: bool = False, workdir: str | None = None) -> str:
 def _sources():
     srcs = [os.path.join(_CSRC, f) for f in ("grape_hip.hip", "grape_t18.hip", "grape_kernels.hip.h", "grape_large.hip.h",
                                              "grape_series.hip.h", "grape_cheby.hip.h", "grape_t18.hip.h", "grape_t18_coeffs.h",
-                                             "grape_deriv3.hip.h", "grape_timegrad.hip.h", "grape_batch.hip.h", "grape_lindblad.hip.h", "grape_lindblad_tg.hip.h", "grape_hvp.hip.h", os.path.join("asm", "gen_t16.py"), os.path.join("asm", "gen_t16p.py"), os.path.join("asm", "gen_t18g.py"), os.path.join("asm", "gen_t18gp.py"), os.path.join("asm", "gen_d3.py"), os.path.join("asm", "gen_d3s.py"), os.path.join("asm", "gen_lg.py"), os.path.join("asm", "gen_d4.py"), os.path.join("asm", "gcn.py"))]
+                                             "grape_deriv3.hip.h", "grape_timegrad.hip.h", "grape_batch.hip.h", "grape_lindblad.hip.h", "grape_lindblad_tg.hip.h", "grape_hvp.hip.h", "grape_lindblad_hvp.hip.h", os.path.join("asm", "gen_t16.py"), os.path.join("asm", "gen_t16p.py"), os.path.join("asm", "gen_t18g.py"), os.path.join("asm", "gen_t18gp.py"), os.path.join("asm", "gen_d3.py"), os.path.join("asm", "gen_d3s.py"), os.path.join("asm", "gen_lg.py"), os.path.join("asm", "gen_d4.py"), os.path.join("asm", "gcn.py"))]
     return srcs, os.path.join(_HERE, "..", "include", "grape_hip.h")
 
 
@@ -215,6 +215,8 @@ def load_library():
     lib.grape_get_batch_info.argtypes = [vp, vp, ip]
     lib.grape_hvp.argtypes = [vp, ip, vp, vp]
     lib.grape_get_hvp_info.argtypes = [vp, vp, ip]
+    lib.grape_open_hvp.argtypes = [vp, ip, vp, vp]
+    lib.grape_get_open_hvp_info.argtypes = [vp, vp, ip]
     lib.grape_last_error.argtypes = [vp]
     lib.grape_last_error.restype = C.c_char_p
     lib.grape_abi_version.restype = ip
@@ -544,8 +546,10 @@ class GrapeHipOpen(GrapeHip):
     or [K, J, d, d] per trajectory, rates folded in;  rho0 / target: [K, d, d] (target=None: only forward + final_states +
     backward_chi);  row-major numpy in, transposed on the way as ``GrapeHip`` does.  ``final_states()`` returns [K, d, d],
     ``storage()`` [K, N_T+1, d, d], ``backward_chi`` takes [K, d, d].  tau_k = tr(target_k^dagger rho_k(T)).
-    ``time_gradient()`` is grape_open_time_gradient.  Not available (GrapeHipError, the handle stays usable): propagator,
-    storage(1), backward_xi, the device-pointer calls."""
+    ``time_gradient()`` is grape_open_time_gradient, ``open_hvp()`` / ``open_hvp_info()`` are grape_open_hvp /
+    grape_get_open_hvp_info.  Not available (GrapeHipError, the handle stays usable): propagator, storage(1), backward_xi, the
+    device-pointer calls, and the inherited ``hvp()`` (grape_hvp keeps its defined refusal of open handles; its message names
+    ``grape_open_hvp``)."""
 
     def __init__(self, H0, Hc, cops, tlist, rho0, target, weights=None, functional=J_T_SM, shape=None, K_total=None,
                  device=0, chi_min_norm=0.0, prop_tolerance=0.0):
@@ -644,6 +648,28 @@ class GrapeHipOpen(GrapeHip):
         out = np.empty(self.N_T)
         self._chk(self._lib.grape_open_time_gradient(self._h, out.ctypes.data))
         return out
+
+    def open_hvp(self, V):
+        """Exact Hessian-vector products at the pulses of the last evaluation (grape_open_hvp): ``V`` [L*N_T] -> H v [L*N_T], or
+        [nv, L*N_T] -> [nv, L*N_T] (all directions in one call, side by side on the GPU).  Needs a successful ``eval`` or
+        ``forward`` on the current time grid; the built-in functional only (include/grape_hip.h lists the refusals).  A method of
+        its own, as the C call is: the inherited ``hvp`` stays grape_hvp, which refuses an open handle."""
+        v = np.ascontiguousarray(V, dtype=np.float64)
+        LN = self.L * self.N_T
+        if v.ndim not in (1, 2) or v.shape[-1] != LN or v.size == 0:
+            raise ValueError(f"V must be [L*N_T] = [{LN}] or [nv, {LN}] with nv >= 1, got {v.shape}")
+        nv = 1 if v.ndim == 1 else v.shape[0]
+        out = np.empty_like(v)
+        self._chk(self._lib.grape_open_hvp(self._h, nv, v.ctypes.data, out.ctypes.data))
+        return out
+
+    def open_hvp_info(self):
+        """What the last ``open_hvp`` did (grape_get_open_hvp_info): series terms and (sub-)steps summed over the workgroups of both
+        sweeps, directions per launch group, bytes of HVP storage the handle holds, milliseconds of the call."""
+        out = np.zeros(7)
+        self._lib.grape_get_open_hvp_info(self._h, out.ctypes.data, 7)
+        return dict(series_terms=int(out[0]), series_steps=int(out[1]), dirs_per_group=int(out[2]), bytes=int(out[3]), ms=float(out[4]),
+                    terms_forward=int(out[5]), terms_backward=int(out[6]))
 
     def backward_xi(self, xi, lambda_b, f_total=None, chi=None):
         dummy = np.zeros(2)

@@ -17,6 +17,7 @@
 #include "grape_lindblad.hip.h"
 #include "grape_lindblad_tg.hip.h"
 #include "grape_hvp.hip.h"
+#include "grape_lindblad_hvp.hip.h"
 
 #include <rccl/rccl.h>
 #include <dlfcn.h>
@@ -1469,6 +1470,17 @@ struct OpenCtx {
     size_t ws_mats = 0;           // matrices (2 NP^2 doubles) d_ws holds
     double2 *d_tq = nullptr;      // [K][N_T] per-trajectory terms of dJ/d(dt_n) (allocated on first use)
     double *d_dJdt = nullptr;     // [N_T]
+    // grape_open_hvp (grape_lindblad_hvp.hip.h): Hessian-vector products on the stored rho_k(t_n).  Validity is a
+    // word of its own: tg_state asks for a backward half, this call needs the forward half alone.  The storage is allocated
+    // by the first call and grows with the directions of a launch group.
+    enum { HV_NONE, HV_READY, HV_FAILED, HV_NEW_GRID, HV_BATCH };
+    int hv_state = HV_NONE;
+    int hv_cap = 0;               // directions the storage holds
+    size_t hv_bytes = 0;
+    double *d_hvV = nullptr, *d_hvws = nullptr, *d_hvds = nullptr, *d_hvout = nullptr;
+    double2 *d_hvdtau = nullptr, *d_hvdcoef = nullptr, *d_hvtg = nullptr;
+    unsigned long long *d_hvstats = nullptr;
+    double hv_info[7] = {0., 0., 0., 0., 0., 0., 0.};   // grape_get_open_hvp_info
 };
 
 namespace {
@@ -1566,6 +1578,7 @@ int open_forward(grape_handle *h, const double *pulsevals, double *tau) {
     h->have_forward = false;
     o->have_bwd = false;
     o->tg_state = OpenCtx::TG_FAILED;   // (until this sweep has succeeded)
+    o->hv_state = OpenCtx::HV_FAILED;
     HIPCHK(h, hipMemcpyAsync(o->d_eps, pulsevals, nl * 8, hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemsetAsync(o->d_flags, 0, 8 * sizeof(int), h->stream));
     HIPCHK(h, hipMemsetAsync(o->d_stats, 0, 2 * (K + K * h->L) * sizeof(unsigned long long), h->stream));
@@ -1586,6 +1599,7 @@ int open_forward(grape_handle *h, const double *pulsevals, double *tau) {
     if (rc) return rc;
     h->have_forward = true;
     o->tg_state = OpenCtx::TG_FORWARD_ONLY;
+    o->hv_state = OpenCtx::HV_READY;
     if (tau) memcpy(tau, o->out.data(), 2 * K * 8);
     return GRAPE_OK;
 }
@@ -1706,6 +1720,7 @@ int open_set_tlist(grape_handle *h, const double *tlist) {
     h->have_forward = false;
     o->have_bwd = false;
     o->tg_state = OpenCtx::TG_NEW_GRID;
+    o->hv_state = OpenCtx::HV_NEW_GRID;
     return GRAPE_OK;
 }
 
@@ -1745,6 +1760,135 @@ int open_time_gradient(grape_handle *h, double *dJdt) {
     HIPCHK(h, hipMemcpyAsync(flags, o->d_flags, sizeof(flags), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return open_status(h, flags[0]);
+}
+
+#define OPEN_HV_REFUSE(text) do { h->err = "grape_open_hvp: " text; return GRAPE_ERR_INVALID; } while (0)
+#define OPEN_HVF_THREADS(np) ((np) * (np) / 4)
+
+void open_hvp_release(OpenCtx *o) {
+    void *bufs[] = {o->d_hvV, o->d_hvws, o->d_hvds, o->d_hvout, o->d_hvdtau, o->d_hvdcoef, o->d_hvtg, o->d_hvstats};
+    for (void *b : bufs)
+        if (b) {
+            hipFree(b);
+            o->bufs.erase(std::remove(o->bufs.begin(), o->bufs.end(), b), o->bufs.end());
+        }
+    o->d_hvV = o->d_hvws = o->d_hvds = o->d_hvout = nullptr;
+    o->d_hvdtau = o->d_hvdcoef = o->d_hvtg = nullptr;
+    o->d_hvstats = nullptr;
+    o->bytes -= o->hv_bytes;
+    o->hv_cap = 0; o->hv_bytes = 0;
+}
+
+// bytes of storage one direction needs: the workspaces of its K L backward workgroups (the K forward ones fit inside),
+// rho', the per-trajectory terms, tau', c', the statistics, V and H v
+size_t open_hvp_bytes_per_direction(const grape_handle *h) {
+    const size_t K = (size_t)h->K, L = (size_t)h->L, LN = L * h->N_T, m2 = 2 * (size_t)h->NP * h->NP, J = (size_t)h->open->J;
+    return K * L * (16 + 4 * J) * m2 * 8 + K * (size_t)(h->N_T + 1) * m2 * 8 + K * LN * 16 + K * 32 + 2 * (K + K * L) * 8 + 2 * LN * 8;
+}
+
+// directions per launch group and storage for that many: the budget rule of hvp_reserve (half of what the device has free,
+// counting what the storage already holds, at most 8 GB; GRAPE_HVP_DIRS overrides).  The storage only grows.
+int open_hvp_reserve(grape_handle *h, int nv, int *dirs) {
+    OpenCtx *o = h->open;
+    const size_t per = open_hvp_bytes_per_direction(h);
+    int nd = std::min(nv, 65535);   // (the direction is grid.z of the backward launch)
+    if (h->hvp_dirs_env > 0) nd = std::min(nd, h->hvp_dirs_env);
+    else if (nd > o->hv_cap) {
+        size_t free_b = 0, total_b = 0;
+        HIPCHK(h, hipMemGetInfo(&free_b, &total_b));
+        const double budget = std::min(0.5 * ((double)free_b + (double)o->hv_bytes), 8.0 * 1073741824.0);
+        nd = (int)std::max<double>(1.0, std::min<double>((double)nd, std::floor(budget / (double)per)));
+    }
+    *dirs = nd;
+    if (nd <= o->hv_cap) return GRAPE_OK;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    open_hvp_release(o);
+    const size_t n = (size_t)nd, K = (size_t)h->K, L = (size_t)h->L, LN = L * h->N_T, m2 = 2 * (size_t)h->NP * h->NP, J = (size_t)o->J;
+    const size_t before = o->bytes;
+    int rc = GRAPE_OK;
+    auto get = [&](auto **ptr, size_t count) {
+        if (rc == GRAPE_OK && open_alloc(o, ptr, count) != hipSuccess) {
+            h->err = "grape_open_hvp: out of device memory for the storage of " + std::to_string(nd) + " directions (" +
+                     std::to_string(per * n >> 20) + " MB); GRAPE_HVP_DIRS=<n> makes the launch groups smaller";
+            (void)hipGetLastError();
+            *ptr = nullptr;
+            rc = GRAPE_ERR_HIP;
+        }
+    };
+    get(&o->d_hvV, n * LN); get(&o->d_hvws, n * K * L * (16 + 4 * J) * m2); get(&o->d_hvds, n * K * (size_t)(h->N_T + 1) * m2);
+    get(&o->d_hvout, n * LN); get(&o->d_hvdtau, n * K); get(&o->d_hvdcoef, n * K); get(&o->d_hvtg, n * K * LN);
+    get(&o->d_hvstats, 2 * n * (K + K * L));
+    o->hv_bytes = o->bytes - before;
+    if (rc) { open_hvp_release(o); return rc; }
+    o->hv_cap = nd;
+    return GRAPE_OK;
+}
+
+// HV[j] = (d^2 J / d eps^2) V[j] at the pulses of the last forward half, from the stored rho_k(t_n), tau, f and the device copy
+// of the pulses (grape_lindblad_hvp.hip.h).  Touches nothing an evaluation or a getter reads: storage of its own, the timing
+// events and the statistics of the evaluation are left alone; d_flags is cleared by every launch group, as by every launch.
+int open_hvp(grape_handle *h, int nv, const double *V, double *HV) {
+    OpenCtx *o = h->open;
+    if (h->K != h->K_total) OPEN_HV_REFUSE("a split-phase shard (K < K_total) is out of scope: f' would need an all-reduce of its own");
+    if (h->no_target) OPEN_HV_REFUSE("this handle has no target states (grape_problem.target == NULL): chi'(T) would be the caller's");
+    switch (o->hv_state) {
+    case OpenCtx::HV_READY: break;
+    case OpenCtx::HV_NONE: OPEN_HV_REFUSE("no valid forward state: no evaluation on this handle yet");
+    case OpenCtx::HV_NEW_GRID: OPEN_HV_REFUSE("no valid forward state: grape_set_tlist came after the last evaluation, the stored states belong to the previous grid");
+    case OpenCtx::HV_BATCH: OPEN_HV_REFUSE("no valid forward state: the last call was grape_eval_batch, the stored states are not those of one defined evaluation");
+    default: OPEN_HV_REFUSE("no valid forward state: the last forward sweep failed");
+    }
+    const auto t0 = std::chrono::steady_clock::now();
+    HIPCHK(h, hipSetDevice(h->device));
+    (void)hipGetLastError();
+    int nd = 0;
+    const int rc = open_hvp_reserve(h, nv, &nd);
+    if (rc) return rc;
+    const size_t K = (size_t)h->K, L = (size_t)h->L, LN = L * h->N_T;
+    hipStream_t s = h->stream;
+    LindHvpArgs q{};
+    q.a = open_args(h);
+    q.a.f = o->d_out + 2 * K;   // sum_k w_k tau_k as the forward half reduced it (d_f belongs to the backward half)
+    q.a.ws = nullptr; q.a.tg = nullptr; q.a.stats = nullptr; q.a.rho = nullptr;
+    q.V = o->d_hvV; q.dstore = o->d_hvds; q.dtau = o->d_hvdtau; q.dcoef = o->d_hvdcoef; q.tg = o->d_hvtg; q.ws = o->d_hvws;
+    q.stats = o->d_hvstats;
+    std::vector<unsigned long long> st;
+    double terms_fw = 0., terms_bw = 0., substeps = 0.;
+    for (int j0 = 0; j0 < nv; j0 += nd) {
+        const int ng = std::min(nd, nv - j0);
+        const size_t nst = 2 * (size_t)ng * (K + K * L);
+        q.nd = ng;
+        HIPCHK(h, hipMemcpyAsync(o->d_hvV, V + (size_t)j0 * LN, (size_t)ng * LN * 8, hipMemcpyHostToDevice, s));
+        HIPCHK(h, hipMemsetAsync(o->d_flags, 0, 8 * sizeof(int), s));
+        HIPCHK(h, hipMemsetAsync(o->d_hvstats, 0, nst * sizeof(unsigned long long), s));
+        OPEN_LAUNCH(lind_hvp_forward_kernel, dim3((unsigned)K, (unsigned)ng), OPEN_HVF_THREADS, q)
+        hipLaunchKernelGGL(lind_hvp_boundary_kernel, dim3((unsigned)ng), dim3(64), 0, s, q);
+        OPEN_LAUNCH(lind_hvp_backward_kernel, dim3((unsigned)K, (unsigned)L, (unsigned)ng), OPEN_BWD_THREADS, q)
+        HIPCHK(h, hipGetLastError());
+        // (H v)_j = -2 Re sum_k of the per-trajectory terms: the gradient's reduction, fixed order
+        for (int j = 0; j < ng; ++j)
+            hipLaunchKernelGGL(grad_reduce_kernel, dim3((unsigned)((LN + 15) / 16)), dim3(256), 0, s, o->d_hvtg + (size_t)j * K * LN, h->K,
+                               (int)LN, o->d_hvout + (size_t)j * LN, (const double2 *)nullptr);
+        HIPCHK(h, hipGetLastError());
+        int flags[8] = {0};
+        st.assign(nst, 0ull);
+        HIPCHK(h, hipMemcpyAsync(HV + (size_t)j0 * LN, o->d_hvout, (size_t)ng * LN * 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(h, hipMemcpyAsync(st.data(), o->d_hvstats, nst * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+        HIPCHK(h, hipMemcpyAsync(flags, o->d_flags, sizeof(flags), hipMemcpyDeviceToHost, s));
+        HIPCHK(h, hipStreamSynchronize(s));
+        for (size_t w = 0; w < nst / 2; ++w) {
+            (w < (size_t)ng * K ? terms_fw : terms_bw) += (double)st[2 * w];
+            substeps += (double)st[2 * w + 1];
+        }
+        if (flags[0] & 16) {
+            h->err = "grape_open_hvp: a series did not converge within 200 terms (direction group starting at " + std::to_string(j0) + ")";
+            return GRAPE_ERR_TAYLOR;
+        }
+    }
+    o->hv_info[0] = terms_fw + terms_bw; o->hv_info[1] = substeps; o->hv_info[2] = (double)nd; o->hv_info[3] = (double)o->hv_bytes;
+    o->hv_info[4] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    o->hv_info[5] = terms_fw; o->hv_info[6] = terms_bw;
+    return GRAPE_OK;
 }
 
 }  // namespace
@@ -1858,6 +2002,7 @@ int grape_create_open(grape_handle **out, const grape_problem *p, const grape_li
     if (p->chi_min_norm > 0) h->chi_min_norm = p->chi_min_norm;
     if (p->prop_tolerance > 0) h->series_tol = p->prop_tolerance;
     o->J = diss->J; o->cops_per_traj = diss->cops_per_traj ? 1 : 0;
+    if (const char *envh = getenv("GRAPE_HVP_DIRS")) h->hvp_dirs_env = std::max(0, atoi(envh));   // (grape_open_hvp: as grape_create)
     o->Kj = o->cops_per_traj ? p->K : 1; o->Kc = p->hc_per_traj ? p->K : 1;
 
     auto fail = [&](int code) { g_create_error = h->err; return code; };   // (the guard releases the handle)
@@ -4097,6 +4242,25 @@ int grape_open_time_gradient(grape_handle *h, double *dJdt) try {
 }
 GRAPE_BARRIER(h ? &h->err : &g_create_error)
 
+int grape_open_hvp(grape_handle *h, int nv, const double *V, double *HV) try {
+    if (!h) { g_create_error = "grape_open_hvp: h == NULL"; return GRAPE_ERR_INVALID; }
+    if (nv <= 0 || !V || !HV) { h->err = "grape_open_hvp: nv must be positive, V and HV must not be NULL"; return GRAPE_ERR_INVALID; }
+    if (!h->open) {
+        h->err = "grape_open_hvp: not an open-system handle (grape_create_open); grape_hvp is the call for a closed one";
+        return GRAPE_ERR_INVALID;
+    }
+    return open_hvp(h, nv, V, HV);
+}
+GRAPE_BARRIER(h ? &h->err : &g_create_error)
+
+int grape_get_open_hvp_info(grape_handle *h, double *out, int n) try {
+    if (!h || !out || !h->open) return GRAPE_ERR_INVALID;
+    const int m = std::max(0, std::min(n, 7));
+    for (int i = 0; i < m; ++i) out[i] = h->open->hv_info[i];
+    return m;
+}
+GRAPE_BARRIER(h ? &h->err : &g_create_error)
+
 int grape_set_tlist(grape_handle *h, const double *tlist) try {
     if (!h || !tlist) return GRAPE_ERR_INVALID;
     const int N_T = h->N_T;
@@ -4314,7 +4478,7 @@ int batch_group(grape_handle *h, const BatchStrides &st, int p0, int Pg, const d
 void batch_invalidate(grape_handle *h) {
     h->tg_state = 0;
     for (grape_handle *c : h->shards) c->tg_state = 0;
-    if (h->open) h->open->tg_state = OpenCtx::TG_BATCH;
+    if (h->open) { h->open->tg_state = OpenCtx::TG_BATCH; h->open->hv_state = OpenCtx::HV_BATCH; }
 }
 
 }  // namespace
@@ -4447,7 +4611,7 @@ void hvp_launch(const HvpArgs &a, int nd, int nct, hipStream_t s) {
 
 // why this handle cannot give H v (nullptr: it can); every test precedes the first HIP call
 const char *hvp_refusal(const grape_handle *h) {
-    if (h->open) return "open-system handles are out of scope (DESIGN.md 14)";
+    if (h->open) return "open-system handles are out of scope (DESIGN.md 14): grape_open_hvp is the call for one";
     if (!h->shards.empty() || h->p.ndev > 1) return "several devices behind one handle (ndev > 1) are out of scope";
     if (h->N > 64) return "N > 64 is out of scope (the kernels work on at most four 16-wide tiles)";
     if (h->K != h->K_total) return "a split-phase shard (K < K_total) is out of scope: f' would need an all-reduce of its own";

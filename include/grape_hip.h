@@ -411,7 +411,8 @@ int grape_get_batch_info(grape_handle *h, double *out, int n);
  *     has ||term|| <= prop_tolerance ||sum|| (default 1e-17), after at most 200 terms -- beyond that GRAPE_ERR_TAYLOR, the
  *     handle stays usable.
  *   - GRAPE_ERR_INVALID with a message that names the reason, the handle stays usable: h == NULL, nv <= 0, V == NULL,
- *     HV == NULL; N > 64; ndev > 1; a split-phase shard (K < K_total); an open-system handle; a handle without targets; the
+ *     HV == NULL; N > 64; ndev > 1; a split-phase shard (K < K_total); an open-system handle (grape_open_hvp is the call
+ *     for one); a handle without targets; the
  *     built-in running cost (Dpen, lambda_b != 0); no valid forward state (no evaluation yet, the last one failed,
  *     grape_set_tlist came since, or the last call was grape_eval_batch).  A caller-supplied chi (grape_backward_chi)
  *     is out of scope: it would need the caller's chi'(T).  The full Hessian is nv = L*N_T unit directions. */
@@ -424,6 +425,43 @@ int grape_hvp(grape_handle *h, int nv, const double *V, double *HV);
  * [6] of the backward sweeps ([0] = [5] + [6]; tools/hvp_ab.py counts the executed matrix instructions from them).
  * Returns the number of entries written (at most n). */
 int grape_get_hvp_info(grape_handle *h, double *out, int n);
+
+/* Exact Hessian-vector products on an open-system handle (grape_create_open; entry points only, the ABI version stays 7;
+ * csrc/grape_lindblad_hvp.hip.h):
+ *   HV[j] = (d^2 J / d eps^2) V[j],  j < nv,  at the pulses of the last evaluation;  V, HV: [nv][L*N_T], control-major.
+ * J is the handle's built-in functional (J_T_sm / ss / re with weights, K == K_total).  With B = sum_l v_nl s_ln D_l the
+ * directional derivative of the generator of interval n, a tangent forward sweep carries rho'_k next to the STORED rho_k(t_n)
+ * (u'_{a+1} = h / (a+1) (L u'_a + B u_a)), chi'_k(T) = c'_k sigma_k (sm: w_k f' / K^2, ss: w_k tau'_k / K, re: 0), and a
+ * backward sweep carries chi, chi', P_l, P'_l under L^dagger:
+ *   (H v)_nl = -2 Re sum_k [ <<P'_l | rho_k(t_n)>> + <<P_l | rho'_k(t_n)>> ]
+ * exact to rounding like the gradient, term by term through the series of every (sub-)step; not a difference of gradients.
+ *   - Valid after any successful forward half on the current grid: grape_eval with or without G, grape_forward with or
+ *     without its backward half.  It reads only the stored forward states, tau, f and the device copy of the pulses and
+ *     recomputes the backward chain itself, not normalised (everything is linear in chi, the stopping rule is relative).
+ *   - The directions are a grid axis of the kernels (forward grid (K, nv), backward grid (K, L, nv)); a direction's result
+ *     does not depend on nv or on the launch groups, bit for bit, and two calls give the same bits.  The storage is
+ *     allocated by the first call, grows with nv in launch groups under the memory budget of grape_hvp (GRAPE_HVP_DIRS=<n>,
+ *     read at create, sets the group size) and is freed by grape_destroy.
+ *   - It owns its buffers and leaves the timing events and the statistics alone: after it grape_open_time_gradient,
+ *     grape_get_tau_grads, grape_get_work, grape_get_timings and grape_get_storage(0) return what they returned before and
+ *     a grape_eval is bit for bit what it was.
+ *   - Series: m = ceil(beta_n dt_n / theta) sub-steps with the beta_n and theta of the gradient (B does not enter beta); all
+ *     chains carry over between sub-steps; a series stops when EVERY chain has ||term||_F <= prop_tolerance ||sum||_F (a chain
+ *     that is identically zero counts as converged), after at most 200 terms -- beyond that GRAPE_ERR_TAYLOR, and the
+ *     handle stays usable.
+ *   - GRAPE_ERR_INVALID with a message that names the reason, the handle stays usable: h == NULL (message:
+ *     grape_last_error(NULL)), nv <= 0, V == NULL, HV == NULL; a closed handle (use grape_hvp); a split-phase shard
+ *     (K < K_total); a handle without targets; no valid forward state (no evaluation yet, the last one failed,
+ *     grape_set_tlist came since, or the last call was grape_eval_batch).  A caller-supplied chi (grape_backward_chi) is
+ *     out of scope: it would need the caller's chi'(T). */
+int grape_open_hvp(grape_handle *h, int nv, const double *V, double *HV);
+
+/* What the last grape_open_hvp of this handle did, in the slots of grape_get_hvp_info: [0] series terms and [1] (sub-)steps
+ * summed over the workgroups of both sweeps (K nv forward and K L nv backward workgroups, N_T steps each when no interval is
+ * cut);  [2] directions per launch group;  [3] bytes of HVP storage the handle holds;  [4] milliseconds of the last call
+ * (host wall time, copies included);  [5] the series terms of the tangent forward sweeps, [6] of the backward sweeps
+ * ([0] = [5] + [6]).  Returns the number of entries written (at most n); GRAPE_ERR_INVALID for a closed handle. */
+int grape_get_open_hvp_info(grape_handle *h, double *out, int n);
 
 const char *grape_last_error(grape_handle *h); /* h may be NULL: error of the last failed create */
 int grape_abi_version(void);

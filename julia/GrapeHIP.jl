@@ -516,4 +516,37 @@ function open_time_gradient!(dJdt::Vector{Float64}, h::Handle)
     return dJdt
 end
 
+"""
+    open_hvp!(HV, h, V)
+
+Exact Hessian-vector products `HV[:, j] = (∂²J/∂ε²) V[:, j]` for a handle made by `create_open` (grape_open_hvp), at the pulses
+of the last evaluation: `V`, `HV` are `L*N_T × nv` (or vectors of length `L*N_T`), control-major like the pulse vector.  All
+directions run side by side on the GPU.  A function of its own, as `open_time_gradient!` is: the library refuses `grape_hvp`
+on such a handle (and this call on a closed one) with a message.  Valid after `fg!` (with or without gradient) or
+`grape_forward` on the current time grid, for the built-in functionals with `K == K_total`.
+"""
+function open_hvp!(HV::VecOrMat{Float64}, h::Handle, V::VecOrMat{Float64})
+    isempty(h.fixed) || error("GrapeHIP.open_hvp!: handles with pseudo-controls are not supported (the directions have no entries for them)")
+    size(V, 1) == h.L * h.N_T || throw(DimensionMismatch("V must be L*N_T = $(h.L * h.N_T) × nv"))
+    size(HV) == size(V) || throw(DimensionMismatch("HV must have the size of V"))
+    nv = size(V, 2)
+    nv >= 1 || throw(DimensionMismatch("V must hold at least one direction"))
+    check(h, GC.@preserve HV V ccall((:grape_open_hvp, libgrape), Cint, (Ptr{Cvoid}, Cint, Ptr{Float64}, Ptr{Float64}), h.ptr, nv, V, HV))
+    return HV
+end
+
+"""
+    open_hvp_info(h)
+
+What the last `open_hvp!` did (grape_get_open_hvp_info): series `terms` and (sub-)`steps` summed over the workgroups of both
+sweeps, directions per launch group, `bytes` of storage held by the handle, milliseconds of the call, and the terms of the
+tangent forward / the backward sweeps.
+"""
+function open_hvp_info(h::Handle)
+    out = zeros(Float64, 7)
+    GC.@preserve out ccall((:grape_get_open_hvp_info, libgrape), Cint, (Ptr{Cvoid}, Ptr{Float64}, Cint), h.ptr, out, 7)
+    return (terms = Int(out[1]), steps = Int(out[2]), dirs_per_group = Int(out[3]), bytes = Int(out[4]), ms = out[5],
+            terms_forward = Int(out[6]), terms_backward = Int(out[7]))
+end
+
 end # module
