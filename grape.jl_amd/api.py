@@ -34,7 +34,8 @@ EXPORTS = ["grape_create", "grape_destroy", "grape_eval", "grape_forward", "grap
            "grape_last_error", "grape_abi_version", "grape_set_fused_sweeps", "grape_get_sums", "grape_backward_xi",
            "grape_get_final_states", "grape_backward_chi",
            "grape_get_time_gradient", "grape_set_tlist", "grape_eval_batch", "grape_get_batch_info", "grape_create_open",
-           "grape_hvp", "grape_get_hvp_info", "grape_open_time_gradient", "grape_open_hvp", "grape_get_open_hvp_info"]
+           "grape_hvp", "grape_get_hvp_info", "grape_open_time_gradient", "grape_open_hvp", "grape_get_open_hvp_info",
+           "grape_open_eval_batch", "grape_get_open_batch_info"]
 
 
 class GrapeHipError(RuntimeError):
@@ -102,7 +103,7 @@ def build_asm(verbose: bool = False, workdir: str | None = None) -> str:
 def _sources():
     srcs = [os.path.join(_CSRC, f) for f in ("grape_hip.hip", "grape_t18.hip", "grape_kernels.hip.h", "grape_large.hip.h",
                                              "grape_series.hip.h", "grape_cheby.hip.h", "grape_t18.hip.h", "grape_t18_coeffs.h",
-                                             "grape_deriv3.hip.h", "grape_timegrad.hip.h", "grape_batch.hip.h", "grape_lindblad.hip.h", "grape_lindblad_tg.hip.h", "grape_hvp.hip.h", "grape_lindblad_hvp.hip.h", os.path.join("asm", "gen_t16.py"), os.path.join("asm", "gen_t16p.py"), os.path.join("asm", "gen_t18g.py"), os.path.join("asm", "gen_t18gp.py"), os.path.join("asm", "gen_d3.py"), os.path.join("asm", "gen_d3s.py"), os.path.join("asm", "gen_lg.py"), os.path.join("asm", "gen_d4.py"), os.path.join("asm", "gcn.py"))]
+                                             "grape_deriv3.hip.h", "grape_timegrad.hip.h", "grape_batch.hip.h", "grape_lindblad.hip.h", "grape_lindblad_tg.hip.h", "grape_hvp.hip.h", "grape_lindblad_hvp.hip.h", "grape_lindblad_batch.hip.h", os.path.join("asm", "gen_t16.py"), os.path.join("asm", "gen_t16p.py"), os.path.join("asm", "gen_t18g.py"), os.path.join("asm", "gen_t18gp.py"), os.path.join("asm", "gen_d3.py"), os.path.join("asm", "gen_d3s.py"), os.path.join("asm", "gen_lg.py"), os.path.join("asm", "gen_d4.py"), os.path.join("asm", "gcn.py"))]
     return srcs, os.path.join(_HERE, "..", "include", "grape_hip.h")
 
 
@@ -217,6 +218,8 @@ def load_library():
     lib.grape_get_hvp_info.argtypes = [vp, vp, ip]
     lib.grape_open_hvp.argtypes = [vp, ip, vp, vp]
     lib.grape_get_open_hvp_info.argtypes = [vp, vp, ip]
+    lib.grape_open_eval_batch.argtypes = [vp, ip, vp, vp, vp, vp]
+    lib.grape_get_open_batch_info.argtypes = [vp, vp, ip]
     lib.grape_last_error.argtypes = [vp]
     lib.grape_last_error.restype = C.c_char_p
     lib.grape_abi_version.restype = ip
@@ -547,7 +550,8 @@ class GrapeHipOpen(GrapeHip):
     backward_chi);  row-major numpy in, transposed on the way as ``GrapeHip`` does.  ``final_states()`` returns [K, d, d],
     ``storage()`` [K, N_T+1, d, d], ``backward_chi`` takes [K, d, d].  tau_k = tr(target_k^dagger rho_k(T)).
     ``time_gradient()`` is grape_open_time_gradient, ``open_hvp()`` / ``open_hvp_info()`` are grape_open_hvp /
-    grape_get_open_hvp_info.  Not available (GrapeHipError, the handle stays usable): propagator, storage(1), backward_xi, the
+    grape_get_open_hvp_info, ``open_eval_batch()`` / ``open_batch_info()`` grape_open_eval_batch / grape_get_open_batch_info
+    (the inherited ``eval_batch`` stays the loop over ``eval`` it is on such a handle).  Not available (GrapeHipError, the handle stays usable): propagator, storage(1), backward_xi, the
     device-pointer calls, and the inherited ``hvp()`` (grape_hvp keeps its defined refusal of open handles; its message names
     ``grape_open_hvp``)."""
 
@@ -670,6 +674,31 @@ class GrapeHipOpen(GrapeHip):
         self._lib.grape_get_open_hvp_info(self._h, out.ctypes.data, 7)
         return dict(series_terms=int(out[0]), series_steps=int(out[1]), dirs_per_group=int(out[2]), bytes=int(out[3]), ms=float(out[4]),
                     terms_forward=int(out[5]), terms_backward=int(out[6]))
+
+    def open_eval_batch(self, pulsevals, gradient=True):
+        """P pulse vectors through this handle's problem side by side on the GPU (grape_open_eval_batch): ``pulsevals``
+        [P, L*N_T] -> (J [P], G [P, L*N_T] or None, tau [P, K]); row p is what ``eval(pulsevals[p])`` returns, to rounding, and
+        does not depend on the other rows, bit for bit.  Leaves the handle's last ordinary evaluation as it was
+        (``time_gradient``, ``open_hvp``, ``tau_grads``, ``storage`` still answer for it)."""
+        x = np.ascontiguousarray(pulsevals, dtype=np.float64)
+        if x.ndim != 2 or x.shape[1] != self.L * self.N_T:
+            raise ValueError(f"pulsevals must be [P, L*N_T] = [P, {self.L * self.N_T}], got {x.shape}")
+        P = x.shape[0]
+        J = np.empty(P)
+        G = np.empty((P, self.L * self.N_T)) if gradient else None
+        tau = np.empty((P, self.K), dtype=np.complex128)
+        self._chk(self._lib.grape_open_eval_batch(self._h, P, x.ctypes.data, J.ctypes.data,
+                                                  None if G is None else G.ctypes.data, tau.ctypes.data))
+        return J, G, tau
+
+    def open_batch_info(self):
+        """What the last ``open_eval_batch`` did (grape_get_open_batch_info): sets per launch group, number of groups, bytes of
+        batch storage the handle holds, milliseconds of the call, series terms of the forward and of the backward sweeps and
+        (sub-)steps summed over all workgroups of the call."""
+        out = np.zeros(7)
+        self._lib.grape_get_open_batch_info(self._h, out.ctypes.data, 7)
+        return dict(sets_per_group=int(out[0]), groups=int(out[1]), bytes=int(out[2]), ms=float(out[3]), terms_forward=int(out[4]),
+                    terms_backward=int(out[5]), series_steps=int(out[6]))
 
     def backward_xi(self, xi, lambda_b, f_total=None, chi=None):
         dummy = np.zeros(2)

@@ -18,6 +18,7 @@
 #include "grape_lindblad_tg.hip.h"
 #include "grape_hvp.hip.h"
 #include "grape_lindblad_hvp.hip.h"
+#include "grape_lindblad_batch.hip.h"
 
 #include <rccl/rccl.h>
 #include <dlfcn.h>
@@ -1481,6 +1482,17 @@ struct OpenCtx {
     double2 *d_hvdtau = nullptr, *d_hvdcoef = nullptr, *d_hvtg = nullptr;
     unsigned long long *d_hvstats = nullptr;
     double hv_info[7] = {0., 0., 0., 0., 0., 0., 0.};   // grape_get_open_hvp_info
+    // grape_open_eval_batch (grape_lindblad_batch.hip.h): every per-set buffer belongs to the call -- pulses, stored
+    // states, workspaces, tau | sums, ||chi||, tau_grads, G, flags, statistics.  Allocated by the first call, grows with the sets
+    // of a launch group.  Nothing an ordinary evaluation or a getter reads is touched, no state word changes.
+    int ob_cap = 0;               // sets the storage holds
+    int ob_sets_env = 0;          // GRAPE_OPEN_BATCH_SETS: sets per launch group (0: from the memory budget)
+    size_t ob_bytes = 0;
+    double *d_obeps = nullptr, *d_obstore = nullptr, *d_obws = nullptr, *d_obout = nullptr, *d_obrho = nullptr, *d_obG = nullptr;
+    double2 *d_obtg = nullptr;
+    int *d_obflags = nullptr;
+    unsigned long long *d_obstats = nullptr;
+    double ob_info[7] = {0., 0., 0., 0., 0., 0., 0.};   // grape_get_open_batch_info
 };
 
 namespace {
@@ -1560,12 +1572,12 @@ int open_refuse(grape_handle *h, const char *what) {
     return GRAPE_ERR_INVALID;
 }
 
-#define OPEN_LAUNCH(kernel, grid, threads_of, args)                                                          \
+#define OPEN_LAUNCH(kernel, grid, threads_of, ...)                                                           \
     switch (h->NP) {                                                                                         \
-    case 16: hipLaunchKernelGGL(kernel<16>, grid, dim3(threads_of(16)), 0, h->stream, args); break;          \
-    case 32: hipLaunchKernelGGL(kernel<32>, grid, dim3(threads_of(32)), 0, h->stream, args); break;          \
-    case 48: hipLaunchKernelGGL(kernel<48>, grid, dim3(threads_of(48)), 0, h->stream, args); break;          \
-    default: hipLaunchKernelGGL(kernel<64>, grid, dim3(threads_of(64)), 0, h->stream, args); break;          \
+    case 16: hipLaunchKernelGGL(kernel<16>, grid, dim3(threads_of(16)), 0, h->stream, __VA_ARGS__); break;   \
+    case 32: hipLaunchKernelGGL(kernel<32>, grid, dim3(threads_of(32)), 0, h->stream, __VA_ARGS__); break;   \
+    case 48: hipLaunchKernelGGL(kernel<48>, grid, dim3(threads_of(48)), 0, h->stream, __VA_ARGS__); break;   \
+    default: hipLaunchKernelGGL(kernel<64>, grid, dim3(threads_of(64)), 0, h->stream, __VA_ARGS__); break;   \
     }
 #define OPEN_FWD_THREADS(np) ((np) * (np) / 4)
 #define OPEN_BWD_THREADS(np) LindBwd<np>::NTH
@@ -1891,6 +1903,145 @@ int open_hvp(grape_handle *h, int nv, const double *V, double *HV) {
     return GRAPE_OK;
 }
 
+#define OPEN_OB_REFUSE(text) do { h->err = "grape_open_eval_batch: " text; return GRAPE_ERR_INVALID; } while (0)
+
+void open_batch_release(OpenCtx *o) {
+    void *bufs[] = {o->d_obeps, o->d_obstore, o->d_obws, o->d_obout, o->d_obrho, o->d_obG, o->d_obtg, o->d_obflags, o->d_obstats};
+    for (void *b : bufs)
+        if (b) {
+            hipFree(b);
+            o->bufs.erase(std::remove(o->bufs.begin(), o->bufs.end(), b), o->bufs.end());
+        }
+    o->d_obeps = o->d_obstore = o->d_obws = o->d_obout = o->d_obrho = o->d_obG = nullptr;
+    o->d_obtg = nullptr;
+    o->d_obflags = nullptr;
+    o->d_obstats = nullptr;
+    o->bytes -= o->ob_bytes;
+    o->ob_cap = 0; o->ob_bytes = 0;
+}
+
+LindBatchStrides open_batch_strides(const grape_handle *h) {
+    const size_t K = (size_t)h->K, L = (size_t)h->L, LN = L * h->N_T, m2 = 2 * (size_t)h->NP * h->NP, J = (size_t)h->open->J;
+    LindBatchStrides st{};
+    st.eps = LN; st.store = K * (size_t)(h->N_T + 1) * m2; st.ws = K * L * (8 + 2 * J) * m2; st.out = 2 * K + 8; st.k = K;
+    st.tg = K * LN; st.flags = 8; st.stats = 2 * (K + K * L);
+    return st;
+}
+
+// bytes of storage one pulse set needs: pulses and G, the stored rho_k(t_n), the workspaces of its K L backward workgroups,
+// tau | sums, ||chi||, tau_grads, flags, statistics
+size_t open_batch_bytes_per_set(const LindBatchStrides &st) {
+    return (2 * st.eps + st.store + st.ws + st.out + st.k) * 8 + st.tg * 16 + st.flags * sizeof(int) + st.stats * sizeof(unsigned long long);
+}
+
+// sets per launch group for a call with P sets, and storage for that many: the budget rule of open_hvp_reserve (half of what
+// the device has free, counting what the storage already holds, at most 8 GB; GRAPE_OPEN_BATCH_SETS overrides).  The storage
+// only grows.
+int open_batch_reserve(grape_handle *h, int P, const LindBatchStrides &st, int *sets) {
+    OpenCtx *o = h->open;
+    const size_t per = open_batch_bytes_per_set(st);
+    int ns = std::min(P, 65535);   // (the set is grid.y / grid.z of the launches)
+    if (o->ob_sets_env > 0) ns = std::min(ns, o->ob_sets_env);
+    else if (ns > o->ob_cap) {
+        size_t free_b = 0, total_b = 0;
+        HIPCHK(h, hipMemGetInfo(&free_b, &total_b));
+        const double budget = std::min(0.5 * ((double)free_b + (double)o->ob_bytes), 8.0 * 1073741824.0);
+        ns = (int)std::max<double>(1.0, std::min<double>((double)ns, std::floor(budget / (double)per)));
+    }
+    *sets = ns;
+    if (ns <= o->ob_cap) return GRAPE_OK;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    open_batch_release(o);
+    const size_t n = (size_t)ns, before = o->bytes;
+    int rc = GRAPE_OK;
+    auto get = [&](auto **ptr, size_t count) {
+        if (rc == GRAPE_OK && open_alloc(o, ptr, count) != hipSuccess) {
+            h->err = "grape_open_eval_batch: out of device memory for the storage of " + std::to_string(ns) + " pulse sets (" +
+                     std::to_string(per * n >> 20) + " MB); GRAPE_OPEN_BATCH_SETS=<n> makes the launch groups smaller";
+            (void)hipGetLastError();
+            *ptr = nullptr;
+            rc = GRAPE_ERR_HIP;
+        }
+    };
+    get(&o->d_obeps, n * st.eps); get(&o->d_obstore, n * st.store); get(&o->d_obws, n * st.ws); get(&o->d_obout, n * st.out);
+    get(&o->d_obrho, n * st.k); get(&o->d_obG, n * st.eps); get(&o->d_obtg, n * st.tg); get(&o->d_obflags, n * st.flags);
+    get(&o->d_obstats, n * st.stats);
+    o->ob_bytes = o->bytes - before;
+    if (rc) { open_batch_release(o); return rc; }
+    o->ob_cap = ns;
+    return GRAPE_OK;
+}
+
+// P evaluations side by side: forward grid (K, Pg), backward grid (K, L, Pg), the reductions segmented over the sets
+// (grape_lindblad_batch.hip.h).  Shares the static data of the handle, the current dts and the stream; every buffer a set
+// writes is storage of this call.  Touches nothing an evaluation or a getter reads: not d_store, d_eps, d_out, d_f, d_chi, d_tg,
+// d_flags, d_stats, the timing events or the state words.
+int open_eval_batch(grape_handle *h, int P, const double *pulsevals, double *J, double *G, double *tau) {
+    OpenCtx *o = h->open;
+    const auto t0 = std::chrono::steady_clock::now();
+    HIPCHK(h, hipSetDevice(h->device));
+    (void)hipGetLastError();
+    const LindBatchStrides st = open_batch_strides(h);
+    int Pg = 0;
+    const int rc = open_batch_reserve(h, P, st, &Pg);
+    if (rc) return rc;
+    const size_t K = (size_t)h->K, L = (size_t)h->L, LN = L * h->N_T;
+    hipStream_t s = h->stream;
+    LindArgs a = open_args(h);
+    a.eps = o->d_obeps; a.store = o->d_obstore; a.ws = o->d_obws; a.tau = (double2 *)o->d_obout; a.f = nullptr; a.rho = o->d_obrho;
+    a.tg = o->d_obtg; a.flags = o->d_obflags; a.stats = o->d_obstats; a.chi_in = nullptr;
+    // word [0] of a set's flags belongs to its forward sweep, word [1] to its backward sweep: a set whose forward half failed
+    // reports that, as grape_eval does, whatever its backward half then made of the states
+    LindArgs ab = a;
+    ab.flags = o->d_obflags + 1;
+    std::vector<double> out;
+    std::vector<int> flags;
+    std::vector<unsigned long long> stats;
+    double terms_fw = 0., terms_bw = 0., substeps = 0.;
+    int groups = 0;
+    for (int p0 = 0; p0 < P; p0 += Pg, ++groups) {
+        const int ng = std::min(Pg, P - p0);
+        const size_t n = (size_t)ng;
+        HIPCHK(h, hipMemcpyAsync(o->d_obeps, pulsevals + (size_t)p0 * LN, n * LN * 8, hipMemcpyHostToDevice, s));
+        HIPCHK(h, hipMemsetAsync(o->d_obflags, 0, n * st.flags * sizeof(int), s));
+        HIPCHK(h, hipMemsetAsync(o->d_obstats, 0, n * st.stats * sizeof(unsigned long long), s));
+        OPEN_LAUNCH(lind_batch_forward_kernel, dim3((unsigned)K, (unsigned)ng), OPEN_FWD_THREADS, a, st)
+        hipLaunchKernelGGL(lind_batch_tau_reduce_kernel, dim3(1, (unsigned)ng), dim3(64), 0, s, o->d_obout, (const double *)o->d_weights, h->K, st);
+        if (G) {   // f of every set is on the device, where its reduction left it
+            OPEN_LAUNCH(lind_batch_backward_kernel, dim3((unsigned)K, (unsigned)L, (unsigned)ng), OPEN_BWD_THREADS, ab, st)
+            hipLaunchKernelGGL(lind_batch_grad_reduce_kernel, dim3((unsigned)((LN + 15) / 16), (unsigned)ng), dim3(256), 0, s, o->d_obtg, h->K,
+                               (int)LN, o->d_obG, st);
+        }
+        HIPCHK(h, hipGetLastError());
+        out.assign(n * st.out, 0.0); flags.assign(n * st.flags, 0); stats.assign(n * st.stats, 0ull);
+        HIPCHK(h, hipMemcpyAsync(out.data(), o->d_obout, n * st.out * 8, hipMemcpyDeviceToHost, s));
+        if (G) HIPCHK(h, hipMemcpyAsync(G + (size_t)p0 * LN, o->d_obG, n * LN * 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(h, hipMemcpyAsync(flags.data(), o->d_obflags, n * st.flags * sizeof(int), hipMemcpyDeviceToHost, s));
+        HIPCHK(h, hipMemcpyAsync(stats.data(), o->d_obstats, n * st.stats * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+        HIPCHK(h, hipStreamSynchronize(s));
+        for (size_t q = 0; q < n; ++q) {
+            int rq = open_status(h, flags[q * st.flags]);
+            if (!rq) rq = open_status(h, flags[q * st.flags + 1]);
+            if (rq) {
+                h->err = "pulse set " + std::to_string((size_t)p0 + q) + ": " + h->err;
+                return rq;
+            }
+            const double *slab = out.data() + q * st.out;
+            J[(size_t)p0 + q] = functional_from_sums(h, slab + 2 * K);
+            if (tau) memcpy(tau + ((size_t)p0 + q) * 2 * K, slab, 2 * K * 8);
+            const unsigned long long *sq = stats.data() + q * st.stats;
+            for (size_t w = 0; w < K + K * L; ++w) {
+                (w < K ? terms_fw : terms_bw) += (double)sq[2 * w];
+                substeps += (double)sq[2 * w + 1];
+            }
+        }
+    }
+    o->ob_info[0] = (double)Pg; o->ob_info[1] = (double)groups; o->ob_info[2] = (double)o->ob_bytes;
+    o->ob_info[3] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    o->ob_info[4] = terms_fw; o->ob_info[5] = terms_bw; o->ob_info[6] = substeps;
+    return GRAPE_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2003,6 +2154,7 @@ int grape_create_open(grape_handle **out, const grape_problem *p, const grape_li
     if (p->prop_tolerance > 0) h->series_tol = p->prop_tolerance;
     o->J = diss->J; o->cops_per_traj = diss->cops_per_traj ? 1 : 0;
     if (const char *envh = getenv("GRAPE_HVP_DIRS")) h->hvp_dirs_env = std::max(0, atoi(envh));   // (grape_open_hvp: as grape_create)
+    if (const char *envb = getenv("GRAPE_OPEN_BATCH_SETS")) o->ob_sets_env = std::max(0, atoi(envb));   // (grape_open_eval_batch: sets per launch group)
     o->Kj = o->cops_per_traj ? p->K : 1; o->Kc = p->hc_per_traj ? p->K : 1;
 
     auto fail = [&](int code) { g_create_error = h->err; return code; };   // (the guard releases the handle)
@@ -4257,6 +4409,26 @@ int grape_get_open_hvp_info(grape_handle *h, double *out, int n) try {
     if (!h || !out || !h->open) return GRAPE_ERR_INVALID;
     const int m = std::max(0, std::min(n, 7));
     for (int i = 0; i < m; ++i) out[i] = h->open->hv_info[i];
+    return m;
+}
+GRAPE_BARRIER(h ? &h->err : &g_create_error)
+
+int grape_open_eval_batch(grape_handle *h, int P, const double *pulsevals, double *J, double *G, double *tau) try {
+    if (!h) { g_create_error = "grape_open_eval_batch: h == NULL"; return GRAPE_ERR_INVALID; }
+    if (P <= 0) OPEN_OB_REFUSE("P must be positive");
+    if (!pulsevals) OPEN_OB_REFUSE("pulsevals == NULL");
+    if (!J) OPEN_OB_REFUSE("J == NULL");
+    if (!h->open) OPEN_OB_REFUSE("not an open-system handle (grape_create_open); use grape_eval_batch for a closed one");
+    if (h->K != h->K_total) OPEN_OB_REFUSE("a split-phase shard (K < K_total) is out of scope: f of a set would need an all-reduce of its own");
+    if (h->no_target) OPEN_OB_REFUSE("this handle has no target states (grape_problem.target == NULL): J_T and chi are the caller's, per pulse vector");
+    return open_eval_batch(h, P, pulsevals, J, G, tau);
+}
+GRAPE_BARRIER(h ? &h->err : &g_create_error)
+
+int grape_get_open_batch_info(grape_handle *h, double *out, int n) try {
+    if (!h || !out || !h->open) return GRAPE_ERR_INVALID;
+    const int m = std::max(0, std::min(n, 7));
+    for (int i = 0; i < m; ++i) out[i] = h->open->ob_info[i];
     return m;
 }
 GRAPE_BARRIER(h ? &h->err : &g_create_error)

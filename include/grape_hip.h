@@ -463,6 +463,38 @@ int grape_open_hvp(grape_handle *h, int nv, const double *V, double *HV);
  * ([0] = [5] + [6]).  Returns the number of entries written (at most n); GRAPE_ERR_INVALID for a closed handle. */
 int grape_get_open_hvp_info(grape_handle *h, double *out, int n);
 
+/* P pulse vectors through the problem of one open-system handle, side by side (grape_create_open; entry points only, the
+ * ABI version stays 7; csrc/grape_lindblad_batch.hip.h).  Arguments as grape_eval_batch:
+ *   pulsevals [P][L*N_T] control-major per set;  J [P];  G NULL (forward half only) or [P][L*N_T];  tau NULL or [P][K] complex.
+ * Element p is what grape_eval(h, pulsevals + p*L*N_T, ...) returns, to rounding.  An evaluation on such a handle is a latency
+ * chain on K and K L of the 256 CUs whose time does not depend on K; here the sets are a grid axis of the kernels (forward
+ * grid (K, Pg), backward grid (K, L, Pg)), so up to floor(256 / (K L)) evaluations cost about the time of one.
+ *   - There is no route rule: P = 1 runs the same kernels.  A set's result does not depend on P, on its neighbours, on its
+ *     position or on how P is cut into launch groups, bit for bit, and two calls give the same bits.  The kernels have no
+ *     dependency between workgroups: any group size is legal, K L Pg far above the number of CUs included.
+ *   - The call owns every per-set buffer (pulses, stored states, workspaces, tau and sums, ||chi||, tau_grads, G, flags,
+ *     statistics): allocated by the first call, growing with P in launch groups under the memory budget of grape_open_hvp
+ *     (GRAPE_OPEN_BATCH_SETS=<n>, read by grape_create_open, sets the group size), freed by grape_destroy.  It shares only the
+ *     static data of the handle, the current time grid (grape_set_tlist is honoured) and the stream.  The last ordinary
+ *     evaluation stays defined across the call: grape_open_time_gradient, grape_open_hvp, grape_get_tau_grads,
+ *     grape_get_storage(0), grape_get_work, grape_get_timings and grape_get_sums return what they returned before, and a
+ *     grape_eval afterwards is bit for bit what it was.  (grape_eval_batch on an open handle stays the loop over grape_eval
+ *     it was, bit for bit, and does invalidate that state.)
+ *   - No memory for even one set: GRAPE_ERR_HIP with a message that names the size; nothing is left allocated.
+ *   - Flags are per set.  If a set raises GRAPE_ERR_TAYLOR or GRAPE_ERR_CHI_NORM the call returns the status of the lowest such
+ *     p and grape_last_error names it ("pulse set p: ..."); the outputs are unspecified, the handle stays usable.
+ *   - GRAPE_ERR_INVALID with a message that names the reason, before the first HIP call, the handle stays usable: h == NULL
+ *     (message: grape_last_error(NULL)), P <= 0, pulsevals == NULL, J == NULL; a closed handle (use grape_eval_batch); a
+ *     split-phase shard (K < K_total); a handle without targets.  A caller-supplied chi and final states per set are out of
+ *     scope. */
+int grape_open_eval_batch(grape_handle *h, int P, const double *pulsevals, double *J, double *G, double *tau);
+
+/* What the last grape_open_eval_batch of this handle did: [0] sets per launch group;  [1] number of groups;  [2] bytes of batch
+ * storage the handle holds;  [3] milliseconds of the last call (host wall time, copies included);  [4] series terms of the
+ * forward sweeps, [5] of the backward sweeps (0 after a call without G), [6] (sub-)steps, each summed over all workgroups of
+ * the call.  Returns the number of entries written (at most n); GRAPE_ERR_INVALID for a closed handle. */
+int grape_get_open_batch_info(grape_handle *h, double *out, int n);
+
 const char *grape_last_error(grape_handle *h); /* h may be NULL: error of the last failed create */
 int grape_abi_version(void);
 

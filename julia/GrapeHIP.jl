@@ -549,4 +549,43 @@ function open_hvp_info(h::Handle)
             terms_forward = Int(out[6]), terms_backward = Int(out[7]))
 end
 
+"""
+    open_eval_batch!(h, J, G, tau, pulsevals)
+
+`P = size(pulsevals, 2)` pulse vectors through the problem of a handle made by `create_open`, side by side on the GPU
+(grape_open_eval_batch): arguments as `eval_batch!`.  Column `p` is what `fg!` on that column returns, to rounding, and does not
+depend on the other columns, bit for bit.  Unlike `eval_batch!` on such a handle (one ordinary evaluation per set), the call
+owns its buffers: the handle's last ordinary evaluation stays defined (`open_time_gradient!`, `open_hvp!`, stored states).
+Multi-start, populations, line-search trial points, amplitude scans: up to `256 ÷ (K*L)` evaluations for the time of one.
+"""
+function open_eval_batch!(h::Handle, J::Vector{Float64}, G::Union{Nothing,Matrix{Float64}}, tau::Union{Nothing,Matrix{ComplexF64}},
+                          pulsevals::Matrix{Float64})
+    P = size(pulsevals, 2)
+    # (pseudo-controls would have to be appended to every column: not offered here, as in eval_batch!)
+    isempty(h.fixed) || error("GrapeHIP.open_eval_batch!: handles with pseudo-controls evaluate one pulse vector at a time (fg!)")
+    size(pulsevals, 1) == h.L * h.N_T || throw(DimensionMismatch("pulsevals must be L*N_T = $(h.L * h.N_T) × P"))
+    length(J) == P || throw(DimensionMismatch("J must have one entry per pulse vector ($P)"))
+    isnothing(G) || size(G) == size(pulsevals) || throw(DimensionMismatch("G must have the size of pulsevals"))
+    isnothing(tau) || size(tau, 2) == P || throw(DimensionMismatch("tau must be K × $P"))
+    Gp = isnothing(G) ? Ptr{Float64}(C_NULL) : pointer(G)
+    tp = isnothing(tau) ? Ptr{ComplexF64}(C_NULL) : pointer(tau)
+    check(h, GC.@preserve J G tau pulsevals ccall((:grape_open_eval_batch, libgrape), Cint,
+        (Ptr{Cvoid}, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{ComplexF64}), h.ptr, P, pulsevals, J, Gp, tp))
+    return J
+end
+
+"""
+    open_batch_info(h)
+
+What the last `open_eval_batch!` did (grape_get_open_batch_info): `sets_per_group`, `groups`, `bytes` of batch storage held by
+the handle, milliseconds of the call, series terms of the forward and of the backward sweeps and (sub-)`steps`, summed over all
+workgroups of the call.
+"""
+function open_batch_info(h::Handle)
+    out = zeros(Float64, 7)
+    GC.@preserve out ccall((:grape_get_open_batch_info, libgrape), Cint, (Ptr{Cvoid}, Ptr{Float64}, Cint), h.ptr, out, 7)
+    return (sets_per_group = Int(out[1]), groups = Int(out[2]), bytes = Int(out[3]), ms = out[4], terms_forward = Int(out[5]),
+            terms_backward = Int(out[6]), steps = Int(out[7]))
+end
+
 end # module
