@@ -19,6 +19,7 @@
 #include "grape_hvp.hip.h"
 #include "grape_lindblad_hvp.hip.h"
 #include "grape_lindblad_batch.hip.h"
+#include "grape_devmem.h"
 
 #include <rccl/rccl.h>
 #include <dlfcn.h>
@@ -194,6 +195,7 @@ struct grape_handle {
     double lambda_user = 0.0;
     unsigned long long *d_stats = nullptr;
     double *h_pin = nullptr;  // pinned staging
+    DeviceBufs mem;           // owns every buffer above and below that this handle allocated (grape_devmem.h)
     size_t h_pin_doubles = 0;
     Phase ph[kRing][kPhases]{};
     long n_fwd = 0, n_bwd = 0;  // evaluations recorded since the last grape_reset_timings
@@ -291,24 +293,24 @@ struct grape_handle {
     bool batch_ok = false;         // the handle is inside the envelope of the batched kernels (grape_create)
     int batch_env = -1;            // GRAPE_BATCH at grape_create: 0 one ordinary evaluation per set, 1 the batched kernels
                                    // wherever batch_ok, unset: the route rule of grape_eval_batch
-    int batch_sets_env = 0;        // GRAPE_BATCH_SETS at grape_create: sets per launch group (tests; 0: from the memory budget)
-    int batch_cap = 0;             // sets the batch storage holds
-    size_t batch_bytes = 0;        // ... and its size on the device
-    double *d_beps = nullptr, *d_bSf = nullptr, *d_bslab = nullptr, *d_brho = nullptr;
-    double2 *d_bU = nullptr, *d_bfw = nullptr, *d_bbw = nullptr, *d_btg = nullptr, *d_bz = nullptr;
-    unsigned long long *d_bstats = nullptr;   // work statistics of the batched kernels (one block for all sets, not reported)
-    double *h_bpin = nullptr;      // pinned staging of a launch group: pulses | result slabs
-    double batch_info[4] = {0., 0., 0., 0.};   // grape_get_batch_info
+    struct BatchStore {
+        GroupStore store;          // units: pulse sets; env: GRAPE_BATCH_SETS at grape_create
+        double *d_beps = nullptr, *d_bSf = nullptr, *d_bslab = nullptr, *d_brho = nullptr;
+        double2 *d_bU = nullptr, *d_bfw = nullptr, *d_bbw = nullptr, *d_btg = nullptr, *d_bz = nullptr;
+        unsigned long long *d_bstats = nullptr;   // work statistics of the batched kernels (one block for all sets, not reported)
+        double *h_bpin = nullptr;  // pinned staging of a launch group: pulses | result slabs
+        double info[4] = {0., 0., 0., 0.};   // grape_get_batch_info
+    } batch;
     // grape_hvp (grape_hvp.hip.h): Hessian-vector products on the stored forward states.  Its storage is
     // allocated by the first call, grows with the directions of a launch group and is freed by grape_destroy; nothing an
     // evaluation uses is touched.
-    int hvp_dirs_env = 0;          // GRAPE_HVP_DIRS at grape_create: directions per launch group (tests; 0: from the memory budget)
-    int hvp_cap = 0;               // directions the storage holds
-    size_t hvp_bytes = 0;          // ... and its size on the device
-    double *d_hvV = nullptr, *d_hvws = nullptr, *d_hvout = nullptr;
-    double2 *d_hvdpsi = nullptr, *d_hvdtau = nullptr, *d_hvdcoef = nullptr, *d_hvtg = nullptr;
-    unsigned long long *d_hvstats = nullptr;   // [4 hvp_cap K] statistics of the workgroups, then the flag word
-    double hvp_info[7] = {0., 0., 0., 0., 0., 0., 0.};   // grape_get_hvp_info
+    struct HvpStore {
+        GroupStore store;          // units: directions; env: GRAPE_HVP_DIRS at grape_create
+        double *d_hvV = nullptr, *d_hvws = nullptr, *d_hvout = nullptr;
+        double2 *d_hvdpsi = nullptr, *d_hvdtau = nullptr, *d_hvdcoef = nullptr, *d_hvtg = nullptr;
+        unsigned long long *d_hvstats = nullptr;   // [4 cap K] statistics of the workgroups, then the flag word
+        double info[7] = {0., 0., 0., 0., 0., 0., 0.};   // grape_get_hvp_info
+    } hvp;
     // grape_create_open (grape_lindblad.hip.h): the states are d x d density matrices under a Lindblad
     // generator.  Such a handle owns none of the buffers above: everything it holds hangs off this pointer, and the entry
     // points dispatch on it.
@@ -326,8 +328,29 @@ namespace {
         }                                                                                       \
     } while (0)
 
-template <typename T>
-hipError_t dmalloc(T **p, size_t n) { return hipMalloc((void **)p, n * sizeof(T)); }
+// units per launch group of a call that wants `want`, and storage for that many in g (grape_devmem.h: budget rule, growth);
+// layout(get) requests the buffers.  *grown: the storage is new.
+template <typename Layout>
+int group_reserve(grape_handle *h, GroupStore &g, int want, size_t per, double budget_cap, const char *call, const char *unit_word,
+                  const char *env_name, int *units, Layout &&layout, bool *grown = nullptr) {
+    hipError_t e = g.plan(want, per, budget_cap, units);
+    if (e != hipSuccess) { h->err = std::string("hipMemGetInfo(&free_b, &total_b): ") + hipGetErrorString(e); return GRAPE_ERR_HIP; }
+    const GroupStore::Grow r = g.grow(*units, h->stream, layout, &e);
+    if (grown) *grown = r == GroupStore::Grow::grown;
+    if (r == GroupStore::Grow::sync_failed) { h->err = std::string("hipStreamSynchronize(h->stream): ") + hipGetErrorString(e); return GRAPE_ERR_HIP; }
+    if (r == GroupStore::Grow::alloc_failed) {
+        h->err = GroupStore::oom_message(call, *units, unit_word, per, env_name);
+        (void)hipGetLastError();
+        return GRAPE_ERR_HIP;
+    }
+    return GRAPE_OK;
+}
+
+int copy_info(const double *info, int len, double *out, int n) {
+    const int m = std::max(0, std::min(n, len));
+    for (int i = 0; i < m; ++i) out[i] = info[i];
+    return m;
+}
 
 // hipFuncAttributeMaxDynamicSharedMemorySize is raised per kernel and device whenever a launch needs more than has been
 // set so far (the size depends on NP and on diagnostic padding: a cache keyed by the device alone would let a second,
@@ -1455,8 +1478,7 @@ struct OpenCtx {
     double2 *d_tg = nullptr;
     int *d_flags = nullptr;
     unsigned long long *d_stats = nullptr;
-    std::vector<void *> bufs;
-    size_t bytes = 0;
+    DeviceBufs mem;               // owns every buffer of the handle outside the two stores below
     hipEvent_t ev[2] = {nullptr, nullptr};
     double ms_fwd = 0.0, ms_bwd = 0.0;
     long n_fwd = 0, n_bwd = 0;
@@ -1476,39 +1498,36 @@ struct OpenCtx {
     // by the first call and grows with the directions of a launch group.
     enum { HV_NONE, HV_READY, HV_FAILED, HV_NEW_GRID, HV_BATCH };
     int hv_state = HV_NONE;
-    int hv_cap = 0;               // directions the storage holds
-    size_t hv_bytes = 0;
-    double *d_hvV = nullptr, *d_hvws = nullptr, *d_hvds = nullptr, *d_hvout = nullptr;
-    double2 *d_hvdtau = nullptr, *d_hvdcoef = nullptr, *d_hvtg = nullptr;
-    unsigned long long *d_hvstats = nullptr;
-    double hv_info[7] = {0., 0., 0., 0., 0., 0., 0.};   // grape_get_open_hvp_info
+    struct HvpStore {
+        GroupStore store;         // units: directions; env: GRAPE_HVP_DIRS
+        double *d_hvV = nullptr, *d_hvws = nullptr, *d_hvds = nullptr, *d_hvout = nullptr;
+        double2 *d_hvdtau = nullptr, *d_hvdcoef = nullptr, *d_hvtg = nullptr;
+        unsigned long long *d_hvstats = nullptr;
+        double info[7] = {0., 0., 0., 0., 0., 0., 0.};   // grape_get_open_hvp_info
+    } hv;
     // grape_open_eval_batch (grape_lindblad_batch.hip.h): every per-set buffer belongs to the call -- pulses, stored
     // states, workspaces, tau | sums, ||chi||, tau_grads, G, flags, statistics.  Allocated by the first call, grows with the sets
     // of a launch group.  Nothing an ordinary evaluation or a getter reads is touched, no state word changes.
-    int ob_cap = 0;               // sets the storage holds
-    int ob_sets_env = 0;          // GRAPE_OPEN_BATCH_SETS: sets per launch group (0: from the memory budget)
-    size_t ob_bytes = 0;
-    double *d_obeps = nullptr, *d_obstore = nullptr, *d_obws = nullptr, *d_obout = nullptr, *d_obrho = nullptr, *d_obG = nullptr;
-    double2 *d_obtg = nullptr;
-    int *d_obflags = nullptr;
-    unsigned long long *d_obstats = nullptr;
-    double ob_info[7] = {0., 0., 0., 0., 0., 0., 0.};   // grape_get_open_batch_info
+    struct BatchStore {
+        GroupStore store;         // units: pulse sets; env: GRAPE_OPEN_BATCH_SETS
+        double *d_obeps = nullptr, *d_obstore = nullptr, *d_obws = nullptr, *d_obout = nullptr, *d_obrho = nullptr, *d_obG = nullptr;
+        double2 *d_obtg = nullptr;
+        int *d_obflags = nullptr;
+        unsigned long long *d_obstats = nullptr;
+        double info[7] = {0., 0., 0., 0., 0., 0., 0.};   // grape_get_open_batch_info
+    } ob;
 };
 
 namespace {
 
 template <typename T>
-hipError_t open_alloc(OpenCtx *o, T **p, size_t n) {
-    const hipError_t e = hipMalloc((void **)p, std::max<size_t>(n, 1) * sizeof(T));
-    if (e == hipSuccess) { o->bufs.push_back((void *)*p); o->bytes += std::max<size_t>(n, 1) * sizeof(T); }
-    return e;
-}
+hipError_t open_alloc(OpenCtx *o, T **p, size_t n) { return o->mem.alloc(p, std::max<size_t>(n, 1)); }   // (an empty array is one element)
 
 void open_destroy(grape_handle *h) {
     OpenCtx *o = h->open;
     hipSetDevice(h->device);
     if (h->stream) hipStreamSynchronize(h->stream);
-    for (void *b : o->bufs) hipFree(b);
+    o->hv.store.release(); o->ob.store.release(); o->mem.release();
     for (hipEvent_t e : o->ev)
         if (e) hipEventDestroy(e);
     if (h->stream) hipStreamDestroy(h->stream);
@@ -1777,20 +1796,6 @@ int open_time_gradient(grape_handle *h, double *dJdt) {
 #define OPEN_HV_REFUSE(text) do { h->err = "grape_open_hvp: " text; return GRAPE_ERR_INVALID; } while (0)
 #define OPEN_HVF_THREADS(np) ((np) * (np) / 4)
 
-void open_hvp_release(OpenCtx *o) {
-    void *bufs[] = {o->d_hvV, o->d_hvws, o->d_hvds, o->d_hvout, o->d_hvdtau, o->d_hvdcoef, o->d_hvtg, o->d_hvstats};
-    for (void *b : bufs)
-        if (b) {
-            hipFree(b);
-            o->bufs.erase(std::remove(o->bufs.begin(), o->bufs.end(), b), o->bufs.end());
-        }
-    o->d_hvV = o->d_hvws = o->d_hvds = o->d_hvout = nullptr;
-    o->d_hvdtau = o->d_hvdcoef = o->d_hvtg = nullptr;
-    o->d_hvstats = nullptr;
-    o->bytes -= o->hv_bytes;
-    o->hv_cap = 0; o->hv_bytes = 0;
-}
-
 // bytes of storage one direction needs: the workspaces of its K L backward workgroups (the K forward ones fit inside),
 // rho', the per-trajectory terms, tau', c', the statistics, V and H v
 size_t open_hvp_bytes_per_direction(const grape_handle *h) {
@@ -1798,42 +1803,18 @@ size_t open_hvp_bytes_per_direction(const grape_handle *h) {
     return K * L * (16 + 4 * J) * m2 * 8 + K * (size_t)(h->N_T + 1) * m2 * 8 + K * LN * 16 + K * 32 + 2 * (K + K * L) * 8 + 2 * LN * 8;
 }
 
-// directions per launch group and storage for that many: the budget rule of hvp_reserve (half of what the device has free,
-// counting what the storage already holds, at most 8 GB; GRAPE_HVP_DIRS overrides).  The storage only grows.
+// directions per launch group (the direction is grid.z of the backward launch) and storage for that many, at most 8 GB
 int open_hvp_reserve(grape_handle *h, int nv, int *dirs) {
     OpenCtx *o = h->open;
-    const size_t per = open_hvp_bytes_per_direction(h);
-    int nd = std::min(nv, 65535);   // (the direction is grid.z of the backward launch)
-    if (h->hvp_dirs_env > 0) nd = std::min(nd, h->hvp_dirs_env);
-    else if (nd > o->hv_cap) {
-        size_t free_b = 0, total_b = 0;
-        HIPCHK(h, hipMemGetInfo(&free_b, &total_b));
-        const double budget = std::min(0.5 * ((double)free_b + (double)o->hv_bytes), 8.0 * 1073741824.0);
-        nd = (int)std::max<double>(1.0, std::min<double>((double)nd, std::floor(budget / (double)per)));
-    }
-    *dirs = nd;
-    if (nd <= o->hv_cap) return GRAPE_OK;
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    open_hvp_release(o);
-    const size_t n = (size_t)nd, K = (size_t)h->K, L = (size_t)h->L, LN = L * h->N_T, m2 = 2 * (size_t)h->NP * h->NP, J = (size_t)o->J;
-    const size_t before = o->bytes;
-    int rc = GRAPE_OK;
-    auto get = [&](auto **ptr, size_t count) {
-        if (rc == GRAPE_OK && open_alloc(o, ptr, count) != hipSuccess) {
-            h->err = "grape_open_hvp: out of device memory for the storage of " + std::to_string(nd) + " directions (" +
-                     std::to_string(per * n >> 20) + " MB); GRAPE_HVP_DIRS=<n> makes the launch groups smaller";
-            (void)hipGetLastError();
-            *ptr = nullptr;
-            rc = GRAPE_ERR_HIP;
-        }
-    };
-    get(&o->d_hvV, n * LN); get(&o->d_hvws, n * K * L * (16 + 4 * J) * m2); get(&o->d_hvds, n * K * (size_t)(h->N_T + 1) * m2);
-    get(&o->d_hvout, n * LN); get(&o->d_hvdtau, n * K); get(&o->d_hvdcoef, n * K); get(&o->d_hvtg, n * K * LN);
-    get(&o->d_hvstats, 2 * n * (K + K * L));
-    o->hv_bytes = o->bytes - before;
-    if (rc) { open_hvp_release(o); return rc; }
-    o->hv_cap = nd;
-    return GRAPE_OK;
+    const size_t K = (size_t)h->K, L = (size_t)h->L, LN = L * h->N_T, m2 = 2 * (size_t)h->NP * h->NP, J = (size_t)o->J;
+    return group_reserve(h, o->hv.store, nv, open_hvp_bytes_per_direction(h), 8.0 * 1073741824.0, "grape_open_hvp", "directions",
+                         "GRAPE_HVP_DIRS", dirs, [&](GroupStore::Requests &req) {
+        const size_t n = (size_t)*dirs;
+        auto get = [&](auto **ptr, size_t count) { req(ptr, std::max<size_t>(count, 1)); };   // (as open_alloc)
+        get(&o->hv.d_hvV, n * LN); get(&o->hv.d_hvws, n * K * L * (16 + 4 * J) * m2); get(&o->hv.d_hvds, n * K * (size_t)(h->N_T + 1) * m2);
+        get(&o->hv.d_hvout, n * LN); get(&o->hv.d_hvdtau, n * K); get(&o->hv.d_hvdcoef, n * K); get(&o->hv.d_hvtg, n * K * LN);
+        get(&o->hv.d_hvstats, 2 * n * (K + K * L));
+    });
 }
 
 // HV[j] = (d^2 J / d eps^2) V[j] at the pulses of the last forward half, from the stored rho_k(t_n), tau, f and the device copy
@@ -1862,30 +1843,30 @@ int open_hvp(grape_handle *h, int nv, const double *V, double *HV) {
     q.a = open_args(h);
     q.a.f = o->d_out + 2 * K;   // sum_k w_k tau_k as the forward half reduced it (d_f belongs to the backward half)
     q.a.ws = nullptr; q.a.tg = nullptr; q.a.stats = nullptr; q.a.rho = nullptr;
-    q.V = o->d_hvV; q.dstore = o->d_hvds; q.dtau = o->d_hvdtau; q.dcoef = o->d_hvdcoef; q.tg = o->d_hvtg; q.ws = o->d_hvws;
-    q.stats = o->d_hvstats;
+    q.V = o->hv.d_hvV; q.dstore = o->hv.d_hvds; q.dtau = o->hv.d_hvdtau; q.dcoef = o->hv.d_hvdcoef; q.tg = o->hv.d_hvtg; q.ws = o->hv.d_hvws;
+    q.stats = o->hv.d_hvstats;
     std::vector<unsigned long long> st;
     double terms_fw = 0., terms_bw = 0., substeps = 0.;
     for (int j0 = 0; j0 < nv; j0 += nd) {
         const int ng = std::min(nd, nv - j0);
         const size_t nst = 2 * (size_t)ng * (K + K * L);
         q.nd = ng;
-        HIPCHK(h, hipMemcpyAsync(o->d_hvV, V + (size_t)j0 * LN, (size_t)ng * LN * 8, hipMemcpyHostToDevice, s));
+        HIPCHK(h, hipMemcpyAsync(o->hv.d_hvV, V + (size_t)j0 * LN, (size_t)ng * LN * 8, hipMemcpyHostToDevice, s));
         HIPCHK(h, hipMemsetAsync(o->d_flags, 0, 8 * sizeof(int), s));
-        HIPCHK(h, hipMemsetAsync(o->d_hvstats, 0, nst * sizeof(unsigned long long), s));
+        HIPCHK(h, hipMemsetAsync(o->hv.d_hvstats, 0, nst * sizeof(unsigned long long), s));
         OPEN_LAUNCH(lind_hvp_forward_kernel, dim3((unsigned)K, (unsigned)ng), OPEN_HVF_THREADS, q)
         hipLaunchKernelGGL(lind_hvp_boundary_kernel, dim3((unsigned)ng), dim3(64), 0, s, q);
         OPEN_LAUNCH(lind_hvp_backward_kernel, dim3((unsigned)K, (unsigned)L, (unsigned)ng), OPEN_BWD_THREADS, q)
         HIPCHK(h, hipGetLastError());
         // (H v)_j = -2 Re sum_k of the per-trajectory terms: the gradient's reduction, fixed order
         for (int j = 0; j < ng; ++j)
-            hipLaunchKernelGGL(grad_reduce_kernel, dim3((unsigned)((LN + 15) / 16)), dim3(256), 0, s, o->d_hvtg + (size_t)j * K * LN, h->K,
-                               (int)LN, o->d_hvout + (size_t)j * LN, (const double2 *)nullptr);
+            hipLaunchKernelGGL(grad_reduce_kernel, dim3((unsigned)((LN + 15) / 16)), dim3(256), 0, s, o->hv.d_hvtg + (size_t)j * K * LN, h->K,
+                               (int)LN, o->hv.d_hvout + (size_t)j * LN, (const double2 *)nullptr);
         HIPCHK(h, hipGetLastError());
         int flags[8] = {0};
         st.assign(nst, 0ull);
-        HIPCHK(h, hipMemcpyAsync(HV + (size_t)j0 * LN, o->d_hvout, (size_t)ng * LN * 8, hipMemcpyDeviceToHost, s));
-        HIPCHK(h, hipMemcpyAsync(st.data(), o->d_hvstats, nst * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+        HIPCHK(h, hipMemcpyAsync(HV + (size_t)j0 * LN, o->hv.d_hvout, (size_t)ng * LN * 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(h, hipMemcpyAsync(st.data(), o->hv.d_hvstats, nst * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
         HIPCHK(h, hipMemcpyAsync(flags, o->d_flags, sizeof(flags), hipMemcpyDeviceToHost, s));
         HIPCHK(h, hipStreamSynchronize(s));
         for (size_t w = 0; w < nst / 2; ++w) {
@@ -1897,28 +1878,13 @@ int open_hvp(grape_handle *h, int nv, const double *V, double *HV) {
             return GRAPE_ERR_TAYLOR;
         }
     }
-    o->hv_info[0] = terms_fw + terms_bw; o->hv_info[1] = substeps; o->hv_info[2] = (double)nd; o->hv_info[3] = (double)o->hv_bytes;
-    o->hv_info[4] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    o->hv_info[5] = terms_fw; o->hv_info[6] = terms_bw;
+    o->hv.info[0] = terms_fw + terms_bw; o->hv.info[1] = substeps; o->hv.info[2] = (double)nd; o->hv.info[3] = (double)o->hv.store.mem.bytes();
+    o->hv.info[4] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    o->hv.info[5] = terms_fw; o->hv.info[6] = terms_bw;
     return GRAPE_OK;
 }
 
 #define OPEN_OB_REFUSE(text) do { h->err = "grape_open_eval_batch: " text; return GRAPE_ERR_INVALID; } while (0)
-
-void open_batch_release(OpenCtx *o) {
-    void *bufs[] = {o->d_obeps, o->d_obstore, o->d_obws, o->d_obout, o->d_obrho, o->d_obG, o->d_obtg, o->d_obflags, o->d_obstats};
-    for (void *b : bufs)
-        if (b) {
-            hipFree(b);
-            o->bufs.erase(std::remove(o->bufs.begin(), o->bufs.end(), b), o->bufs.end());
-        }
-    o->d_obeps = o->d_obstore = o->d_obws = o->d_obout = o->d_obrho = o->d_obG = nullptr;
-    o->d_obtg = nullptr;
-    o->d_obflags = nullptr;
-    o->d_obstats = nullptr;
-    o->bytes -= o->ob_bytes;
-    o->ob_cap = 0; o->ob_bytes = 0;
-}
 
 LindBatchStrides open_batch_strides(const grape_handle *h) {
     const size_t K = (size_t)h->K, L = (size_t)h->L, LN = L * h->N_T, m2 = 2 * (size_t)h->NP * h->NP, J = (size_t)h->open->J;
@@ -1934,42 +1900,17 @@ size_t open_batch_bytes_per_set(const LindBatchStrides &st) {
     return (2 * st.eps + st.store + st.ws + st.out + st.k) * 8 + st.tg * 16 + st.flags * sizeof(int) + st.stats * sizeof(unsigned long long);
 }
 
-// sets per launch group for a call with P sets, and storage for that many: the budget rule of open_hvp_reserve (half of what
-// the device has free, counting what the storage already holds, at most 8 GB; GRAPE_OPEN_BATCH_SETS overrides).  The storage
-// only grows.
+// sets per launch group (the set is grid.y / grid.z of the launches) and storage for that many, at most 8 GB
 int open_batch_reserve(grape_handle *h, int P, const LindBatchStrides &st, int *sets) {
     OpenCtx *o = h->open;
-    const size_t per = open_batch_bytes_per_set(st);
-    int ns = std::min(P, 65535);   // (the set is grid.y / grid.z of the launches)
-    if (o->ob_sets_env > 0) ns = std::min(ns, o->ob_sets_env);
-    else if (ns > o->ob_cap) {
-        size_t free_b = 0, total_b = 0;
-        HIPCHK(h, hipMemGetInfo(&free_b, &total_b));
-        const double budget = std::min(0.5 * ((double)free_b + (double)o->ob_bytes), 8.0 * 1073741824.0);
-        ns = (int)std::max<double>(1.0, std::min<double>((double)ns, std::floor(budget / (double)per)));
-    }
-    *sets = ns;
-    if (ns <= o->ob_cap) return GRAPE_OK;
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    open_batch_release(o);
-    const size_t n = (size_t)ns, before = o->bytes;
-    int rc = GRAPE_OK;
-    auto get = [&](auto **ptr, size_t count) {
-        if (rc == GRAPE_OK && open_alloc(o, ptr, count) != hipSuccess) {
-            h->err = "grape_open_eval_batch: out of device memory for the storage of " + std::to_string(ns) + " pulse sets (" +
-                     std::to_string(per * n >> 20) + " MB); GRAPE_OPEN_BATCH_SETS=<n> makes the launch groups smaller";
-            (void)hipGetLastError();
-            *ptr = nullptr;
-            rc = GRAPE_ERR_HIP;
-        }
-    };
-    get(&o->d_obeps, n * st.eps); get(&o->d_obstore, n * st.store); get(&o->d_obws, n * st.ws); get(&o->d_obout, n * st.out);
-    get(&o->d_obrho, n * st.k); get(&o->d_obG, n * st.eps); get(&o->d_obtg, n * st.tg); get(&o->d_obflags, n * st.flags);
-    get(&o->d_obstats, n * st.stats);
-    o->ob_bytes = o->bytes - before;
-    if (rc) { open_batch_release(o); return rc; }
-    o->ob_cap = ns;
-    return GRAPE_OK;
+    return group_reserve(h, o->ob.store, P, open_batch_bytes_per_set(st), 8.0 * 1073741824.0, "grape_open_eval_batch", "pulse sets",
+                         "GRAPE_OPEN_BATCH_SETS", sets, [&](GroupStore::Requests &req) {
+        const size_t n = (size_t)*sets;
+        auto get = [&](auto **ptr, size_t count) { req(ptr, std::max<size_t>(count, 1)); };   // (as open_alloc)
+        get(&o->ob.d_obeps, n * st.eps); get(&o->ob.d_obstore, n * st.store); get(&o->ob.d_obws, n * st.ws); get(&o->ob.d_obout, n * st.out);
+        get(&o->ob.d_obrho, n * st.k); get(&o->ob.d_obG, n * st.eps); get(&o->ob.d_obtg, n * st.tg); get(&o->ob.d_obflags, n * st.flags);
+        get(&o->ob.d_obstats, n * st.stats);
+    });
 }
 
 // P evaluations side by side: forward grid (K, Pg), backward grid (K, L, Pg), the reductions segmented over the sets
@@ -1988,12 +1929,12 @@ int open_eval_batch(grape_handle *h, int P, const double *pulsevals, double *J, 
     const size_t K = (size_t)h->K, L = (size_t)h->L, LN = L * h->N_T;
     hipStream_t s = h->stream;
     LindArgs a = open_args(h);
-    a.eps = o->d_obeps; a.store = o->d_obstore; a.ws = o->d_obws; a.tau = (double2 *)o->d_obout; a.f = nullptr; a.rho = o->d_obrho;
-    a.tg = o->d_obtg; a.flags = o->d_obflags; a.stats = o->d_obstats; a.chi_in = nullptr;
+    a.eps = o->ob.d_obeps; a.store = o->ob.d_obstore; a.ws = o->ob.d_obws; a.tau = (double2 *)o->ob.d_obout; a.f = nullptr; a.rho = o->ob.d_obrho;
+    a.tg = o->ob.d_obtg; a.flags = o->ob.d_obflags; a.stats = o->ob.d_obstats; a.chi_in = nullptr;
     // word [0] of a set's flags belongs to its forward sweep, word [1] to its backward sweep: a set whose forward half failed
     // reports that, as grape_eval does, whatever its backward half then made of the states
     LindArgs ab = a;
-    ab.flags = o->d_obflags + 1;
+    ab.flags = o->ob.d_obflags + 1;
     std::vector<double> out;
     std::vector<int> flags;
     std::vector<unsigned long long> stats;
@@ -2002,22 +1943,22 @@ int open_eval_batch(grape_handle *h, int P, const double *pulsevals, double *J, 
     for (int p0 = 0; p0 < P; p0 += Pg, ++groups) {
         const int ng = std::min(Pg, P - p0);
         const size_t n = (size_t)ng;
-        HIPCHK(h, hipMemcpyAsync(o->d_obeps, pulsevals + (size_t)p0 * LN, n * LN * 8, hipMemcpyHostToDevice, s));
-        HIPCHK(h, hipMemsetAsync(o->d_obflags, 0, n * st.flags * sizeof(int), s));
-        HIPCHK(h, hipMemsetAsync(o->d_obstats, 0, n * st.stats * sizeof(unsigned long long), s));
+        HIPCHK(h, hipMemcpyAsync(o->ob.d_obeps, pulsevals + (size_t)p0 * LN, n * LN * 8, hipMemcpyHostToDevice, s));
+        HIPCHK(h, hipMemsetAsync(o->ob.d_obflags, 0, n * st.flags * sizeof(int), s));
+        HIPCHK(h, hipMemsetAsync(o->ob.d_obstats, 0, n * st.stats * sizeof(unsigned long long), s));
         OPEN_LAUNCH(lind_batch_forward_kernel, dim3((unsigned)K, (unsigned)ng), OPEN_FWD_THREADS, a, st)
-        hipLaunchKernelGGL(lind_batch_tau_reduce_kernel, dim3(1, (unsigned)ng), dim3(64), 0, s, o->d_obout, (const double *)o->d_weights, h->K, st);
+        hipLaunchKernelGGL(lind_batch_tau_reduce_kernel, dim3(1, (unsigned)ng), dim3(64), 0, s, o->ob.d_obout, (const double *)o->d_weights, h->K, st);
         if (G) {   // f of every set is on the device, where its reduction left it
             OPEN_LAUNCH(lind_batch_backward_kernel, dim3((unsigned)K, (unsigned)L, (unsigned)ng), OPEN_BWD_THREADS, ab, st)
-            hipLaunchKernelGGL(lind_batch_grad_reduce_kernel, dim3((unsigned)((LN + 15) / 16), (unsigned)ng), dim3(256), 0, s, o->d_obtg, h->K,
-                               (int)LN, o->d_obG, st);
+            hipLaunchKernelGGL(lind_batch_grad_reduce_kernel, dim3((unsigned)((LN + 15) / 16), (unsigned)ng), dim3(256), 0, s, o->ob.d_obtg, h->K,
+                               (int)LN, o->ob.d_obG, st);
         }
         HIPCHK(h, hipGetLastError());
         out.assign(n * st.out, 0.0); flags.assign(n * st.flags, 0); stats.assign(n * st.stats, 0ull);
-        HIPCHK(h, hipMemcpyAsync(out.data(), o->d_obout, n * st.out * 8, hipMemcpyDeviceToHost, s));
-        if (G) HIPCHK(h, hipMemcpyAsync(G + (size_t)p0 * LN, o->d_obG, n * LN * 8, hipMemcpyDeviceToHost, s));
-        HIPCHK(h, hipMemcpyAsync(flags.data(), o->d_obflags, n * st.flags * sizeof(int), hipMemcpyDeviceToHost, s));
-        HIPCHK(h, hipMemcpyAsync(stats.data(), o->d_obstats, n * st.stats * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+        HIPCHK(h, hipMemcpyAsync(out.data(), o->ob.d_obout, n * st.out * 8, hipMemcpyDeviceToHost, s));
+        if (G) HIPCHK(h, hipMemcpyAsync(G + (size_t)p0 * LN, o->ob.d_obG, n * LN * 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(h, hipMemcpyAsync(flags.data(), o->ob.d_obflags, n * st.flags * sizeof(int), hipMemcpyDeviceToHost, s));
+        HIPCHK(h, hipMemcpyAsync(stats.data(), o->ob.d_obstats, n * st.stats * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
         HIPCHK(h, hipStreamSynchronize(s));
         for (size_t q = 0; q < n; ++q) {
             int rq = open_status(h, flags[q * st.flags]);
@@ -2036,9 +1977,9 @@ int open_eval_batch(grape_handle *h, int P, const double *pulsevals, double *J, 
             }
         }
     }
-    o->ob_info[0] = (double)Pg; o->ob_info[1] = (double)groups; o->ob_info[2] = (double)o->ob_bytes;
-    o->ob_info[3] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    o->ob_info[4] = terms_fw; o->ob_info[5] = terms_bw; o->ob_info[6] = substeps;
+    o->ob.info[0] = (double)Pg; o->ob.info[1] = (double)groups; o->ob.info[2] = (double)o->ob.store.mem.bytes();
+    o->ob.info[3] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    o->ob.info[4] = terms_fw; o->ob.info[5] = terms_bw; o->ob.info[6] = substeps;
     return GRAPE_OK;
 }
 
@@ -2071,23 +2012,7 @@ void grape_destroy(grape_handle *h) {
     }
     hipSetDevice(h->device);
     if (h->stream) hipStreamSynchronize(h->stream);
-    for (double *b : h->d_lg)
-        if (b) hipFree(b);
-    void *bufs[] = {h->d_celldeg, h->d_xcc_sw, h->d_scanF, h->d_scan_fw, h->d_scan_bw, h->d_dte, h->d_normpart, h->d_xch, h->d_xcc, h->d_batchflag, h->d_chi_in, h->d_n1, h->d_gpark, h->d_morder, h->d_inv_tnorm, h->d_ones, h->d_z, h->d_rb, h->d_cls, h->d_rep, h->d_Dt, h->d_xi, h->d_wq, h->d_gb, h->d_cellflag, h->d_celllist, h->d_gram, h->d_Sf, h->d_dinv, h->d_scell, h->d_colpart, h->d_wgtab, h->d_prog, h->d_splan, h->d_xinit, h->d_H0p, h->d_Hcp, h->d_vecs, h->d_H0q, h->d_Hcq, h->d_H0q3, h->d_Hcq3, h->d_park2, h->d_park3, h->d_H0f, h->d_Hcf, h->d_H0t, h->d_Hct, h->d_dts, h->d_shape, h->d_weights, h->d_psi0,
-                    h->d_target, h->d_eps, h->d_U, h->d_fw, h->d_bw, h->d_tg, h->d_ret, h->d_f,
-                    h->d_rho, h->d_tq, h->d_dJdt};
-    for (void *b : bufs)
-        if (b) hipFree(b);
-    if (h->d_H0p3 && h->d_H0p3 != h->d_H0q3) hipFree(h->d_H0p3);   // (Hermitian operators: the adjoint arrays ARE the plain ones)
-    if (h->d_Hcp3 && h->d_Hcp3 != h->d_Hcq3) hipFree(h->d_Hcp3);
-    if (h->h_pin) hipHostFree(h->h_pin);
-    void *bbufs[] = {h->d_beps, h->d_bSf, h->d_bslab, h->d_brho, h->d_bU, h->d_bfw, h->d_bbw, h->d_btg, h->d_bz, h->d_bstats};
-    for (void *b : bbufs)
-        if (b) hipFree(b);
-    if (h->h_bpin) hipHostFree(h->h_bpin);
-    void *hbufs[] = {h->d_hvV, h->d_hvws, h->d_hvout, h->d_hvdpsi, h->d_hvdtau, h->d_hvdcoef, h->d_hvtg, h->d_hvstats};
-    for (void *b : hbufs)
-        if (b) hipFree(b);
+    h->batch.store.release(); h->hvp.store.release(); h->mem.release();
     for (auto &ring : h->ph)
         for (auto &p : ring) {
             if (p.e0) hipEventDestroy(p.e0);
@@ -2153,8 +2078,8 @@ int grape_create_open(grape_handle **out, const grape_problem *p, const grape_li
     if (p->chi_min_norm > 0) h->chi_min_norm = p->chi_min_norm;
     if (p->prop_tolerance > 0) h->series_tol = p->prop_tolerance;
     o->J = diss->J; o->cops_per_traj = diss->cops_per_traj ? 1 : 0;
-    if (const char *envh = getenv("GRAPE_HVP_DIRS")) h->hvp_dirs_env = std::max(0, atoi(envh));   // (grape_open_hvp: as grape_create)
-    if (const char *envb = getenv("GRAPE_OPEN_BATCH_SETS")) o->ob_sets_env = std::max(0, atoi(envb));   // (grape_open_eval_batch: sets per launch group)
+    if (const char *envh = getenv("GRAPE_HVP_DIRS")) o->hv.store.env = std::max(0, atoi(envh));   // (grape_open_hvp: as grape_create)
+    if (const char *envb = getenv("GRAPE_OPEN_BATCH_SETS")) o->ob.store.env = std::max(0, atoi(envb));   // (grape_open_eval_batch: sets per launch group)
     o->Kj = o->cops_per_traj ? p->K : 1; o->Kc = p->hc_per_traj ? p->K : 1;
 
     auto fail = [&](int code) { g_create_error = h->err; return code; };   // (the guard releases the handle)
@@ -2453,8 +2378,8 @@ int grape_create(grape_handle **out, const grape_problem *p) try {
             h->deriv_stream_never = envs && atoi(envs) == 0;
         }
         if (h->KC < p->K) {
-            if (hipSetDevice(h->device) != hipSuccess || hipMalloc((void **)&h->d_cls, p->K * sizeof(int)) != hipSuccess ||
-                hipMalloc((void **)&h->d_rep, h->KC * sizeof(int)) != hipSuccess ||
+            if (hipSetDevice(h->device) != hipSuccess || h->mem.alloc(&h->d_cls, (size_t)p->K) != hipSuccess ||
+                h->mem.alloc(&h->d_rep, (size_t)h->KC) != hipSuccess ||
                 hipMemcpy(h->d_cls, h->cls.data(), p->K * sizeof(int), hipMemcpyHostToDevice) != hipSuccess ||
                 hipMemcpy(h->d_rep, rep.data(), h->KC * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) {
                 h->err = "generator class tables: HIP allocation/copy failed";
@@ -2502,7 +2427,7 @@ int grape_create(grape_handle **out, const grape_problem *p) try {
                 t[(size_t)k * 2 * pp + (size_t)j * NP + i] = re;
                 t[(size_t)k * 2 * pp + pp + (size_t)j * NP + i] = im;
             }
-    CCHK(dmalloc(&h->d_H0f, f.size())); CCHK(dmalloc(&h->d_H0t, t.size()));
+    CCHK(h->mem.alloc(&h->d_H0f, f.size())); CCHK(h->mem.alloc(&h->d_H0t, t.size()));
     CCHK(hipMemcpy(h->d_H0f, f.data(), f.size() * 8, hipMemcpyHostToDevice));
     CCHK(hipMemcpy(h->d_H0t, t.data(), t.size() * 8, hipMemcpyHostToDevice));
     f.assign((size_t)Kc * L * 2 * pp, 0.0); t.assign((size_t)Kc * L * 2 * pp, 0.0);
@@ -2516,7 +2441,7 @@ int grape_create(grape_handle **out, const grape_problem *p) try {
                 t[(size_t)kl * 2 * pp + (size_t)j * NP + i] = re;
                 t[(size_t)kl * 2 * pp + pp + (size_t)j * NP + i] = im;
             }
-    CCHK(dmalloc(&h->d_Hcf, f.size())); CCHK(dmalloc(&h->d_Hct, t.size()));
+    CCHK(h->mem.alloc(&h->d_Hcf, f.size())); CCHK(h->mem.alloc(&h->d_Hct, t.size()));
     CCHK(hipMemcpy(h->d_Hcf, f.data(), f.size() * 8, hipMemcpyHostToDevice));
     CCHK(hipMemcpy(h->d_Hct, t.data(), t.size() * 8, hipMemcpyHostToDevice));
 
@@ -2542,10 +2467,10 @@ int grape_create(grape_handle **out, const grape_problem *p) try {
         };
         std::vector<double> pk;
         pack(p->H0, K, pk);
-        CCHK(dmalloc(&h->d_H0p, pk.size()));
+        CCHK(h->mem.alloc(&h->d_H0p, pk.size()));
         CCHK(hipMemcpy(h->d_H0p, pk.data(), pk.size() * 8, hipMemcpyHostToDevice));
         pack(p->Hc, Kc * L, pk);
-        CCHK(dmalloc(&h->d_Hcp, pk.size()));
+        CCHK(h->mem.alloc(&h->d_Hcp, pk.size()));
         CCHK(hipMemcpy(h->d_Hcp, pk.data(), pk.size() * 8, hipMemcpyHostToDevice));
         const long nbatch = (long)K * ((N_T + 15) / 16);
         // one workgroup per CU walks its batches for the fused sizes (measured at C3: 6.75 ms with 256 workgroups, 6.83
@@ -2558,10 +2483,10 @@ int grape_create(grape_handle **out, const grape_problem *p) try {
             h->deriv2 = !(env && atoi(env) == 0) || (h->large && (L > 4 || NP > 256));
             if (h->deriv2) {
                 pack(p->H0, K, pk, false);
-                CCHK(dmalloc(&h->d_H0q, pk.size()));
+                CCHK(h->mem.alloc(&h->d_H0q, pk.size()));
                 CCHK(hipMemcpy(h->d_H0q, pk.data(), pk.size() * 8, hipMemcpyHostToDevice));
                 pack(p->Hc, Kc * L, pk, false);
-                CCHK(dmalloc(&h->d_Hcq, pk.size()));
+                CCHK(h->mem.alloc(&h->d_Hcq, pk.size()));
                 CCHK(hipMemcpy(h->d_Hcq, pk.data(), pk.size() * 8, hipMemcpyHostToDevice));
                 h->deriv2_maxm = 64;
                 // blocked path: the assembly derivative kernel (asm/gen_d4.py; GRAPE_DERIV4=0: deriv2_kernel, its twin) walks the
@@ -2589,23 +2514,23 @@ int grape_create(grape_handle **out, const grape_problem *p) try {
                     };
                     std::vector<double> pk3;
                     pack3(p->H0, K, pk3, false);
-                    CCHK(dmalloc(&h->d_H0q3, pk3.size()));
+                    CCHK(h->mem.alloc(&h->d_H0q3, pk3.size()));
                     CCHK(hipMemcpy(h->d_H0q3, pk3.data(), pk3.size() * 8, hipMemcpyHostToDevice));
                     pack3(p->Hc, Kc * L, pk3, false);
-                    CCHK(dmalloc(&h->d_Hcq3, pk3.size()));
+                    CCHK(h->mem.alloc(&h->d_Hcq3, pk3.size()));
                     CCHK(hipMemcpy(h->d_Hcq3, pk3.data(), pk3.size() * 8, hipMemcpyHostToDevice));
                     if (h->herm) {   // H^dagger = H: one set of arrays
                         h->d_H0p3 = h->d_H0q3; h->d_Hcp3 = h->d_Hcq3;
                     } else {
                         pack3(p->H0, K, pk3, true);
-                        CCHK(dmalloc(&h->d_H0p3, pk3.size()));
+                        CCHK(h->mem.alloc(&h->d_H0p3, pk3.size()));
                         CCHK(hipMemcpy(h->d_H0p3, pk3.data(), pk3.size() * 8, hipMemcpyHostToDevice));
                         pack3(p->Hc, Kc * L, pk3, true);
-                        CCHK(dmalloc(&h->d_Hcp3, pk3.size()));
+                        CCHK(h->mem.alloc(&h->d_Hcp3, pk3.size()));
                         CCHK(hipMemcpy(h->d_Hcp3, pk3.data(), pk3.size() * 8, hipMemcpyHostToDevice));
                     }
                 }
-                CCHK(dmalloc(&h->d_park2, std::max((size_t)h->deriv_blocks * h->deriv2_maxm, (size_t)h->deriv4_blocks * (h->deriv2_maxm + 1)) * 2 * NP * 16));
+                CCHK(h->mem.alloc(&h->d_park2, std::max((size_t)h->deriv_blocks * h->deriv2_maxm, (size_t)h->deriv4_blocks * (h->deriv2_maxm + 1)) * 2 * NP * 16));
                 const char *env3 = getenv("GRAPE_DERIV3");
                 // round 6: FEW batches (few trajectories): one wave per batch leaves the chip idle for a whole batch latency
                 // (0.41 / 0.65 ms at NP = 48 / 64) while a workgroup per batch (deriv2_kernel) takes 0.17 / 0.21 ms per round of
@@ -2631,11 +2556,11 @@ int grape_create(grape_handle **out, const grape_problem *p) try {
                     const int bpk = (N_T + 15) / 16;
                     h->deriv3_wpt = (int)std::max<long>(1, std::min<long>((bpk + 3) / 4, h->num_cus / std::max(1, K)));
                     h->deriv3_blocks = (int)std::min<long>(h->num_cus, (long)K * h->deriv3_wpt);
-                    CCHK(dmalloc(&h->d_park3, (size_t)h->deriv3_blocks * 4 * (h->deriv2_maxm + 1) * 2 * NP * 16));   // (+ 1: the assembly kernel parks every order it forms)
+                    CCHK(h->mem.alloc(&h->d_park3, (size_t)h->deriv3_blocks * 4 * (h->deriv2_maxm + 1) * 2 * NP * 16));   // (+ 1: the assembly kernel parks every order it forms)
                 }
             }
         }
-        CCHK(dmalloc(&h->d_vecs, (size_t)h->deriv_blocks * 2 * (1 + 8) * 2 * NP * 16));
+        CCHK(h->mem.alloc(&h->d_vecs, (size_t)h->deriv_blocks * 2 * (1 + 8) * 2 * NP * 16));
     }
     if (NP < 48 && h->herm && deriv3_fits(h->NT, L)) {   // one wave per batch also at one and two tiles per side (grape_deriv3.hip.h); the matrix-free
                                           // mode as well: at these sizes the derivative kernel never used the parked forward terms
@@ -2652,7 +2577,7 @@ int grape_create(grape_handle **out, const grape_problem *p) try {
             h->deriv2_maxm = 64;
             h->deriv3_wpt = (int)std::max<long>(1, std::min<long>((bpk + 3) / 4, h->num_cus / std::max(1, K)));
             h->deriv3_blocks = (int)std::min<long>(h->num_cus, (long)K * h->deriv3_wpt);
-            CCHK(dmalloc(&h->d_park3, (size_t)h->deriv3_blocks * 4 * (h->deriv2_maxm + 1) * 2 * NP * 16));   // (+ 1: the assembly kernel parks every order it forms)
+            CCHK(h->mem.alloc(&h->d_park3, (size_t)h->deriv3_blocks * 4 * (h->deriv2_maxm + 1) * 2 * NP * 16));   // (+ 1: the assembly kernel parks every order it forms)
         }
     }
     if (h->large && !h->series) {
@@ -2663,32 +2588,32 @@ int grape_create(grape_handle **out, const grape_problem *p) try {
         const long cap = std::max<long>(1, (long)(6.0e9 / (9.0 * 2.0 * pp * 8.0)));
         h->chunk = (int)std::min<long>(ncell, std::min<long>(cap, 16384));
         if (const char *envc = getenv("GRAPE_LG_CHUNK")) h->chunk = (int)std::max<long>(1, std::min<long>(h->chunk, atol(envc)));   // (experiments: working set against the Infinity Cache)
-        for (auto &b : h->d_lg) CCHK(dmalloc(&b, (size_t)h->chunk * 2 * pp));
-        CCHK(dmalloc(&h->d_dinv, (size_t)h->chunk * 2 * 4096));
-        CCHK(dmalloc(&h->d_scell, (size_t)h->chunk + 1));
-        if (h->t18) CCHK(dmalloc(&h->d_colpart, (size_t)h->chunk * 2 * LG_PARTS * NP));
+        for (auto &b : h->d_lg) CCHK(h->mem.alloc(&b, (size_t)h->chunk * 2 * pp));
+        CCHK(h->mem.alloc(&h->d_dinv, (size_t)h->chunk * 2 * 4096));
+        CCHK(h->mem.alloc(&h->d_scell, (size_t)h->chunk + 1));
+        if (h->t18) CCHK(h->mem.alloc(&h->d_colpart, (size_t)h->chunk * 2 * LG_PARTS * NP));
         h->lg_form2 = h->t18 && !p->hc_per_traj && L <= 4 && NP % LG_FORM_ROWS == 0;
-        if (h->lg_form2) CCHK(dmalloc(&h->d_normpart, (size_t)h->chunk * (NP / LG_FORM_ROWS) * NP));
+        if (h->lg_form2) CCHK(h->mem.alloc(&h->d_normpart, (size_t)h->chunk * (NP / LG_FORM_ROWS) * NP));
         // summed controls of every time step for the generator formation (polynomial route, shared control operators):
         // N_T 2 NP^2 doubles -- 2.1 GB at C5 -- when that is a small part of what the propagators take anyway
         const double sn_bytes = (double)N_T * 2.0 * (double)pp * 8.0;
         if (!h->lg_form2 && h->t18 && !p->hc_per_traj && sn_bytes <= 0.25 * (double)h->KC * N_T * (double)pp * 16.0 + 1e9)
-            CCHK(dmalloc(&h->d_Sf, (size_t)N_T * 2 * pp));
+            CCHK(h->mem.alloc(&h->d_Sf, (size_t)N_T * 2 * pp));
     }
 
     std::vector<double> dts(N_T);
     for (int n = 0; n < N_T; ++n) dts[n] = p->tlist[n + 1] - p->tlist[n];
-    CCHK(dmalloc(&h->d_dts, (size_t)N_T));
+    CCHK(h->mem.alloc(&h->d_dts, (size_t)N_T));
     CCHK(hipMemcpy(h->d_dts, dts.data(), (size_t)N_T * 8, hipMemcpyHostToDevice));
     if (p->shape) {
-        CCHK(dmalloc(&h->d_shape, (size_t)L * N_T));
+        CCHK(h->mem.alloc(&h->d_shape, (size_t)L * N_T));
         CCHK(hipMemcpy(h->d_shape, p->shape, (size_t)L * N_T * 8, hipMemcpyHostToDevice));
     }
     if (p->weights) {
-        CCHK(dmalloc(&h->d_weights, (size_t)K));
+        CCHK(h->mem.alloc(&h->d_weights, (size_t)K));
         CCHK(hipMemcpy(h->d_weights, p->weights, (size_t)K * 8, hipMemcpyHostToDevice));
     }
-    CCHK(dmalloc(&h->d_psi0, (size_t)K * N)); CCHK(dmalloc(&h->d_target, (size_t)K * N));
+    CCHK(h->mem.alloc(&h->d_psi0, (size_t)K * N)); CCHK(h->mem.alloc(&h->d_target, (size_t)K * N));
     CCHK(hipMemcpy(h->d_psi0, p->psi0, (size_t)K * N * 16, hipMemcpyHostToDevice));
     CCHK(hipMemcpy(h->d_target, p->target, (size_t)K * N * 16, hipMemcpyHostToDevice));
     {   // concurrent sweeps (see SweepArgs::unit_chi)
@@ -2702,14 +2627,14 @@ int grape_create(grape_handle **out, const grape_problem *p) try {
             itn[k] = n2 > 0.0 ? 1.0 / std::sqrt(n2) : 0.0;
             if (!(n2 > 0.0)) h->fuse = false;   // a zero target has no direction: the sequential path reports the chi norm
         }
-        CCHK(dmalloc(&h->d_inv_tnorm, (size_t)K)); CCHK(dmalloc(&h->d_ones, (size_t)K)); CCHK(dmalloc(&h->d_z, (size_t)K));
+        CCHK(h->mem.alloc(&h->d_inv_tnorm, (size_t)K)); CCHK(h->mem.alloc(&h->d_ones, (size_t)K)); CCHK(h->mem.alloc(&h->d_z, (size_t)K));
         CCHK(hipMemcpy(h->d_inv_tnorm, itn.data(), (size_t)K * 8, hipMemcpyHostToDevice));
         CCHK(hipMemcpy(h->d_ones, ones.data(), (size_t)K * 8, hipMemcpyHostToDevice));
     }
 
     // ---- per-evaluation buffers ----
-    CCHK(dmalloc(&h->d_eps, (size_t)L * N_T));
-    if (!h->series) CCHK(dmalloc(&h->d_U, (size_t)h->KC * N_T * pp));
+    CCHK(h->mem.alloc(&h->d_eps, (size_t)L * N_T));
+    if (!h->series) CCHK(h->mem.alloc(&h->d_U, (size_t)h->KC * N_T * pp));
     if (!h->series && !h->large) {
         // 1-norms (max column sum; the input is column-major) for the order-13 certificate of expm_single
         const char *env = getenv("GRAPE_NORM_BOUND");
@@ -2726,7 +2651,7 @@ int grape_create(grape_handle **out, const grape_problem *p) try {
             };
             for (int k = 0; k < K; ++k) n1[k] = norm1(p->H0 + 2 * (size_t)k * nn);
             for (int kl = 0; kl < Kc * L; ++kl) n1[K + kl] = norm1(p->Hc + 2 * (size_t)kl * nn);
-            CCHK(dmalloc(&h->d_n1, n1.size()));
+            CCHK(h->mem.alloc(&h->d_n1, n1.size()));
             CCHK(hipMemcpy(h->d_n1, n1.data(), n1.size() * 8, hipMemcpyHostToDevice));
         }
     }
@@ -2743,13 +2668,13 @@ int grape_create(grape_handle **out, const grape_problem *p) try {
         } else {
             for (int q = 0; q < nops; ++q) rb[q] = bound_of(op_ptr(q));
         }
-        CCHK(dmalloc(&h->d_rb, rb.size()));
+        CCHK(h->mem.alloc(&h->d_rb, rb.size()));
         CCHK(hipMemcpy(h->d_rb, rb.data(), rb.size() * 8, hipMemcpyHostToDevice));
         // the exact-derivative route sub-steps its series for ||H|| dt > theta; :taylor is the reference's plain recursion
         const char *envd = getenv("GRAPE_DERIV_THETA");
         h->sub_theta = p->gradient_method == GRAPE_GRAD_GRADGEN ? (envd ? atof(envd) : 4.0) : 0.0;
         // (behind the batch flags, round 6: the flags of the economized derivative series, deriv_econ_kernel)
-        CCHK(dmalloc(&h->d_batchflag, (size_t)2 * K * ((N_T + 15) / 16)));
+        CCHK(h->mem.alloc(&h->d_batchflag, (size_t)2 * K * ((N_T + 15) / 16)));
         CCHK(hipMemset(h->d_batchflag, 0, (size_t)2 * K * ((N_T + 15) / 16) * sizeof(int)));
     }
     if (h->series) {
@@ -2765,13 +2690,13 @@ int grape_create(grape_handle **out, const grape_problem *p) try {
         if (NP >= 48 && !h->large && h->deriv2 && h->series_tol <= h->taylor_tol && bytes <= ((size_t)24 << 30) &&
             (double)bytes <= 0.5 * (double)free_p && !(envp && atoi(envp) == 0)) {
             h->maxp = 32;
-            CCHK(dmalloc(&h->d_gpark, (size_t)K * N_T * h->maxp * NP));
-            CCHK(dmalloc(&h->d_morder, (size_t)K * N_T));
+            CCHK(h->mem.alloc(&h->d_gpark, (size_t)K * N_T * h->maxp * NP));
+            CCHK(h->mem.alloc(&h->d_morder, (size_t)K * N_T));
             CCHK(hipMemset(h->d_morder, 0xFF, (size_t)K * N_T * sizeof(int)));
         }
     }
-    CCHK(dmalloc(&h->d_fw, (size_t)K * (N_T + 1) * NP));
-    CCHK(dmalloc(&h->d_bw, (size_t)K * (N_T + 1) * NP));
+    CCHK(h->mem.alloc(&h->d_fw, (size_t)K * (N_T + 1) * NP));
+    CCHK(h->mem.alloc(&h->d_bw, (size_t)K * (N_T + 1) * NP));
     {   // parallel scan of the sweeps over the time axis (N <= 64): a latency chain of N_T steps becomes Bk + NB + Bk steps.  It
         // pays while the chains alone leave the chip idle: phase 1 does NP times the flops of the sweep it replaces, so its
         // throughput term grows with the number of trajectories while the sequential sweeps do not.  Measured crossovers at
@@ -2798,23 +2723,23 @@ int grape_create(grape_handle **out, const grape_problem *p) try {
             if (const char *envb = getenv("GRAPE_SCAN16_BK")) best = std::max(2, atoi(envb));
             h->scan_Bk = std::min(best, N_T);
             h->scan_NB = (N_T + h->scan_Bk - 1) / h->scan_Bk;
-            CCHK(dmalloc(&h->d_scanF, (size_t)h->KC * h->scan_NB * NP * NP));
-            CCHK(dmalloc(&h->d_scan_fw, (size_t)K * (h->scan_NB + 1) * NP));
-            CCHK(dmalloc(&h->d_scan_bw, (size_t)K * (h->scan_NB + 1) * NP));
+            CCHK(h->mem.alloc(&h->d_scanF, (size_t)h->KC * h->scan_NB * NP * NP));
+            CCHK(h->mem.alloc(&h->d_scan_fw, (size_t)K * (h->scan_NB + 1) * NP));
+            CCHK(h->mem.alloc(&h->d_scan_bw, (size_t)K * (h->scan_NB + 1) * NP));
             h->scan16 = true;
         }
     }
-    CCHK(dmalloc(&h->d_tg, (size_t)K * L * N_T));
+    CCHK(h->mem.alloc(&h->d_tg, (size_t)K * L * N_T));
     // ONE slab for everything an evaluation hands back or resets: [tau + sums (2K + 8) | G (L N_T) | flags (8 ints) | statistics]
     // -- the single-wait grape_eval reads the first three with one copy and resets the last two with one memset (every copy or
     // memset is a launch of its own: 5 us each on a 340-us evaluation at C2)
-    CCHK(dmalloc(&h->d_ret, (size_t)2 * K + 8 + (size_t)L * N_T + 4 + (size_t)GRAPE_STAT_SHARDS * GRAPE_STAT_SLOTS));
+    CCHK(h->mem.alloc(&h->d_ret, (size_t)2 * K + 8 + (size_t)L * N_T + 4 + (size_t)GRAPE_STAT_SHARDS * GRAPE_STAT_SLOTS));
     h->d_out = h->d_ret;
     h->d_G = h->d_ret + (size_t)2 * K + 8;
     h->d_flags = (int *)(h->d_G + (size_t)L * N_T);
     h->d_stats = (unsigned long long *)(h->d_G + (size_t)L * N_T + 4);
-    CCHK(dmalloc(&h->d_f, 2)); CCHK(dmalloc(&h->d_rho, (size_t)K));
-    CCHK(dmalloc(&h->d_cellflag, (size_t)K * N_T));
+    CCHK(h->mem.alloc(&h->d_f, 2)); CCHK(h->mem.alloc(&h->d_rho, (size_t)K));
+    CCHK(h->mem.alloc(&h->d_cellflag, (size_t)K * N_T));
     // more than two controls shared by all trajectories: the cell fetches H0_k and ONE summed operator S_n (ctrl_sum_kernel)
     // control operators per trajectory (the ensemble of robustness problems): the summed controls are an array per CELL of the
     // generator classes -- as large as the propagators themselves -- when that fits; the assembly cells then apply as they are
@@ -2844,21 +2769,21 @@ int grape_create(grape_handle **out, const grape_problem *p) try {
         if (h->deriv_econ) h->d_econ_pairs = grape_econ_pairs();   // (the compiled derivative kernels read the tables through a pointer)
         if (h->deriv_econ && !h->d_econ_pairs) h->deriv_econ = false;
         if (h->deriv_econ && lg_ok) {
-            CCHK(dmalloc(&h->d_celldeg, (size_t)h->KC * N_T));
+            CCHK(h->mem.alloc(&h->d_celldeg, (size_t)h->KC * N_T));
             CCHK(hipMemset(h->d_celldeg, 0, (size_t)h->KC * N_T * sizeof(int)));
         }
     }
-    if (h->asm16p || h->asm18gp) CCHK(dmalloc(&h->d_dte, (size_t)(L <= 2 ? 4 : 8) * N_T));
+    if (h->asm16p || h->asm18gp) CCHK(h->mem.alloc(&h->d_dte, (size_t)(L <= 2 ? 4 : 8) * N_T));
     if (h->t18 && !h->large && !h->series && ((L > 2 && !p->hc_per_traj) || (h->asm16 && !h->asm16p) || (h->asm18g && !h->asm18gp)) && (h->NT >= 3 || h->t18_small))
-        CCHK(dmalloc(&h->d_Sf, (size_t)(p->hc_per_traj ? (size_t)h->KC * N_T : (size_t)N_T) * 2 * NP * NP));
+        CCHK(h->mem.alloc(&h->d_Sf, (size_t)(p->hc_per_traj ? (size_t)h->KC * N_T : (size_t)N_T) * 2 * NP * NP));
     if (h->asm16 || h->asm18g) {
         // one workgroup per CU (512 registers, 139 KB of LDS), never more workgroups than cells
         const long ncell = (long)h->KC * N_T;
         h->asm_blocks = (int)std::max<long>(1, std::min<long>(h->num_cus, ncell));
         std::vector<int> tab((size_t)4 * h->asm_blocks);
         grape_t16_walks(h->KC, N_T, h->asm_blocks, tab.data());
-        CCHK(dmalloc(&h->d_wgtab, tab.size()));
-        CCHK(dmalloc(&h->d_splan, (size_t)ncell));
+        CCHK(h->mem.alloc(&h->d_wgtab, tab.size()));
+        CCHK(h->mem.alloc(&h->d_splan, (size_t)ncell));
         CCHK(hipMemset(h->d_splan, 0, (size_t)ncell * sizeof(int)));
         CCHK(hipMemcpy(h->d_wgtab, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice));
         const char *envw = getenv("GRAPE_EXPM_WALK"), *envq = getenv("GRAPE_EXPM_SQ");
@@ -2879,16 +2804,16 @@ int grape_create(grape_handle **out, const grape_problem *p) try {
                     xi[2 * ((size_t)(K + k) * 64 + i) + 1] = -p->target[2 * ((size_t)k * N + i) + 1] * itn;   // conj
                 }
             }
-            CCHK(dmalloc(&h->d_xinit, (size_t)2 * K * 64));
+            CCHK(h->mem.alloc(&h->d_xinit, (size_t)2 * K * 64));
             CCHK(hipMemcpy(h->d_xinit, xi.data(), xi.size() * 8, hipMemcpyHostToDevice));
-            CCHK(dmalloc(&h->d_prog, (size_t)2 * K));
+            CCHK(h->mem.alloc(&h->d_prog, (size_t)2 * K));
             CCHK(hipMemset(h->d_prog, 0, (size_t)2 * K * sizeof(int)));
         }
     }
     // (N <= 16 stays with five products: one tile per side is latency-bound -- the kernel gains nothing from the shorter
     // polynomial and the second launch costs 10 us of an evaluation of 0.4 ms; measured at C2: 0.079 -> 0.098 ms)
     if (h->t16 && h->t18 && h->herm && !h->large && !h->series && (h->NT >= 3 || (h->NT == 2 && h->t18_small))) {
-        CCHK(dmalloc(&h->d_celllist, (size_t)K * N_T));
+        CCHK(h->mem.alloc(&h->d_celllist, (size_t)K * N_T));
         // Gram matrices of the operators of every generator class (plan of the four-product route, t16_plan_kernel)
         // ... and behind each matrix the SHAPE FACTORS kappa_a of its operators (round-4 advisor finding: the estimate
         // R_est = 2 ||H dt||_F / sqrt(N) assumes a semicircle spectrum and is off by up to sqrt(N) / 2 either way).  What the
@@ -2949,7 +2874,7 @@ int grape_create(grape_handle **out, const grape_problem *p) try {
                 gram[(size_t)kc * GS + (size_t)M * M + a] = (a > 0 && !p->hc_per_traj) ? kap_shared[a - 1] : shape_factor(o, fro2);
             }
         });
-        CCHK(dmalloc(&h->d_gram, gram.size()));
+        CCHK(h->mem.alloc(&h->d_gram, gram.size()));
         CCHK(hipMemcpy(h->d_gram, gram.data(), gram.size() * 8, hipMemcpyHostToDevice));
     }
     if (h->large && h->series) {
@@ -2964,8 +2889,8 @@ int grape_create(grape_handle **out, const grape_problem *p) try {
         h->cheby_pair = h->fuse && per_xcd >= 2 * S;
         if (!h->cheby_pair) h->fuse = false;   // the two directions do not fit side by side: sequential sweeps
         h->cheby_round = 8 * std::max(1, per_xcd / ((h->cheby_pair ? 2 : 1) * S));
-        CCHK(dmalloc(&h->d_xch, (size_t)2 * K * 4 * NP));
-        CCHK(dmalloc(&h->d_xcc, (size_t)2 * K * 32));
+        CCHK(h->mem.alloc(&h->d_xch, (size_t)2 * K * 4 * NP));
+        CCHK(h->mem.alloc(&h->d_xcc, (size_t)2 * K * 32));
     }
     if (h->large && !h->series) {
         // cooperative sweeps when the trajectories alone cannot fill the chip: S siblings per trajectory,
@@ -2985,7 +2910,7 @@ int grape_create(grape_handle **out, const grape_problem *p) try {
             h->coop_S = S;
             h->coop_nw = R >= 16 ? 16 : R;
             h->coop_rpw = R / h->coop_nw;
-            CCHK(dmalloc(&h->d_xcc_sw, (size_t)2 * K * 32));
+            CCHK(h->mem.alloc(&h->d_xcc_sw, (size_t)2 * K * 32));
         }
     }
     CCHK(hipMemset(h->d_flags, 0, 8 * sizeof(int)));
@@ -3004,16 +2929,16 @@ int grape_create(grape_handle **out, const grape_problem *p) try {
                     dt_[2 * ((size_t)kd * pp + (size_t)j * NP + i)] = p->Dpen[2 * ((size_t)kd * nn + (size_t)j * N + i)];
                     dt_[2 * ((size_t)kd * pp + (size_t)j * NP + i) + 1] = p->Dpen[2 * ((size_t)kd * nn + (size_t)j * N + i) + 1];
                 }
-        CCHK(dmalloc(&h->d_Dt, (size_t)Kd * pp));
+        CCHK(h->mem.alloc(&h->d_Dt, (size_t)Kd * pp));
         CCHK(hipMemcpy(h->d_Dt, dt_.data(), dt_.size() * 8, hipMemcpyHostToDevice));
         std::vector<double> wq(N_T + 1);
         for (int m = 0; m <= N_T; ++m)   // trapezoid weights of optimize.jl:727-750
             wq[m] = m == 0 ? (p->tlist[1] - p->tlist[0]) / 2.0
                            : (m < N_T ? 0.5 * (p->tlist[m + 1] - p->tlist[m - 1]) : (p->tlist[N_T] - p->tlist[N_T - 1]) / 2.0);
-        CCHK(dmalloc(&h->d_wq, (size_t)N_T + 1));
+        CCHK(h->mem.alloc(&h->d_wq, (size_t)N_T + 1));
         CCHK(hipMemcpy(h->d_wq, wq.data(), wq.size() * 8, hipMemcpyHostToDevice));
-        CCHK(dmalloc(&h->d_xi, (size_t)K * (N_T + 1) * NP));
-        CCHK(dmalloc(&h->d_gb, (size_t)K * (N_T + 1)));
+        CCHK(h->mem.alloc(&h->d_xi, (size_t)K * (N_T + 1) * NP));
+        CCHK(h->mem.alloc(&h->d_gb, (size_t)K * (N_T + 1)));
     }
     {   // grape_eval_batch: the envelope of the batched kernels (grape_batch.hip.h) -- the one-wave family of N <= 16 on the
         // polynomial exponential, exact derivative, no running cost, concurrent sweeps available (non-zero targets);
@@ -3021,10 +2946,10 @@ int grape_create(grape_handle **out, const grape_problem *p) try {
         h->batch_ok = !h->large && !h->series && NP == 16 && h->t18 && h->t18_small && p->gradient_method == GRAPE_GRAD_GRADGEN &&
                       !h->have_gb && h->fuse && !h->no_target && h->K == h->K_total && !h->test_hooks && L <= 8;
         if (const char *envb = getenv("GRAPE_BATCH")) h->batch_env = atoi(envb) != 0 ? 1 : 0;
-        if (const char *envs = getenv("GRAPE_BATCH_SETS")) h->batch_sets_env = std::max(0, atoi(envs));
-        if (const char *envh = getenv("GRAPE_HVP_DIRS")) h->hvp_dirs_env = std::max(0, atoi(envh));
+        if (const char *envs = getenv("GRAPE_BATCH_SETS")) h->batch.store.env = std::max(0, atoi(envs));
+        if (const char *envh = getenv("GRAPE_HVP_DIRS")) h->hvp.store.env = std::max(0, atoi(envh));
     }
-    CCHK(hipHostMalloc((void **)&h->h_pin, h->h_pin_doubles * 8, hipHostMallocDefault));
+    CCHK(h->mem.alloc_pinned(&h->h_pin, h->h_pin_doubles));
     // Everything above went through the NULL stream (hipMemset of device memory returns before the fill has run; a copy from
     // pageable memory returns once the data is staged), the evaluations run on the handle's own NON-BLOCKING stream, which
     // the NULL stream does not order: without this wait the fill of the stored-state arrays (1 GB at C4) can still be in
@@ -3594,14 +3519,14 @@ int backward_enqueue(grape_handle *h, const double f_total[2], const double *chi
     }
     if (xi) {   // [K][N_T+1][N] complex -> d_xi [K][N_T+1][NP] (zero padded); trapezoid weights of optimize.jl:727-750
         const size_t rows = (size_t)h->K * (h->N_T + 1);
-        if (!h->d_xi) HIPCHK(h, dmalloc(&h->d_xi, rows * h->NP));
+        if (!h->d_xi) HIPCHK(h, h->mem.alloc(&h->d_xi, rows * h->NP));
         if (!h->d_wq) {
             const int N_T = h->N_T;
             std::vector<double> tl(N_T + 1), wq(N_T + 1);
             HIPCHK(h, hipMemcpy(wq.data(), h->d_dts, (size_t)N_T * 8, hipMemcpyDeviceToHost));   // dt_n
             for (int m = 0; m <= N_T; ++m)
                 tl[m] = m == 0 ? 0.5 * wq[0] : (m < N_T ? 0.5 * (wq[m - 1] + wq[m]) : 0.5 * wq[N_T - 1]);
-            HIPCHK(h, dmalloc(&h->d_wq, (size_t)N_T + 1));
+            HIPCHK(h, h->mem.alloc(&h->d_wq, (size_t)N_T + 1));
             HIPCHK(h, hipMemcpy(h->d_wq, tl.data(), tl.size() * 8, hipMemcpyHostToDevice));
         }
         if (h->NP != h->N) HIPCHK(h, hipMemsetAsync(h->d_xi, 0, rows * h->NP * 16, h->stream));
@@ -3610,7 +3535,7 @@ int backward_enqueue(grape_handle *h, const double f_total[2], const double *chi
     }
     const double2 *d_chi = nullptr;
     if (chi) {
-        if (!h->d_chi_in) HIPCHK(h, dmalloc(&h->d_chi_in, (size_t)h->K * h->N));
+        if (!h->d_chi_in) HIPCHK(h, h->mem.alloc(&h->d_chi_in, (size_t)h->K * h->N));
         HIPCHK(h, hipMemcpyAsync(h->d_chi_in, chi, (size_t)h->K * h->N * 16, hipMemcpyHostToDevice, h->stream));
         d_chi = h->d_chi_in;
     }
@@ -4347,8 +4272,8 @@ int grape_get_time_gradient(grape_handle *h, double *dJdt) try {
     // (the states of a device-pointer call on the caller's stream: that stream is not ordered against the handle's)
     if (h->foreign_stream) HIPCHK(h, hipDeviceSynchronize());
     (void)hipGetLastError();
-    if (!h->d_tq) HIPCHK(h, dmalloc(&h->d_tq, (size_t)h->K * N_T));
-    if (!h->d_dJdt) HIPCHK(h, dmalloc(&h->d_dJdt, (size_t)N_T));
+    if (!h->d_tq) HIPCHK(h, h->mem.alloc(&h->d_tq, (size_t)h->K * N_T));
+    if (!h->d_dJdt) HIPCHK(h, h->mem.alloc(&h->d_dJdt, (size_t)N_T));
     TimeGradArgs ta{};
     ta.H0f = h->d_H0f; ta.Hcf = h->d_Hcf; ta.eps = h->d_eps; ta.shape = h->d_shape;
     ta.fw = h->d_fw; ta.bw = h->d_bw; ta.rho = h->d_rho; ta.z = h->tg_unit ? h->d_z : nullptr;
@@ -4407,9 +4332,7 @@ GRAPE_BARRIER(h ? &h->err : &g_create_error)
 
 int grape_get_open_hvp_info(grape_handle *h, double *out, int n) try {
     if (!h || !out || !h->open) return GRAPE_ERR_INVALID;
-    const int m = std::max(0, std::min(n, 7));
-    for (int i = 0; i < m; ++i) out[i] = h->open->hv_info[i];
-    return m;
+    return copy_info(h->open->hv.info, 7, out, n);
 }
 GRAPE_BARRIER(h ? &h->err : &g_create_error)
 
@@ -4427,9 +4350,7 @@ GRAPE_BARRIER(h ? &h->err : &g_create_error)
 
 int grape_get_open_batch_info(grape_handle *h, double *out, int n) try {
     if (!h || !out || !h->open) return GRAPE_ERR_INVALID;
-    const int m = std::max(0, std::min(n, 7));
-    for (int i = 0; i < m; ++i) out[i] = h->open->ob_info[i];
-    return m;
+    return copy_info(h->open->ob.info, 7, out, n);
 }
 GRAPE_BARRIER(h ? &h->err : &g_create_error)
 
@@ -4496,59 +4417,35 @@ BatchStrides batch_strides(const grape_handle *h) {
     return st;
 }
 
-void batch_release(grape_handle *h) {
-    void *bufs[] = {h->d_beps, h->d_bSf, h->d_bslab, h->d_brho, h->d_bU, h->d_bfw, h->d_bbw, h->d_btg, h->d_bz, h->d_bstats};
-    for (void *b : bufs)
-        if (b) hipFree(b);
-    if (h->h_bpin) hipHostFree(h->h_bpin);
-    h->d_beps = h->d_bSf = h->d_bslab = h->d_brho = nullptr;
-    h->d_bU = h->d_bfw = h->d_bbw = h->d_btg = h->d_bz = nullptr;
-    h->d_bstats = nullptr; h->h_bpin = nullptr;
-    h->batch_cap = 0; h->batch_bytes = 0;
-}
-
-// sets per launch group for a call with P sets, and storage for that many: from a memory budget (half of what the device
-// has free -- what the storage already holds counts as free --, at most 16 GB: the propagators of a set are KC N_T 4 KB,
-// 65 MB at the C2 shape), GRAPE_BATCH_SETS overrides.  The storage only grows.
+// sets per launch group (the set is grid.y / grid.z of the launches) and storage for that many, at most 16 GB: the propagators
+// of a set are KC N_T 4 KB, 65 MB at the C2 shape.  A buffer of no elements is not requested (d_bSf == nullptr is read as "none").
 int batch_reserve(grape_handle *h, int P, const BatchStrides &st, int *sets) {
+    auto &b = h->batch;
     const size_t per_set = 8 * (st.eps + st.Sf + st.slab + st.k) + 16 * (st.U + 2 * st.vec + st.tg + st.k);
-    int Pg = std::min(P, 65535);   // (the set is grid.y / grid.z of the launches)
-    if (h->batch_sets_env > 0) Pg = std::min(Pg, h->batch_sets_env);
-    else if (Pg > h->batch_cap) {
-        size_t free_b = 0, total_b = 0;
-        HIPCHK(h, hipMemGetInfo(&free_b, &total_b));
-        const double budget = std::min(0.5 * ((double)free_b + (double)h->batch_bytes), 16.0 * 1073741824.0);
-        Pg = (int)std::max<double>(1.0, std::min<double>((double)Pg, std::floor(budget / (double)per_set)));
-    }
-    *sets = Pg;
-    if (Pg <= h->batch_cap) return GRAPE_OK;
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    batch_release(h);
-    const size_t n = (size_t)Pg;
-    int rc = GRAPE_OK;
-    auto get = [&](auto **ptr, size_t count) {
-        if (rc == GRAPE_OK && count && dmalloc(ptr, count) != hipSuccess) {
-            h->err = "grape_eval_batch: out of device memory for the storage of " + std::to_string(Pg) + " pulse sets (" +
-                     std::to_string(per_set * n >> 20) + " MB); GRAPE_BATCH_SETS=<n> makes the launch groups smaller";
-            (void)hipGetLastError();
-            rc = GRAPE_ERR_HIP;
-        }
-    };
-    get(&h->d_beps, n * st.eps); get(&h->d_bSf, n * st.Sf); get(&h->d_bslab, n * st.slab); get(&h->d_brho, n * st.k);
-    get(&h->d_bU, n * st.U); get(&h->d_bfw, n * st.vec); get(&h->d_bbw, n * st.vec); get(&h->d_btg, n * st.tg); get(&h->d_bz, n * st.k);
-    get(&h->d_bstats, (size_t)GRAPE_STAT_SHARDS * GRAPE_STAT_SLOTS);
-    if (rc == GRAPE_OK && hipHostMalloc((void **)&h->h_bpin, n * (st.eps + st.slab) * 8, hipHostMallocDefault) != hipSuccess) {
+    bool grown = false;
+    const int rc = group_reserve(h, b.store, P, per_set, 16.0 * 1073741824.0, "grape_eval_batch", "pulse sets", "GRAPE_BATCH_SETS", sets,
+                                 [&](GroupStore::Requests &req) {
+        const size_t n = (size_t)*sets;
+        auto get = [&](auto **ptr, size_t count) { if (count) req(ptr, count); };
+        get(&b.d_beps, n * st.eps); get(&b.d_bSf, n * st.Sf); get(&b.d_bslab, n * st.slab); get(&b.d_brho, n * st.k);
+        get(&b.d_bU, n * st.U); get(&b.d_bfw, n * st.vec); get(&b.d_bbw, n * st.vec); get(&b.d_btg, n * st.tg); get(&b.d_bz, n * st.k);
+        get(&b.d_bstats, (size_t)GRAPE_STAT_SHARDS * GRAPE_STAT_SLOTS);
+    }, &grown);
+    if (rc || !grown) return rc;
+    const size_t n = (size_t)*sets;
+    if (b.store.mem.alloc_pinned(&b.h_bpin, n * (st.eps + st.slab)) != hipSuccess) {
         h->err = "grape_eval_batch: out of pinned host memory for the staging area of a launch group";
         (void)hipGetLastError();
-        rc = GRAPE_ERR_HIP;
+        b.store.release();
+        return GRAPE_ERR_HIP;
     }
-    if (rc) { batch_release(h); return rc; }
-    // (the padded rows and columns of the stored states and propagators are never written: the kernels read them as zeros)
-    HIPCHK(h, hipMemsetAsync(h->d_bfw, 0, n * st.vec * 16, h->stream));
-    HIPCHK(h, hipMemsetAsync(h->d_bbw, 0, n * st.vec * 16, h->stream));
-    HIPCHK(h, hipMemsetAsync(h->d_bU, 0, n * st.U * 16, h->stream));
-    h->batch_cap = Pg;
-    h->batch_bytes = per_set * n + (size_t)GRAPE_STAT_SHARDS * GRAPE_STAT_SLOTS * 8;
+    // (the padded rows and columns of the stored states and propagators are never written: the kernels read them as zeros;
+    // the storage holds its sets only once that is enqueued)
+    b.store.cap = 0;
+    HIPCHK(h, hipMemsetAsync(b.d_bfw, 0, n * st.vec * 16, h->stream));
+    HIPCHK(h, hipMemsetAsync(b.d_bbw, 0, n * st.vec * 16, h->stream));
+    HIPCHK(h, hipMemsetAsync(b.d_bU, 0, n * st.U * 16, h->stream));
+    b.store.cap = *sets;
     return GRAPE_OK;
 }
 
@@ -4558,24 +4455,24 @@ int batch_group(grape_handle *h, const BatchStrides &st, int p0, int Pg, const d
     hipStream_t s = h->stream;
     const size_t LN = (size_t)h->L * h->N_T, n = (size_t)Pg;
     const int K = h->K, NP = h->NP, N_T = h->N_T, L = h->L;
-    int *flags0 = (int *)(h->d_bslab + 2 * (size_t)K + 8 + LN);
-    memcpy(h->h_bpin, pulsevals, n * LN * 8);
-    HIPCHK(h, hipMemcpyAsync(h->d_beps, h->h_bpin, n * LN * 8, hipMemcpyHostToDevice, s));
-    HIPCHK(h, hipMemsetAsync(h->d_bslab, 0, n * st.slab * 8, s));
-    HIPCHK(h, hipMemsetAsync(h->d_bstats, 0, (size_t)GRAPE_STAT_SHARDS * GRAPE_STAT_SLOTS * 8, s));
+    int *flags0 = (int *)(h->batch.d_bslab + 2 * (size_t)K + 8 + LN);
+    memcpy(h->batch.h_bpin, pulsevals, n * LN * 8);
+    HIPCHK(h, hipMemcpyAsync(h->batch.d_beps, h->batch.h_bpin, n * LN * 8, hipMemcpyHostToDevice, s));
+    HIPCHK(h, hipMemsetAsync(h->batch.d_bslab, 0, n * st.slab * 8, s));
+    HIPCHK(h, hipMemsetAsync(h->batch.d_bstats, 0, (size_t)GRAPE_STAT_SHARDS * GRAPE_STAT_SLOTS * 8, s));
     // ---- phase A: one wave per cell (p, class, n) ----
     ExpmArgs ea{};
-    ea.H0f = h->d_H0f; ea.Hcf = h->d_Hcf; ea.eps = h->d_beps; ea.shape = h->d_shape; ea.dts = h->d_dts;
-    ea.U = h->d_bU; ea.flags = flags0; ea.stats = h->d_bstats; ea.cellflag = nullptr;
+    ea.H0f = h->d_H0f; ea.Hcf = h->d_Hcf; ea.eps = h->batch.d_beps; ea.shape = h->d_shape; ea.dts = h->d_dts;
+    ea.U = h->batch.d_bU; ea.flags = flags0; ea.stats = h->batch.d_bstats; ea.cellflag = nullptr;
     ea.K = h->KC; ea.rep = h->d_rep; ea.L = L; ea.N_T = N_T; ea.hc_per_traj = h->p.hc_per_traj;
     ea.n1 = h->d_n1; ea.n1_k = K;
-    if (h->d_bSf) {
+    if (h->batch.d_bSf) {
         CtrlSumArgs ca{};
-        ca.Hcf = h->d_Hcf; ca.eps = h->d_beps; ca.shape = h->d_shape; ca.Sf = h->d_bSf;
+        ca.Hcf = h->d_Hcf; ca.eps = h->batch.d_beps; ca.shape = h->d_shape; ca.Sf = h->batch.d_bSf;
         ca.L = L; ca.N_T = N_T; ca.pp2 = 2 * NP * NP; ca.per_traj = 0; ca.rep = nullptr;
         hipLaunchKernelGGL(batch_ctrl_sum_kernel, dim3((unsigned)N_T, 1, (unsigned)Pg), dim3(256), 0, s, ca, st);
         HIPCHK(h, hipGetLastError());
-        ea.Sf = h->d_bSf;
+        ea.Sf = h->batch.d_bSf;
     }
     {   // workgroups per set: ten one-wave workgroups per CU over the whole group (139 registers, 16 KB of LDS), in eights
         const long ncell = (long)h->KC * N_T;
@@ -4585,30 +4482,30 @@ int batch_group(grape_handle *h, const BatchStrides &st, int p0, int Pg, const d
     }
     // ---- phase B: one wave per (p, k, direction), sequential sweeps ----
     SweepArgs sa{};
-    sa.U = h->d_bU; sa.cls = h->d_cls; sa.psi0 = h->d_psi0; sa.target = h->d_target; sa.weights = h->d_weights;
-    sa.store = h->d_bfw; sa.tau = (double2 *)h->d_bslab; sa.f = nullptr; sa.rho = h->d_brho; sa.flags = flags0;
+    sa.U = h->batch.d_bU; sa.cls = h->d_cls; sa.psi0 = h->d_psi0; sa.target = h->d_target; sa.weights = h->d_weights;
+    sa.store = h->batch.d_bfw; sa.tau = (double2 *)h->batch.d_bslab; sa.f = nullptr; sa.rho = h->batch.d_brho; sa.flags = flags0;
     sa.chi_min_norm = h->chi_min_norm;
     sa.K = K; sa.K_total = h->K_total; sa.N = h->N; sa.N_T = N_T; sa.functional = h->p.functional;
     if (G) {
         SweepArgs sb = sa;
-        sb.store = h->d_bbw; sb.unit_chi = 1; sb.inv_tnorm = h->d_inv_tnorm;
+        sb.store = h->batch.d_bbw; sb.unit_chi = 1; sb.inv_tnorm = h->d_inv_tnorm;
         hipLaunchKernelGGL(batch_sweep_pair_kernel, dim3((unsigned)(2 * K), (unsigned)Pg), dim3(64), 0, s, sa, sb, st);
     } else
         hipLaunchKernelGGL(batch_sweep_fw_kernel, dim3((unsigned)K, (unsigned)Pg), dim3(64), 0, s, sa, st);
     HIPCHK(h, hipGetLastError());
-    hipLaunchKernelGGL(batch_tau_reduce_kernel, dim3(1, (unsigned)Pg), dim3(64), 0, s, h->d_bslab, (const double *)h->d_weights, K, st);
+    hipLaunchKernelGGL(batch_tau_reduce_kernel, dim3(1, (unsigned)Pg), dim3(64), 0, s, h->batch.d_bslab, (const double *)h->d_weights, K, st);
     HIPCHK(h, hipGetLastError());
     if (G) {
         ChiCoeffArgs ca{};
-        ca.s = sa; ca.s.inv_tnorm = h->d_inv_tnorm; ca.rho = h->d_brho; ca.z = h->d_bz;
+        ca.s = sa; ca.s.inv_tnorm = h->d_inv_tnorm; ca.rho = h->batch.d_brho; ca.z = h->batch.d_bz;
         hipLaunchKernelGGL(batch_chi_coeff_kernel, dim3((unsigned)((K + 63) / 64), (unsigned)Pg), dim3(64), 0, s, ca, st);
         HIPCHK(h, hipGetLastError());
         // ---- phase C: derivative overlaps.  The cells of a workgroup follow the handle's own rule (K alone): the chain of a
         // workgroup updates its generator incrementally, so the partition must not depend on the batch.  (Measured at the
         // C2 shape, K = 1 .. 32, P = 4 .. 64: 1, 2, 4 or 8 cells per workgroup give the same times within 3 %.) ----
         DerivArgs da{};
-        da.H0t = h->d_H0t; da.Hct = h->d_Hct; da.eps = h->d_beps; da.shape = h->d_shape; da.dts = h->d_dts;
-        da.fw = h->d_bfw; da.bw = h->d_bbw; da.rho = h->d_ones; da.tg = h->d_btg; da.flags = flags0; da.stats = h->d_bstats;
+        da.H0t = h->d_H0t; da.Hct = h->d_Hct; da.eps = h->batch.d_beps; da.shape = h->d_shape; da.dts = h->d_dts;
+        da.fw = h->batch.d_bfw; da.bw = h->batch.d_bbw; da.rho = h->d_ones; da.tg = h->batch.d_btg; da.flags = flags0; da.stats = h->batch.d_bstats;
         da.K = K; da.L = L; da.N_T = N_T; da.hc_per_traj = h->p.hc_per_traj;
         da.max_order = h->taylor_max_order; da.tol = h->taylor_tol;
         da.rb = h->d_rb; da.rb_k = K; da.sub_theta = h->sub_theta;
@@ -4625,12 +4522,12 @@ int batch_group(grape_handle *h, const BatchStrides &st, int p0, int Pg, const d
             default: hipLaunchKernelGGL(batch_deriv_kernel<8>, grid, blk, 0, s, da, st); break;
         }
         HIPCHK(h, hipGetLastError());
-        hipLaunchKernelGGL(batch_grad_reduce_kernel, dim3((unsigned)((LN + 15) / 16), (unsigned)Pg), dim3(256), 0, s, h->d_btg, K, (int)LN,
-                           h->d_bslab, (const double2 *)h->d_bz, st);
+        hipLaunchKernelGGL(batch_grad_reduce_kernel, dim3((unsigned)((LN + 15) / 16), (unsigned)Pg), dim3(256), 0, s, h->batch.d_btg, K, (int)LN,
+                           h->batch.d_bslab, (const double2 *)h->batch.d_bz, st);
         HIPCHK(h, hipGetLastError());
     }
-    double *hs = h->h_bpin + n * LN;
-    HIPCHK(h, hipMemcpyAsync(hs, h->d_bslab, n * st.slab * 8, hipMemcpyDeviceToHost, s));
+    double *hs = h->batch.h_bpin + n * LN;
+    HIPCHK(h, hipMemcpyAsync(hs, h->batch.d_bslab, n * st.slab * 8, hipMemcpyDeviceToHost, s));
     HIPCHK(h, hipStreamSynchronize(s));
     for (int q = 0; q < Pg; ++q) {
         const double *slab = hs + (size_t)q * st.slab;
@@ -4685,7 +4582,7 @@ int grape_eval_batch(grape_handle *h, int P, const double *pulsevals, double *J,
             }
         }
         batch_invalidate(h);
-        h->batch_info[0] = 0.; h->batch_info[1] = 1.; h->batch_info[2] = (double)P; h->batch_info[3] = (double)h->batch_bytes;
+        h->batch.info[0] = 0.; h->batch.info[1] = 1.; h->batch.info[2] = (double)P; h->batch.info[3] = (double)h->batch.store.mem.bytes();
         return GRAPE_OK;
     }
     HIPCHK(h, hipSetDevice(h->device));
@@ -4700,16 +4597,14 @@ int grape_eval_batch(grape_handle *h, int P, const double *pulsevals, double *J,
         rc = batch_group(h, st, p0, std::min(Pg, P - p0), pulsevals + (size_t)p0 * LN, J, G, tau);
         if (rc) return rc;
     }
-    h->batch_info[0] = 1.; h->batch_info[1] = (double)Pg; h->batch_info[2] = (double)groups; h->batch_info[3] = (double)h->batch_bytes;
+    h->batch.info[0] = 1.; h->batch.info[1] = (double)Pg; h->batch.info[2] = (double)groups; h->batch.info[3] = (double)h->batch.store.mem.bytes();
     return GRAPE_OK;
 }
 GRAPE_BARRIER(h ? &h->err : &g_create_error)
 
 int grape_get_batch_info(grape_handle *h, double *out, int n) try {
     if (!h || !out) return GRAPE_ERR_INVALID;
-    const int m = std::max(0, std::min(n, 4));
-    for (int i = 0; i < m; ++i) out[i] = h->batch_info[i];
-    return m;
+    return copy_info(h->batch.info, 4, out, n);
 }
 GRAPE_BARRIER(h ? &h->err : &g_create_error)
 
@@ -4720,56 +4615,23 @@ GRAPE_BARRIER(h ? &h->err : &g_create_error)
 // ---------------------------------------------------------------------------------------
 namespace {
 
-void hvp_release(grape_handle *h) {
-    void *bufs[] = {h->d_hvV, h->d_hvws, h->d_hvout, h->d_hvdpsi, h->d_hvdtau, h->d_hvdcoef, h->d_hvtg, h->d_hvstats};
-    for (void *b : bufs)
-        if (b) hipFree(b);
-    h->d_hvV = h->d_hvws = h->d_hvout = nullptr;
-    h->d_hvdpsi = h->d_hvdtau = h->d_hvdcoef = h->d_hvtg = nullptr;
-    h->d_hvstats = nullptr;
-    h->hvp_cap = 0; h->hvp_bytes = 0;
-}
-
 // bytes of storage one direction needs: step matrices of K workgroups, Psi', the per-trajectory terms, V and H v
 size_t hvp_bytes_per_direction(const grape_handle *h) {
     const size_t K = (size_t)h->K, LN = (size_t)h->L * h->N_T, pp = (size_t)h->NP * h->NP;
     return K * (4 * pp * 8 + (size_t)(h->N_T + 1) * h->NP * 16 + LN * 16 + 32 + 32) + 2 * LN * 8;
 }
 
-// directions per launch group for a call with nv directions, and storage for that many: from a memory budget (half of what
-// the device has free -- what the storage already holds counts as free --, at most 8 GB), GRAPE_HVP_DIRS overrides.
-// The storage only grows.
+// directions per launch group (the direction is grid.y of the launches) and storage for that many, at most 8 GB
 int hvp_reserve(grape_handle *h, int nv, int *dirs) {
-    const size_t per = hvp_bytes_per_direction(h);
-    int nd = std::min(nv, 65535);   // (the direction is grid.y of the launches)
-    if (h->hvp_dirs_env > 0) nd = std::min(nd, h->hvp_dirs_env);
-    else if (nd > h->hvp_cap) {
-        size_t free_b = 0, total_b = 0;
-        HIPCHK(h, hipMemGetInfo(&free_b, &total_b));
-        const double budget = std::min(0.5 * ((double)free_b + (double)h->hvp_bytes), 8.0 * 1073741824.0);
-        nd = (int)std::max<double>(1.0, std::min<double>((double)nd, std::floor(budget / (double)per)));
-    }
-    *dirs = nd;
-    if (nd <= h->hvp_cap) return GRAPE_OK;
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    hvp_release(h);
-    const size_t n = (size_t)nd, K = (size_t)h->K, LN = (size_t)h->L * h->N_T, pp = (size_t)h->NP * h->NP;
-    int rc = GRAPE_OK;
-    auto get = [&](auto **ptr, size_t count) {
-        if (rc == GRAPE_OK && dmalloc(ptr, count) != hipSuccess) {
-            h->err = "grape_hvp: out of device memory for the storage of " + std::to_string(nd) + " directions (" +
-                     std::to_string(per * n >> 20) + " MB); GRAPE_HVP_DIRS=<n> makes the launch groups smaller";
-            (void)hipGetLastError();
-            rc = GRAPE_ERR_HIP;
-        }
-    };
-    get(&h->d_hvV, n * LN); get(&h->d_hvws, n * K * 4 * pp); get(&h->d_hvout, n * LN);
-    get(&h->d_hvdpsi, n * K * (size_t)(h->N_T + 1) * h->NP); get(&h->d_hvdtau, n * K); get(&h->d_hvdcoef, n * K);
-    get(&h->d_hvtg, n * K * LN); get(&h->d_hvstats, 4 * n * K + 1);
-    if (rc) { hvp_release(h); return rc; }
-    h->hvp_cap = nd;
-    h->hvp_bytes = per * n + 8;
-    return GRAPE_OK;
+    auto &v = h->hvp;
+    const size_t K = (size_t)h->K, LN = (size_t)h->L * h->N_T, pp = (size_t)h->NP * h->NP;
+    return group_reserve(h, v.store, nv, hvp_bytes_per_direction(h), 8.0 * 1073741824.0, "grape_hvp", "directions", "GRAPE_HVP_DIRS", dirs,
+                         [&](GroupStore::Requests &get) {
+        const size_t n = (size_t)*dirs;
+        get(&v.d_hvV, n * LN); get(&v.d_hvws, n * K * 4 * pp); get(&v.d_hvout, n * LN);
+        get(&v.d_hvdpsi, n * K * (size_t)(h->N_T + 1) * h->NP); get(&v.d_hvdtau, n * K); get(&v.d_hvdcoef, n * K);
+        get(&v.d_hvtg, n * K * LN); get(&v.d_hvstats, 4 * n * K + 1);
+    });
 }
 
 template <int NP>
@@ -4812,13 +4674,13 @@ int grape_hvp(grape_handle *h, int nv, const double *V, double *HV) try {
     if (rc) return rc;
     const size_t LN = (size_t)h->L * h->N_T, K = (size_t)h->K;
     hipStream_t s = h->stream;
-    int *d_flag = (int *)(h->d_hvstats + 4 * (size_t)h->hvp_cap * K);
+    int *d_flag = (int *)(h->hvp.d_hvstats + 4 * (size_t)h->hvp.store.cap * K);
     HvpArgs a{};
     a.H0f = h->d_H0f; a.Hcf = h->d_Hcf; a.eps = h->d_eps; a.shape = h->d_shape; a.dts = h->d_dts; a.rb = h->d_rb;
-    a.V = h->d_hvV; a.fw = h->d_fw; a.target = h->d_target; a.weights = h->d_weights;
+    a.V = h->hvp.d_hvV; a.fw = h->d_fw; a.target = h->d_target; a.weights = h->d_weights;
     a.tau = (const double2 *)h->d_out; a.f = h->d_out + 2 * K;
-    a.dpsi = h->d_hvdpsi; a.dtau = h->d_hvdtau; a.dcoef = h->d_hvdcoef; a.tg = h->d_hvtg; a.ws = h->d_hvws;
-    a.flags = d_flag; a.stats = h->d_hvstats;
+    a.dpsi = h->hvp.d_hvdpsi; a.dtau = h->hvp.d_hvdtau; a.dcoef = h->hvp.d_hvdcoef; a.tg = h->hvp.d_hvtg; a.ws = h->hvp.d_hvws;
+    a.flags = d_flag; a.stats = h->hvp.d_hvstats;
     a.tol = h->series_tol; a.theta = h->series_theta;
     a.K = h->K; a.K_total = h->K_total; a.L = h->L; a.N = h->N; a.N_T = h->N_T; a.functional = h->p.functional;
     a.hc_per_traj = h->p.hc_per_traj;
@@ -4827,8 +4689,8 @@ int grape_hvp(grape_handle *h, int nv, const double *V, double *HV) try {
     double terms = 0., substeps = 0., terms_fw = 0.;
     for (int j0 = 0; j0 < nv; j0 += nd) {
         const int ng = std::min(nd, nv - j0);
-        HIPCHK(h, hipMemcpyAsync(h->d_hvV, V + (size_t)j0 * LN, (size_t)ng * LN * 8, hipMemcpyHostToDevice, s));
-        HIPCHK(h, hipMemsetAsync(h->d_hvstats, 0, (4 * (size_t)h->hvp_cap * K + 1) * 8, s));
+        HIPCHK(h, hipMemcpyAsync(h->hvp.d_hvV, V + (size_t)j0 * LN, (size_t)ng * LN * 8, hipMemcpyHostToDevice, s));
+        HIPCHK(h, hipMemsetAsync(h->hvp.d_hvstats, 0, (4 * (size_t)h->hvp.store.cap * K + 1) * 8, s));
         switch (h->NP) {
             case 16: hvp_launch<16>(a, ng, nct, s); break;
             case 32: hvp_launch<32>(a, ng, nct, s); break;
@@ -4838,13 +4700,13 @@ int grape_hvp(grape_handle *h, int nv, const double *V, double *HV) try {
         HIPCHK(h, hipGetLastError());
         // (H v)_j = -2 Re sum_k of the per-trajectory terms: the gradient's reduction, fixed order
         for (int j = 0; j < ng; ++j)
-            hipLaunchKernelGGL(grad_reduce_kernel, dim3((unsigned)((LN + 15) / 16)), dim3(256), 0, s, h->d_hvtg + (size_t)j * K * LN, h->K,
-                               (int)LN, h->d_hvout + (size_t)j * LN, (const double2 *)nullptr);
+            hipLaunchKernelGGL(grad_reduce_kernel, dim3((unsigned)((LN + 15) / 16)), dim3(256), 0, s, h->hvp.d_hvtg + (size_t)j * K * LN, h->K,
+                               (int)LN, h->hvp.d_hvout + (size_t)j * LN, (const double2 *)nullptr);
         HIPCHK(h, hipGetLastError());
-        HIPCHK(h, hipMemcpyAsync(HV + (size_t)j0 * LN, h->d_hvout, (size_t)ng * LN * 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(h, hipMemcpyAsync(HV + (size_t)j0 * LN, h->hvp.d_hvout, (size_t)ng * LN * 8, hipMemcpyDeviceToHost, s));
         st.assign(4 * (size_t)ng * K + 1, 0ull);
         // (the statistics of this group: forward workgroups, then backward workgroups; the flag word sits behind the capacity)
-        HIPCHK(h, hipMemcpyAsync(st.data(), h->d_hvstats, 4 * (size_t)ng * K * 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(h, hipMemcpyAsync(st.data(), h->hvp.d_hvstats, 4 * (size_t)ng * K * 8, hipMemcpyDeviceToHost, s));
         HIPCHK(h, hipMemcpyAsync(&st[4 * (size_t)ng * K], d_flag, 8, hipMemcpyDeviceToHost, s));
         HIPCHK(h, hipStreamSynchronize(s));
         for (size_t q = 0; q < 2 * (size_t)ng * K; ++q) {
@@ -4856,18 +4718,16 @@ int grape_hvp(grape_handle *h, int nv, const double *V, double *HV) try {
             return GRAPE_ERR_TAYLOR;
         }
     }
-    h->hvp_info[0] = terms; h->hvp_info[1] = substeps; h->hvp_info[2] = (double)nd; h->hvp_info[3] = (double)h->hvp_bytes;
-    h->hvp_info[4] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    h->hvp_info[5] = terms_fw; h->hvp_info[6] = terms - terms_fw;
+    h->hvp.info[0] = terms; h->hvp.info[1] = substeps; h->hvp.info[2] = (double)nd; h->hvp.info[3] = (double)h->hvp.store.mem.bytes();
+    h->hvp.info[4] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    h->hvp.info[5] = terms_fw; h->hvp.info[6] = terms - terms_fw;
     return GRAPE_OK;
 }
 GRAPE_BARRIER(h ? &h->err : &g_create_error)
 
 int grape_get_hvp_info(grape_handle *h, double *out, int n) try {
     if (!h || !out) return GRAPE_ERR_INVALID;
-    const int m = std::max(0, std::min(n, 7));
-    for (int i = 0; i < m; ++i) out[i] = h->hvp_info[i];
-    return m;
+    return copy_info(h->hvp.info, 7, out, n);
 }
 GRAPE_BARRIER(h ? &h->err : &g_create_error)
 

@@ -495,6 +495,79 @@ def test_exception_barrier_with_device_memory_in_flight(g, monkeypatch):
         assert np.isfinite(J) and np.isfinite(G).all()
 
 
+def _cycle_closed_batch(g):
+    """N = 16 on the batched route: 4 sets, then 8 (release and regrow); the propagators alone are 13 MB per set"""
+    from grape_jl_amd import synth
+    pr = synth.make_problem(16, 2, 400, 8, seed=21)
+    X = np.stack([s * pr["pulsevals"] for s in (1.0, 0.5, 1.3, 0.7, 0.9, 1.1, 0.6, 1.2)])
+
+    def cycle():
+        with g.GrapeHip(pr["H0"], pr["Hc"], pr["tlist"], pr["psi0"], pr["target"], pr["weights"]) as h:
+            for P in (4, 8):
+                J, G, _ = h.eval_batch(X[:P])
+                assert h.batch_info()["route"] == 1 and h.batch_info()["sets_per_group"] == P
+                assert np.isfinite(J).all() and np.isfinite(G).all() and np.abs(G).max() > 0
+    return cycle
+
+
+def _cycle_closed_hvp(g):
+    """N = 64: 4 directions, then 8 (5.5 MB each), and the buffers of the first time gradient and the first caller's chi"""
+    from grape_jl_amd import synth
+    pr = synth.make_problem(64, 2, 200, 16, seed=8)
+    x = pr["pulsevals"]
+    V = np.random.default_rng(5).standard_normal((8, x.size))
+
+    def cycle():
+        with g.GrapeHip(pr["H0"], pr["Hc"], pr["tlist"], pr["psi0"], pr["target"], pr["weights"]) as h:
+            J, G, _ = h.eval(x)
+            outs = [G, h.hvp(V[:4]), h.hvp(V), h.time_gradient(), h.backward_chi(0.25 * np.conj(h.final_states()))]
+            assert h.hvp_info()["dirs_per_group"] == 8 and h.hvp_info()["bytes"] > 8 * (5 << 20)
+            assert np.isfinite(J) and all(np.isfinite(o).all() and np.abs(o).max() > 0 for o in outs)
+    return cycle
+
+
+def _cycle_open(g):
+    """d = 32, J = 2: 8 directions (3 MB each), 8 then 16 pulse sets (2.4 MB each), time gradient, a caller's chi"""
+    from grape_jl_amd import synth
+    pr = synth.make_open_problem(32, 2, 50, 2, 2, seed=3202)
+    x = pr["pulsevals"]
+    V = np.random.default_rng(6).standard_normal((8, x.size))
+    X = np.stack([(0.5 + 0.05 * p) * x for p in range(16)])
+
+    def cycle():
+        with g.GrapeHipOpen(pr["H0"], pr["Hc"], pr["cops"], pr["tlist"], pr["rho0"], pr["target"]) as h:
+            J, G, _ = h.eval(x)
+            outs = [G, h.open_hvp(V)]
+            for P in (8, 16):
+                Jb, Gb, _ = h.open_eval_batch(X[:P])
+                assert h.open_batch_info()["sets_per_group"] == P
+                outs += [Jb, Gb]
+            outs += [h.time_gradient(), h.backward_chi(0.25 * pr["target"])]
+            assert h.open_hvp_info()["bytes"] > 8 * (2 << 20) and h.open_batch_info()["bytes"] > 16 * (2 << 20)
+            assert np.isfinite(J) and all(np.isfinite(o).all() and np.abs(o).max() > 0 for o in outs)
+    return cycle
+
+
+@pytest.mark.parametrize("which", ["closed_batch", "closed_hvp", "open"])
+def test_create_use_every_growing_store_destroy_repeatedly(g, monkeypatch, which):
+    """whatever a handle allocated -- the buffers of grape_create, the storage of grape_eval_batch, grape_hvp, grape_open_hvp and
+    grape_open_eval_batch after it has grown once, the buffers of the first time gradient and of the first caller's chi --
+    goes with the handle: after eight create / use / destroy cycles free device memory is where it was (64 MB of slack, as
+    above; one leaked store would be 190 MB or more)"""
+    import torch
+    monkeypatch.setenv("GRAPE_BATCH", "1")
+    cycle = {"closed_batch": _cycle_closed_batch, "closed_hvp": _cycle_closed_hvp, "open": _cycle_open}[which](g)
+    cycle()                                            # (runtime warm: module loads, pools)
+    torch.cuda.synchronize()
+    free0 = torch.cuda.mem_get_info()[0]
+    for _ in range(8):
+        cycle()
+    torch.cuda.synchronize()
+    drift = torch.cuda.mem_get_info()[0] - free0
+    print(dict(which=which, drift_mb=drift / 2 ** 20))
+    assert abs(drift) <= 64 << 20
+
+
 def test_composite_handle_validates_its_first_collective(g, monkeypatch):
     """the first evaluation of a handle that reduces with RCCL also takes the host-staged sums and compares (advisor
     finding of round 4: the collective path had never been checked against anything); a second handle on the same device
