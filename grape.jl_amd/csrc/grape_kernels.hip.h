@@ -4112,24 +4112,26 @@ struct GbArgs {
     int NP, N_T, d_per_traj;
 };
 __global__ void __launch_bounds__(256) gb_kernel(GbArgs a) {
-    __shared__ double2 psi[256];
+    __shared__ double2 psi[512];                 // NP <= 512: a thread owns rows tid and tid + 256
     __shared__ double part[256];
     const int NP = a.NP, tid = threadIdx.x;
     const int cell = blockIdx.x;                 // k * (N_T+1) + n
     const int k = cell / (a.N_T + 1);
     const double2 *Dt = a.Dt + (size_t)(a.d_per_traj ? k : 0) * NP * NP;
-    if (tid < NP) psi[tid] = a.fw[(size_t)cell * NP + tid];
+    for (int i = tid; i < NP; i += 256) psi[i] = a.fw[(size_t)cell * NP + i];
     __syncthreads();
-    double ar = 0., ai = 0.;
-    if (tid < NP) {
+    double acc = 0.;
+    for (int i = tid; i < NP; i += 256) {
+        double ar = 0., ai = 0.;
         for (int j = 0; j < NP; ++j) {
-            const double2 d = Dt[(size_t)j * NP + tid], p = psi[j];
+            const double2 d = Dt[(size_t)j * NP + i], p = psi[j];
             ar += d.x * p.x - d.y * p.y;
             ai += d.x * p.y + d.y * p.x;
         }
-        a.xi[(size_t)cell * NP + tid] = make_double2(-ar, -ai);
+        a.xi[(size_t)cell * NP + i] = make_double2(-ar, -ai);
+        acc += psi[i].x * ar + psi[i].y * ai;    // Re conj(psi_i) (D psi)_i
     }
-    part[tid] = tid < NP ? psi[tid].x * ar + psi[tid].y * ai : 0.;   // Re conj(psi_i) (D psi)_i
+    part[tid] = acc;
     __syncthreads();
     for (int off = 128; off >= 1; off >>= 1) {
         if (tid < off) part[tid] += part[tid + off];
