@@ -35,7 +35,7 @@ EXPORTS = ["grape_create", "grape_destroy", "grape_eval", "grape_forward", "grap
            "grape_get_final_states", "grape_backward_chi",
            "grape_get_time_gradient", "grape_set_tlist", "grape_eval_batch", "grape_get_batch_info", "grape_create_open",
            "grape_hvp", "grape_get_hvp_info", "grape_open_time_gradient", "grape_open_hvp", "grape_get_open_hvp_info",
-           "grape_open_eval_batch", "grape_get_open_batch_info"]
+           "grape_open_eval_batch", "grape_get_open_batch_info", "grape_open_set_running_cost", "grape_open_backward_xi"]
 
 
 class GrapeHipError(RuntimeError):
@@ -103,7 +103,7 @@ def build_asm(verbose: bool = False, workdir: str | None = None) -> str:
 def _sources():
     srcs = [os.path.join(_CSRC, f) for f in ("grape_hip.hip", "grape_t18.hip", "grape_kernels.hip.h", "grape_large.hip.h",
                                              "grape_series.hip.h", "grape_cheby.hip.h", "grape_t18.hip.h", "grape_t18_coeffs.h",
-                                             "grape_deriv3.hip.h", "grape_timegrad.hip.h", "grape_batch.hip.h", "grape_lindblad.hip.h", "grape_lindblad_tg.hip.h", "grape_hvp.hip.h", "grape_lindblad_hvp.hip.h", "grape_lindblad_batch.hip.h", "grape_devmem.h", os.path.join("asm", "gen_t16.py"), os.path.join("asm", "gen_t16p.py"), os.path.join("asm", "gen_t18g.py"), os.path.join("asm", "gen_t18gp.py"), os.path.join("asm", "gen_d3.py"), os.path.join("asm", "gen_d3s.py"), os.path.join("asm", "gen_lg.py"), os.path.join("asm", "gen_d4.py"), os.path.join("asm", "gcn.py"))]
+                                             "grape_deriv3.hip.h", "grape_timegrad.hip.h", "grape_batch.hip.h", "grape_lindblad.hip.h", "grape_lindblad_tg.hip.h", "grape_hvp.hip.h", "grape_lindblad_hvp.hip.h", "grape_lindblad_batch.hip.h", "grape_lindblad_rc.hip.h", "grape_devmem.h", os.path.join("asm", "gen_t16.py"), os.path.join("asm", "gen_t16p.py"), os.path.join("asm", "gen_t18g.py"), os.path.join("asm", "gen_t18gp.py"), os.path.join("asm", "gen_d3.py"), os.path.join("asm", "gen_d3s.py"), os.path.join("asm", "gen_lg.py"), os.path.join("asm", "gen_d4.py"), os.path.join("asm", "gcn.py"))]
     return srcs, os.path.join(_HERE, "..", "include", "grape_hip.h")
 
 
@@ -220,6 +220,8 @@ def load_library():
     lib.grape_get_open_hvp_info.argtypes = [vp, vp, ip]
     lib.grape_open_eval_batch.argtypes = [vp, ip, vp, vp, vp, vp]
     lib.grape_get_open_batch_info.argtypes = [vp, vp, ip]
+    lib.grape_open_set_running_cost.argtypes = [vp, vp, ip, C.c_double]
+    lib.grape_open_backward_xi.argtypes = [vp, vp, vp, vp, C.c_double, vp]
     lib.grape_last_error.argtypes = [vp]
     lib.grape_last_error.restype = C.c_char_p
     lib.grape_abi_version.restype = ip
@@ -551,7 +553,8 @@ class GrapeHipOpen(GrapeHip):
     ``storage()`` [K, N_T+1, d, d], ``backward_chi`` takes [K, d, d].  tau_k = tr(target_k^dagger rho_k(T)).
     ``time_gradient()`` is grape_open_time_gradient, ``open_hvp()`` / ``open_hvp_info()`` are grape_open_hvp /
     grape_get_open_hvp_info, ``open_eval_batch()`` / ``open_batch_info()`` grape_open_eval_batch / grape_get_open_batch_info
-    (the inherited ``eval_batch`` stays the loop over ``eval`` it is on such a handle).  Not available (GrapeHipError, the handle stays usable): propagator, storage(1), backward_xi, the
+    (the inherited ``eval_batch`` stays the loop over ``eval`` it is on such a handle).  ``set_running_cost()`` /
+    ``open_backward_xi()`` are grape_open_set_running_cost / grape_open_backward_xi, the state running costs.  Not available (GrapeHipError, the handle stays usable): propagator, storage(1), backward_xi, the
     device-pointer calls, and the inherited ``hvp()`` (grape_hvp keeps its defined refusal of open handles; its message names
     ``grape_open_hvp``)."""
 
@@ -699,6 +702,43 @@ class GrapeHipOpen(GrapeHip):
         self._lib.grape_get_open_batch_info(self._h, out.ctypes.data, 7)
         return dict(sets_per_group=int(out[0]), groups=int(out[1]), bytes=int(out[2]), ms=float(out[3]), terms_forward=int(out[4]),
                     terms_backward=int(out[5]), series_steps=int(out[6]))
+
+    def set_running_cost(self, D, lambda_b):
+        """Install the state running cost g_b(rho) = Re tr(D rho) with weight ``lambda_b`` (grape_open_set_running_cost), or
+        remove it (``D`` None or ``lambda_b`` 0).  D: [d, d] shared or [K, d, d], row-major numpy.  The next call has to be
+        ``eval`` or ``forward``; while the cost is set J = J_T + lambda_b J_b, ``sums()[4]`` = sum_k J_b,k and every gradient
+        includes it."""
+        ptr, per_traj = None, 0
+        if D is not None:
+            D = np.asarray(D)
+            if D.shape not in ((self.N, self.N), (self.K, self.N, self.N)):
+                raise ValueError(f"D must be [d, d] or [K, d, d] with d = {self.N}, K = {self.K}, got {D.shape}")
+            per_traj = int(D.ndim == 3)
+            D = _c128(np.swapaxes(D, -1, -2))
+            ptr = D.ctypes.data
+        self._chk(self._lib.grape_open_set_running_cost(self._h, ptr, per_traj, float(lambda_b)))
+        self.lambda_b = float(lambda_b) if D is not None else 0.0
+
+    def open_backward_xi(self, xi, lambda_b, f_total=None, chi=None):
+        """Backward half with a caller-supplied inhomogeneity xi_k(t_n) of an ARBITRARY state running cost g_b, defined by
+        dg_b = -2 Re <<xi | d rho>> ([K, N_T+1, d, d], evaluated by the caller on ``storage()``; grape_open_backward_xi).
+        ``chi``: boundary matrices of a user-defined J_T ([K, d, d]) or None for the handle's functional with ``f_total``
+        (default: this handle's own sum_k w_k tau_k).  Returns the gradient of J_T + lambda_b J_b.  A method of its own, as the
+        C call is: ``backward_xi`` stays grape_backward_xi, which refuses an open handle."""
+        xi = _c128(np.swapaxes(np.asarray(xi), -1, -2), (self.K, self.N_T + 1, self.N, self.N))
+        G = np.empty(self.L * self.N_T)
+        cptr, fptr = None, None
+        if chi is not None:
+            chi = _c128(np.swapaxes(np.asarray(chi), -1, -2), (self.K, self.N, self.N))
+            cptr = chi.ctypes.data
+        else:
+            if f_total is None:
+                sm = self.sums()
+                f_total = complex(sm[0], sm[1])
+            f = np.array([complex(f_total).real, complex(f_total).imag], dtype=np.float64)
+            fptr = f.ctypes.data
+        self._chk(self._lib.grape_open_backward_xi(self._h, fptr, cptr, xi.ctypes.data, float(lambda_b), G.ctypes.data))
+        return G
 
     def backward_xi(self, xi, lambda_b, f_total=None, chi=None):
         dummy = np.zeros(2)

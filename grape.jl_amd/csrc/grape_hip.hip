@@ -19,6 +19,7 @@
 #include "grape_hvp.hip.h"
 #include "grape_lindblad_hvp.hip.h"
 #include "grape_lindblad_batch.hip.h"
+#include "grape_lindblad_rc.hip.h"
 #include "grape_devmem.h"
 
 #include <rccl/rccl.h>
@@ -1450,6 +1451,7 @@ struct HandleGuard {
 thread_local const std::vector<double> *tl_forced_bal = nullptr;
 int multi_fail(grape_handle *h, grape_handle *c, int rc);
 int backward_device_impl(grape_handle *h, const double *d_f, double *d_G, hipStream_t s, const double2 *d_chi);
+double open_lambda_b(const grape_handle *h);   // lambda_b of the built-in running cost of an open-system handle, 0 without one
 
 // J from the (all-)reduced sums [Re f, Im f, sum w|tau|^2, Re sum w tau, sum_k J_b,k]: J_parts[1] + J_parts[3],
 // optimize.jl:757-766
@@ -1459,7 +1461,8 @@ double functional_from_sums(const grape_handle *h, const double *sums) {
     if (h->p.functional == GRAPE_J_T_SM) J = 1.0 - (sums[0] * sums[0] + sums[1] * sums[1]) / (Kt * Kt);
     else if (h->p.functional == GRAPE_J_T_SS) J = 1.0 - sums[2] / Kt;
     else J = 1.0 - sums[3] / Kt;
-    if (h->p.Dpen && h->p.lambda_b != 0.0) J += h->p.lambda_b * sums[4];
+    if (h->open) { if (open_lambda_b(h) != 0.0) J += open_lambda_b(h) * sums[4]; }   // (grape_open_set_running_cost)
+    else if (h->p.Dpen && h->p.lambda_b != 0.0) J += h->p.lambda_b * sums[4];
     return J;
 }
 
@@ -1487,7 +1490,7 @@ struct OpenCtx {
     bool have_bwd = false;
     // grape_open_time_gradient (grape_lindblad_tg.hip.h): what the stored states and the boundary data on the
     // device can give.  Validity is a flag of its own (have_bwd belongs to grape_get_tau_grads).
-    enum { TG_NONE, TG_NO_GRADIENT, TG_FORWARD_ONLY, TG_READY, TG_FAILED, TG_NEW_GRID, TG_BATCH };
+    enum { TG_NONE, TG_NO_GRADIENT, TG_FORWARD_ONLY, TG_READY, TG_FAILED, TG_NEW_GRID, TG_BATCH, TG_NEW_COST, TG_RUNNING_COST };
     int tg_state = TG_NONE;
     bool tg_chi_user = false;     // ... the last backward half took the caller's chi_k(T) (still in d_chi)
     size_t ws_mats = 0;           // matrices (2 NP^2 doubles) d_ws holds
@@ -1496,7 +1499,7 @@ struct OpenCtx {
     // grape_open_hvp (grape_lindblad_hvp.hip.h): Hessian-vector products on the stored rho_k(t_n).  Validity is a
     // word of its own: tg_state asks for a backward half, this call needs the forward half alone.  The storage is allocated
     // by the first call and grows with the directions of a launch group.
-    enum { HV_NONE, HV_READY, HV_FAILED, HV_NEW_GRID, HV_BATCH };
+    enum { HV_NONE, HV_READY, HV_FAILED, HV_NEW_GRID, HV_BATCH, HV_NEW_COST };
     int hv_state = HV_NONE;
     struct HvpStore {
         GroupStore store;         // units: directions; env: GRAPE_HVP_DIRS
@@ -1516,12 +1519,22 @@ struct OpenCtx {
         unsigned long long *d_obstats = nullptr;
         double info[7] = {0., 0., 0., 0., 0., 0., 0.};   // grape_get_open_batch_info
     } ob;
+    // state running costs (grape_lindblad_rc.hip.h).  The built-in cost g_b = Re tr(D rho) of
+    // grape_open_set_running_cost: Xi_k = -D_k^dagger / 2, the trapezoid weights of the current grid, g_b of every stored state.
+    // d_xi_user holds the caller's xi of grape_open_backward_xi.  All four are allocated on first use.
+    bool rc_set = false;
+    int rc_per_traj = 0;
+    double rc_lambda = 0.0;
+    double *d_Xi = nullptr, *d_wq = nullptr, *d_gb = nullptr, *d_xi_user = nullptr;
+    std::vector<double> tlist;    // the current grid (the weights are recomputed from it)
 };
 
 namespace {
 
 template <typename T>
 hipError_t open_alloc(OpenCtx *o, T **p, size_t n) { return o->mem.alloc(p, std::max<size_t>(n, 1)); }   // (an empty array is one element)
+
+double open_lambda_b(const grape_handle *h) { return h->open->rc_set ? h->open->rc_lambda : 0.0; }
 
 void open_destroy(grape_handle *h) {
     OpenCtx *o = h->open;
@@ -1591,6 +1604,16 @@ int open_refuse(grape_handle *h, const char *what) {
     return GRAPE_ERR_INVALID;
 }
 
+// a buffer of the running-cost calls through the handle's allocator; a failure names the size and leaves nothing behind
+template <typename T>
+int open_rc_alloc(grape_handle *h, T **p, size_t n, const char *what) {
+    const hipError_t e = open_alloc(h->open, p, n);
+    if (e == hipSuccess) return GRAPE_OK;
+    (void)hipGetLastError();
+    h->err = std::string("out of device memory for ") + what + " (" + std::to_string(n * sizeof(T)) + " bytes): " + hipGetErrorString(e);
+    return GRAPE_ERR_HIP;
+}
+
 #define OPEN_LAUNCH(kernel, grid, threads_of, ...)                                                           \
     switch (h->NP) {                                                                                         \
     case 16: hipLaunchKernelGGL(kernel<16>, grid, dim3(threads_of(16)), 0, h->stream, __VA_ARGS__); break;   \
@@ -1618,6 +1641,14 @@ int open_forward(grape_handle *h, const double *pulsevals, double *tau) {
     OPEN_LAUNCH(lind_forward_kernel, dim3((unsigned)K), OPEN_FWD_THREADS, a)
     hipLaunchKernelGGL(tau_reduce_kernel, dim3(1), dim3(64), 0, h->stream, (const double2 *)o->d_out, (const double *)o->d_weights, h->K,
                        o->d_out + 2 * K);
+    if (o->rc_set) {   // g_b of every stored state and their trapezoid sum (optimize.jl:727-750): sums[4]
+        LindGbArgs ga{};
+        ga.Xi = o->d_Xi; ga.stride_k = o->rc_per_traj ? 2 * (size_t)h->NP * h->NP : 0; ga.store = o->d_store; ga.gb = o->d_gb;
+        ga.NP2 = h->NP * h->NP; ga.N_T = h->N_T;
+        hipLaunchKernelGGL(lind_gb_kernel, dim3((unsigned)(K * (h->N_T + 1))), dim3(256), 0, h->stream, ga);
+        hipLaunchKernelGGL(jb_reduce_kernel, dim3(1), dim3(256), 0, h->stream, (const double *)o->d_gb, (const double *)o->d_wq, h->K, h->N_T,
+                           o->d_out + 2 * K + 4);
+    }
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipEventRecord(o->ev[1], h->stream));
     int flags[8] = {0};
@@ -1635,8 +1666,10 @@ int open_forward(grape_handle *h, const double *pulsevals, double *tau) {
     return GRAPE_OK;
 }
 
-// backward sweep + gradient from f = sum_k w_k tau_k (built-in functionals) or from the caller's chi_k(T) ([K][N*N] column-major)
-int open_backward(grape_handle *h, const double f_total[2], const double *chi, double *G) {
+// backward sweep + gradient from f = sum_k w_k tau_k (built-in functionals) or from the caller's chi_k(T) ([K][N*N] column-major).
+// xi_user: the caller's xi is in d_xi_user and weighs lambda_user (grape_open_backward_xi); otherwise the built-in running
+// cost, if one is set.  Either launches lind_backward_rc_kernel; a handle without a cost launches what it always did.
+int open_backward(grape_handle *h, const double f_total[2], const double *chi, double *G, bool xi_user = false, double lambda_user = 0.0) {
     OpenCtx *o = h->open;
     HIPCHK(h, hipSetDevice(h->device));
     (void)hipGetLastError();
@@ -1654,8 +1687,17 @@ int open_backward(grape_handle *h, const double f_total[2], const double *chi, d
         HIPCHK(h, hipMemcpyAsync(o->d_f, f_total, 16, hipMemcpyHostToDevice, h->stream));
     }
     HIPCHK(h, hipMemsetAsync(o->d_flags, 0, 8 * sizeof(int), h->stream));
+    const bool with_cost = xi_user || o->rc_set;
     HIPCHK(h, hipEventRecord(o->ev[0], h->stream));
-    OPEN_LAUNCH(lind_backward_kernel, dim3((unsigned)K, (unsigned)h->L), OPEN_BWD_THREADS, a)
+    if (with_cost) {
+        LindRcArgs rc{};
+        rc.wq = o->d_wq;
+        if (xi_user) { rc.xi = o->d_xi_user; rc.stride_k = (size_t)(h->N_T + 1) * 2 * np2; rc.stride_n = 2 * np2; rc.lambda_b = lambda_user; }
+        else { rc.xi = o->d_Xi; rc.stride_k = o->rc_per_traj ? 2 * np2 : 0; rc.stride_n = 0; rc.lambda_b = o->rc_lambda; }
+        OPEN_LAUNCH(lind_backward_rc_kernel, dim3((unsigned)K, (unsigned)h->L), OPEN_BWD_THREADS, a, rc)
+    } else {
+        OPEN_LAUNCH(lind_backward_kernel, dim3((unsigned)K, (unsigned)h->L), OPEN_BWD_THREADS, a)
+    }
     hipLaunchKernelGGL(grad_reduce_kernel, dim3((unsigned)((nl + 15) / 16)), dim3(256), 0, h->stream, o->d_tg, h->K, (int)nl, o->d_G,
                        (const double2 *)nullptr);
     HIPCHK(h, hipGetLastError());
@@ -1669,7 +1711,7 @@ int open_backward(grape_handle *h, const double f_total[2], const double *chi, d
     const int rc = open_status(h, flags[0]);
     if (rc) return rc;
     o->have_bwd = true;
-    o->tg_state = OpenCtx::TG_READY; o->tg_chi_user = chi != nullptr;
+    o->tg_state = with_cost ? OpenCtx::TG_RUNNING_COST : OpenCtx::TG_READY; o->tg_chi_user = chi != nullptr;
     return GRAPE_OK;
 }
 
@@ -1741,6 +1783,22 @@ int open_work(grape_handle *h, double *out, int n) {
     return 4;
 }
 
+// trapezoid weights of the running cost on the current grid (optimize.jl:727-750); d_wq is allocated on first use
+int open_upload_wq(grape_handle *h) {
+    OpenCtx *o = h->open;
+    const int N_T = h->N_T;
+    const std::vector<double> &t = o->tlist;
+    std::vector<double> wq((size_t)N_T + 1);
+    for (int m = 0; m <= N_T; ++m)
+        wq[m] = m == 0 ? (t[1] - t[0]) / 2.0 : (m == N_T ? (t[N_T] - t[N_T - 1]) / 2.0 : (t[m + 1] - t[m - 1]) / 2.0);
+    if (!o->d_wq) {
+        const int rc = open_rc_alloc(h, &o->d_wq, wq.size(), "the trapezoid weights");
+        if (rc) return rc;
+    }
+    HIPCHK(h, hipMemcpy(o->d_wq, wq.data(), wq.size() * 8, hipMemcpyHostToDevice));
+    return GRAPE_OK;
+}
+
 int open_set_tlist(grape_handle *h, const double *tlist) {
     OpenCtx *o = h->open;
     HIPCHK(h, hipSetDevice(h->device));
@@ -1748,6 +1806,8 @@ int open_set_tlist(grape_handle *h, const double *tlist) {
     std::vector<double> dts(h->N_T);
     for (int n = 0; n < h->N_T; ++n) dts[n] = tlist[n + 1] - tlist[n];
     HIPCHK(h, hipMemcpy(o->d_dts, dts.data(), dts.size() * 8, hipMemcpyHostToDevice));
+    o->tlist.assign(tlist, tlist + h->N_T + 1);
+    if (o->d_wq) { const int rc = open_upload_wq(h); if (rc) return rc; }
     h->have_forward = false;
     o->have_bwd = false;
     o->tg_state = OpenCtx::TG_NEW_GRID;
@@ -1770,6 +1830,9 @@ int open_time_gradient(grape_handle *h, double *dJdt) {
     case OpenCtx::TG_FORWARD_ONLY: OPEN_TG_REFUSE("called between grape_forward and the backward half");
     case OpenCtx::TG_NEW_GRID: OPEN_TG_REFUSE("grape_set_tlist came after the last evaluation: the stored states belong to the previous grid");
     case OpenCtx::TG_BATCH: OPEN_TG_REFUSE("the last call was grape_eval_batch: the stored states are not those of one defined evaluation");
+    case OpenCtx::TG_NEW_COST: OPEN_TG_REFUSE("grape_open_set_running_cost came after the last evaluation: its backward half belongs to the previous cost");
+    case OpenCtx::TG_RUNNING_COST: OPEN_TG_REFUSE("the last backward half carried a state running cost (grape_open_set_running_cost or "
+                                                  "grape_open_backward_xi): the time-gradient kernel does not carry the inhomogeneity");
     default: OPEN_TG_REFUSE("the last evaluation failed");
     }
     const size_t K = (size_t)h->K, N_T = (size_t)h->N_T;
@@ -1824,10 +1887,12 @@ int open_hvp(grape_handle *h, int nv, const double *V, double *HV) {
     OpenCtx *o = h->open;
     if (h->K != h->K_total) OPEN_HV_REFUSE("a split-phase shard (K < K_total) is out of scope: f' would need an all-reduce of its own");
     if (h->no_target) OPEN_HV_REFUSE("this handle has no target states (grape_problem.target == NULL): chi'(T) would be the caller's");
+    if (o->rc_set) OPEN_HV_REFUSE("a state running cost is set on this handle (grape_open_set_running_cost): its second-order terms are not carried");
     switch (o->hv_state) {
     case OpenCtx::HV_READY: break;
     case OpenCtx::HV_NONE: OPEN_HV_REFUSE("no valid forward state: no evaluation on this handle yet");
     case OpenCtx::HV_NEW_GRID: OPEN_HV_REFUSE("no valid forward state: grape_set_tlist came after the last evaluation, the stored states belong to the previous grid");
+    case OpenCtx::HV_NEW_COST: OPEN_HV_REFUSE("no valid forward state: grape_open_set_running_cost came after the last evaluation");
     case OpenCtx::HV_BATCH: OPEN_HV_REFUSE("no valid forward state: the last call was grape_eval_batch, the stored states are not those of one defined evaluation");
     default: OPEN_HV_REFUSE("no valid forward state: the last forward sweep failed");
     }
@@ -1983,6 +2048,57 @@ int open_eval_batch(grape_handle *h, int P, const double *pulsevals, double *J, 
     return GRAPE_OK;
 }
 
+#define OPEN_RC_REFUSE(call, text) do { h->err = call ": " text; return GRAPE_ERR_INVALID; } while (0)
+
+// Installs g_b(rho) = Re tr(D rho) with weight lambda_b, or removes it (D == NULL or lambda_b == 0).  D: [N*N] shared or
+// [K][N*N], column-major.  Xi_k = -D_k^dagger / 2 in the layout of the kernels.  The next call has to be a forward evaluation.
+int open_set_running_cost(grape_handle *h, const double *D, int d_per_traj, double lambda_b) {
+    OpenCtx *o = h->open;
+    HIPCHK(h, hipSetDevice(h->device));
+    (void)hipGetLastError();
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    const size_t K = (size_t)h->K, np2 = (size_t)h->NP * h->NP, m2 = 2 * np2, nn = (size_t)h->N * h->N;
+    h->have_forward = false;
+    o->have_bwd = false;
+    o->tg_state = OpenCtx::TG_NEW_COST;
+    o->hv_state = OpenCtx::HV_NEW_COST;
+    o->rc_set = false; o->rc_lambda = 0.0; o->rc_per_traj = 0;
+    if (!D || lambda_b == 0.0) return GRAPE_OK;
+    int rc;
+    if (!o->d_Xi && (rc = open_rc_alloc(h, &o->d_Xi, K * m2, "Xi of the running cost"))) return rc;   // (room for a D per trajectory)
+    if (!o->d_gb && (rc = open_rc_alloc(h, &o->d_gb, K * (size_t)(h->N_T + 1), "the g_b values of the running cost"))) return rc;
+    if ((rc = open_upload_wq(h))) return rc;
+    const size_t Kd = d_per_traj ? K : 1;
+    std::vector<double> buf(Kd * m2), tmp(m2);
+    for (size_t k = 0; k < Kd; ++k) {
+        open_to_planar(D + 2 * k * nn, h->N, h->NP, tmp.data());
+        double *x = buf.data() + k * m2;
+        open_planar_adjoint(tmp.data(), h->NP, x);
+        for (size_t e = 0; e < m2; ++e) x[e] *= -0.5;
+    }
+    HIPCHK(h, hipMemcpy(o->d_Xi, buf.data(), buf.size() * 8, hipMemcpyHostToDevice));
+    o->rc_set = true; o->rc_lambda = lambda_b; o->rc_per_traj = d_per_traj ? 1 : 0;
+    return GRAPE_OK;
+}
+
+// backward half with the caller's xi_k(t_n) ([K][N_T+1][N*N] column-major, n = 0 unused) in place of a built-in cost
+int open_backward_xi(grape_handle *h, const double f_total[2], const double *chi, const double *xi, double lambda_b, double *G) {
+    OpenCtx *o = h->open;
+    HIPCHK(h, hipSetDevice(h->device));
+    (void)hipGetLastError();
+    const size_t K = (size_t)h->K, np2 = (size_t)h->NP * h->NP, m2 = 2 * np2, nn = (size_t)h->N * h->N, per_k = (size_t)h->N_T + 1;
+    int rc;
+    if (!o->d_xi_user && (rc = open_rc_alloc(h, &o->d_xi_user, K * per_k * m2, "the caller's xi"))) return rc;
+    if (!o->d_wq && (rc = open_upload_wq(h))) return rc;
+    o->stage.resize(per_k * m2);
+    for (size_t k = 0; k < K; ++k) {   // (one trajectory at a time, as open_storage)
+        for (size_t n = 0; n < per_k; ++n) open_to_planar(xi + 2 * (k * per_k + n) * nn, h->N, h->NP, o->stage.data() + n * m2);
+        HIPCHK(h, hipMemcpy(o->d_xi_user + k * per_k * m2, o->stage.data(), per_k * m2 * 8, hipMemcpyHostToDevice));
+    }
+    o->stage.clear(); o->stage.shrink_to_fit();
+    return open_backward(h, f_total, chi, G, true, lambda_b);
+}
+
 }  // namespace
 
 extern "C" {
@@ -2053,7 +2169,8 @@ int grape_create_open(grape_handle **out, const grape_problem *p, const grape_li
         return GRAPE_ERR_INVALID;
     }
     if (p->prop_method != GRAPE_PROP_EXP) { g_create_error = "grape_create_open: prop_method must be GRAPE_PROP_EXP"; return GRAPE_ERR_INVALID; }
-    if (p->Dpen) { g_create_error = "grape_create_open: the state running cost (Dpen) is not supported on open-system handles"; return GRAPE_ERR_INVALID; }
+    if (p->Dpen) { g_create_error = "grape_create_open: the state running cost (Dpen) is not supported on open-system handles at create; "
+                                       "grape_open_set_running_cost installs g_b = Re tr(D rho) on the handle, grape_open_backward_xi takes a caller's xi"; return GRAPE_ERR_INVALID; }
     if (p->ndev > 1) {
         g_create_error = "grape_create_open: ndev > 1 is not supported (one open-system handle per GPU with K_total, through the split-phase calls)";
         return GRAPE_ERR_INVALID;
@@ -2173,6 +2290,7 @@ int grape_create_open(grape_handle **out, const grape_problem *p, const grape_li
     CCHK(open_alloc(o, &o->d_stats, 2 * ((size_t)K + (size_t)K * L)));
     CCHK(hipMemset(o->d_stats, 0, 2 * ((size_t)K + (size_t)K * L) * sizeof(unsigned long long)));
     o->out.assign(2 * (size_t)K + 8, 0.0);
+    o->tlist.assign(p->tlist, p->tlist + N_T + 1);
     *out = guard.release();
     return GRAPE_OK;
 }
@@ -3816,7 +3934,7 @@ GRAPE_BARRIER(h ? &h->err : &g_create_error)
 
 int grape_backward_xi(grape_handle *h, const double f_total[2], const double *chi, const double *xi, double lambda_b,
                       double *G) try {
-    if (h && h->open) return open_refuse(h, "grape_backward_xi (state running costs)");
+    if (h && h->open) return open_refuse(h, "grape_backward_xi (state running costs; grape_open_backward_xi and grape_open_set_running_cost are the calls for one)");
     if (!h || !xi || !G || (!chi && !f_total)) return GRAPE_ERR_INVALID;
     if (!h->have_forward) { h->err = "grape_backward_xi called before grape_forward"; return GRAPE_ERR_INVALID; }
     if (h->no_target && !chi) { h->err = "this handle has no target states (grape_problem.target == NULL): grape_backward_xi needs the caller's chi"; return GRAPE_ERR_INVALID; }
@@ -4344,6 +4462,8 @@ int grape_open_eval_batch(grape_handle *h, int P, const double *pulsevals, doubl
     if (!h->open) OPEN_OB_REFUSE("not an open-system handle (grape_create_open); use grape_eval_batch for a closed one");
     if (h->K != h->K_total) OPEN_OB_REFUSE("a split-phase shard (K < K_total) is out of scope: f of a set would need an all-reduce of its own");
     if (h->no_target) OPEN_OB_REFUSE("this handle has no target states (grape_problem.target == NULL): J_T and chi are the caller's, per pulse vector");
+    if (h->open->rc_set) OPEN_OB_REFUSE("a state running cost is set on this handle (grape_open_set_running_cost): the batched kernels do not "
+                                        "carry it; grape_eval_batch, the loop over grape_eval, does");
     return open_eval_batch(h, P, pulsevals, J, G, tau);
 }
 GRAPE_BARRIER(h ? &h->err : &g_create_error)
@@ -4351,6 +4471,26 @@ GRAPE_BARRIER(h ? &h->err : &g_create_error)
 int grape_get_open_batch_info(grape_handle *h, double *out, int n) try {
     if (!h || !out || !h->open) return GRAPE_ERR_INVALID;
     return copy_info(h->open->ob.info, 7, out, n);
+}
+GRAPE_BARRIER(h ? &h->err : &g_create_error)
+
+int grape_open_set_running_cost(grape_handle *h, const double *D, int d_per_traj, double lambda_b) try {
+    if (!h) { g_create_error = "grape_open_set_running_cost: h == NULL"; return GRAPE_ERR_INVALID; }
+    if (!h->open) OPEN_RC_REFUSE("grape_open_set_running_cost", "not an open-system handle (grape_create_open); a closed one takes Dpen and lambda_b at grape_create");
+    if (D && !std::isfinite(lambda_b)) OPEN_RC_REFUSE("grape_open_set_running_cost", "lambda_b is not finite");
+    return open_set_running_cost(h, D, d_per_traj, lambda_b);
+}
+GRAPE_BARRIER(h ? &h->err : &g_create_error)
+
+int grape_open_backward_xi(grape_handle *h, const double f_total[2], const double *chi, const double *xi, double lambda_b,
+                           double *G) try {
+    if (!h) { g_create_error = "grape_open_backward_xi: h == NULL"; return GRAPE_ERR_INVALID; }
+    if (!h->open) OPEN_RC_REFUSE("grape_open_backward_xi", "not an open-system handle (grape_create_open); grape_backward_xi is the call for a closed one");
+    if (!xi || !G) OPEN_RC_REFUSE("grape_open_backward_xi", "xi and G must not be NULL");
+    if (!chi && !f_total) OPEN_RC_REFUSE("grape_open_backward_xi", "f_total == NULL without a caller's chi");
+    if (!chi && h->no_target) OPEN_RC_REFUSE("grape_open_backward_xi", "this handle has no target states (grape_problem.target == NULL): the caller's chi is needed");
+    if (!h->have_forward) OPEN_RC_REFUSE("grape_open_backward_xi", "no forward half since grape_create_open, grape_set_tlist or grape_open_set_running_cost");
+    return open_backward_xi(h, chi ? nullptr : f_total, chi, xi, lambda_b, G);
 }
 GRAPE_BARRIER(h ? &h->err : &g_create_error)
 

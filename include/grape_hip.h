@@ -182,7 +182,8 @@ typedef struct {
  * cops == NULL with J > 0, diss == NULL, gradient_method != GRAPE_GRAD_GRADGEN, prop_method != GRAPE_PROP_EXP, Dpen != NULL,
  * ndev > 1; later (the handle stays usable) -- grape_get_propagator, grape_get_storage(which = 1), grape_backward_xi,
  * grape_get_time_gradient (the time gradient of an open handle is grape_open_time_gradient, below), grape_forward_device,
- * grape_backward_device. */
+ * grape_backward_device.  The state running cost of such a handle has entry points of its own: grape_open_set_running_cost and
+ * grape_open_backward_xi, below. */
 int grape_create_open(grape_handle **out, const grape_problem *problem, const grape_lindblad *diss);
 
 /*
@@ -494,6 +495,42 @@ int grape_open_eval_batch(grape_handle *h, int P, const double *pulsevals, doubl
  * forward sweeps, [5] of the backward sweeps (0 after a call without G), [6] (sub-)steps, each summed over all workgroups of
  * the call.  Returns the number of entries written (at most n); GRAPE_ERR_INVALID for a closed handle. */
 int grape_get_open_batch_info(grape_handle *h, double *out, int n);
+
+/* State running costs on open-system handles (grape_create_open; entry points only, the ABI version stays 7;
+ * csrc/grape_lindblad_rc.hip.h): J = J_T + lambda_b J_b with J_b = sum_k sum_{n=0}^{N_T} wq_n g_b(rho_k(t_n)) and the
+ * trapezoid weights wq of optimize.jl:727-750 on the current grid.  grape_create_open with Dpen and grape_backward_xi on an
+ * open handle stay the refusals they are.
+ *
+ * grape_open_set_running_cost installs the built-in family g_b(rho) = Re tr(D rho) -- the population of leakage levels for a
+ * projector D; <Psi|D|Psi> of the closed path for a pure rho -- or removes it (D == NULL or lambda_b == 0).
+ *   D: [N*N] shared (d_per_traj == 0) or [K][N*N], column-major complex, Hermitian in the intended use.  In the reference's
+ *   convention dg_b = -2 Re <<xi | d rho>> the family has the constant xi_k = -D_k^dagger / 2.
+ *   - The call waits for work in flight, uploads -D^dagger / 2 and (re)computes wq.  Like grape_set_tlist it makes the next call
+ *     a forward evaluation; it may be repeated, e.g. for a continuation in lambda_b.  grape_set_tlist recomputes wq.
+ *   - While a cost is set grape_eval, grape_forward, grape_backward, grape_backward_chi and grape_eval_batch (the loop over
+ *     grape_eval) include it: grape_get_sums[4] = sum_k J_b,k of this handle's trajectories, J of grape_eval is
+ *     J_T + lambda_b J_b, the backward half adds lambda_b wq_{N_T} xi_k(T) to chi_k(T) BEFORE the norm, the chi_min_norm guard and
+ *     the normalisation, and (lambda_b wq_n / ||chi_k(T)||) xi_k to chi_k(t_n) for 0 < n < N_T, once per interval.
+ *   - After removal every result is bit for bit what a handle that never had a cost gives: such a handle launches the
+ *     kernels it always did.
+ *   - Not carried, and refused with a message that names the running cost (the handle stays usable): grape_open_hvp and
+ *     grape_open_eval_batch while a cost is set; grape_open_time_gradient after a backward half that carried a cost of either
+ *     form (a later backward half without one makes it answer again).
+ *   - GRAPE_ERR_INVALID, the handle stays usable: h == NULL (message: grape_last_error(NULL)); a closed handle; D != NULL with a
+ *     non-finite lambda_b.  An allocation failure is GRAPE_ERR_HIP with a message that names the size. */
+int grape_open_set_running_cost(grape_handle *h, const double *D, int d_per_traj, double lambda_b);
+
+/* The backward half with the inhomogeneity of an ARBITRARY state running cost: the arguments of grape_backward_xi with matrices
+ * for states.  xi [K][N_T+1][N*N] column-major, xi_k(t_n) defined by dg_b = -2 Re <<xi | d rho>> and evaluated by the caller on
+ * grape_get_storage(0) (entry n = 0 is not read; g_b = -tr rho^2 has xi = rho);  chi NULL (the handle's functional with f_total)
+ * or [K][N*N], the caller's chi_k(T);  G [L*N_T] = the gradient of J_T + lambda_b J_b.  J_b itself stays the caller's.  The call
+ * overrides a built-in cost for this backward half.  The xi buffer on the device is allocated by the first call and freed by
+ * grape_destroy; xi is staged one trajectory at a time.
+ *   GRAPE_ERR_INVALID with a message that names the reason, the handle stays usable: h == NULL; a closed handle (use
+ *   grape_backward_xi); xi == NULL or G == NULL; chi == NULL with f_total == NULL or on a handle without targets; no forward half
+ *   since grape_create_open, grape_set_tlist or grape_open_set_running_cost. */
+int grape_open_backward_xi(grape_handle *h, const double f_total[2], const double *chi, const double *xi, double lambda_b,
+                           double *G);
 
 const char *grape_last_error(grape_handle *h); /* h may be NULL: error of the last failed create */
 int grape_abi_version(void);

@@ -588,4 +588,51 @@ function open_batch_info(h::Handle)
             terms_backward = Int(out[6]), steps = Int(out[7]))
 end
 
+"""
+    open_set_running_cost!(h, D, lambda_b)
+
+Install the state running cost `g_b(ρ) = Re tr(D ρ)` with weight `lambda_b` on a handle made by `create_open`
+(grape_open_set_running_cost), or remove it (`D === nothing` or `lambda_b == 0`).  `D`: one `d × d` matrix shared by all
+trajectories or a vector of `K` of them (a projector on leakage levels penalises their population during the pulse).  While
+the cost is set `fg!` returns `J_T + λ_b J_b` and its gradient, and `grape_get_sums[5]` holds `Σ_k J_b,k`; the next call has to
+be a forward evaluation.  `open_time_gradient!`, `open_hvp!` and `open_eval_batch!` refuse while the cost is in effect.
+"""
+function open_set_running_cost!(h::Handle, D::Union{Nothing,AbstractMatrix,AbstractVector{<:AbstractMatrix}}, lambda_b::Real)
+    if isnothing(D)
+        check(h, ccall((:grape_open_set_running_cost, libgrape), Cint, (Ptr{Cvoid}, Ptr{ComplexF64}, Cint, Cdouble), h.ptr, C_NULL, 0, 0.0))
+        return h
+    end
+    per_traj = D isa AbstractVector
+    per_traj && length(D) != h.K && throw(DimensionMismatch("D must hold one matrix per trajectory ($(h.K))"))
+    Df = per_traj ? ComplexF64.(reduce(hcat, vec.(D))) : ComplexF64.(vec(D))
+    length(Df) == h.N * (per_traj ? h.K : 1) || throw(DimensionMismatch("every D must be d × d with d^2 = $(h.N)"))
+    check(h, GC.@preserve Df ccall((:grape_open_set_running_cost, libgrape), Cint, (Ptr{Cvoid}, Ptr{ComplexF64}, Cint, Cdouble),
+        h.ptr, Df, per_traj ? 1 : 0, Float64(lambda_b)))
+    return h
+end
+
+"""
+    open_backward_xi!(G, h, xi, lambda_b; f_total = nothing, chi = nothing)
+
+The backward half with the inhomogeneity of an arbitrary state running cost on a handle made by `create_open`
+(grape_open_backward_xi): `xi` is `d^2 × (N_T+1) × K` (column `[:, n+1, k]` is `vec(ξ_k(t_n))`, defined by
+`dg_b = -2 Re⟨⟨ξ|dρ⟩⟩` and evaluated by the caller on the stored states; `n = 0` is not read), `chi` is `nothing` (the
+handle's functional with `f_total = Σ_k w_k τ_k`) or `d^2 × K`, the caller's `χ_k(T)`.  `G` receives the gradient of
+`J_T + λ_b J_b`; `J_b` itself stays the caller's.  A function of its own: the library refuses `grape_backward_xi` on such a
+handle (and this call on a closed one) with a message.
+"""
+function open_backward_xi!(G::Vector{Float64}, h::Handle, xi::Array{ComplexF64,3}, lambda_b::Real;
+                           f_total::Union{Nothing,Complex} = nothing, chi::Union{Nothing,Matrix{ComplexF64}} = nothing)
+    size(xi) == (h.N, h.N_T + 1, h.K) || throw(DimensionMismatch("xi must be d^2 × (N_T+1) × K = $(h.N) × $(h.N_T + 1) × $(h.K)"))
+    length(G) == h.L * h.N_T || throw(DimensionMismatch("G must have L*N_T = $(h.L * h.N_T) entries"))
+    isnothing(chi) || size(chi) == (h.N, h.K) || throw(DimensionMismatch("chi must be d^2 × K"))
+    isnothing(chi) && isnothing(f_total) && error("GrapeHIP.open_backward_xi!: either f_total or chi")
+    f = isnothing(f_total) ? Float64[0.0, 0.0] : Float64[real(f_total), imag(f_total)]
+    cp = isnothing(chi) ? Ptr{ComplexF64}(C_NULL) : pointer(chi)
+    check(h, GC.@preserve G xi f chi ccall((:grape_open_backward_xi, libgrape), Cint,
+        (Ptr{Cvoid}, Ptr{Float64}, Ptr{ComplexF64}, Ptr{ComplexF64}, Cdouble, Ptr{Float64}),
+        h.ptr, f, cp, xi, Float64(lambda_b), G))
+    return G
+end
+
 end # module
