@@ -64,6 +64,7 @@ import sys
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from gcn import Prog, Reg, V, A, S, VCC, EXEC, Neg, Abs, kernel_text  # noqa: E402
+from gcn import HZ_MFMA_TO_VALU as gcn_wait_valu, HZ_MFMA_TO_MEM as gcn_wait_mem  # noqa: E402
 
 NT = 4
 NP = 64
@@ -82,6 +83,9 @@ XS0 = RED + 16 * 8
 XS1 = XS0 + 1024
 LDS_BYTES = XS1 + 1024
 KERNARG = 136
+# splan[cell] (t16_plan_kernel): bits 0..7 the planned squarings, bit 8 the cell's spectrum was certified before the launch
+SQ_MASK = 0xFF
+CERT_BIT = 0x100
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -498,7 +502,8 @@ class Gen:
         p.salu("s_add_u32", self.s_hb.sub(0), self.s_H0.sub(0), t0)
         p.salu("s_addc_u32", self.s_hb.sub(1), self.s_H0.sub(1), t1)
         # the cell exponentiates A / 2^s: dt / 2^s (exact: the exponent field)
-        p.salu("s_lshl_b32", t0, self.s_snext, 20)
+        p.salu("s_and_b32", t0, self.s_snext, SQ_MASK)
+        p.salu("s_lshl_b32", t0, t0, 20)
         p.salu("s_sub_u32", self.s_dt.sub(1), self.s_dt.sub(1), t0)
 
     def cell_bases(self, kc, n, cell):
@@ -866,6 +871,17 @@ class Gen:
             vp.free(t)
         self.cell_bases_finish(self.s_nkc)
         self.stamp(3)
+        # A cell the plan certified from the trace tables of its generator class (t16_plan_kernel: the same inequality with a
+        # wider margin, decided from the pulse values before the launch) forms y0 and takes the barrier, nothing else: no
+        # sums, no reductions, no LDS round trip, no verdict store -- verdict[cell] = 0 was written by the plan.  Scalar
+        # branches on the bit, like the one around the walk's mat-vec; every other cell runs the list below as before.
+        # (The one matrix instruction of the bound stays on both paths: the executed-work counter books 120 + 3 * 192 + 1 per cell
+        # and wave for this kernel and the suite pins that figure, in the list and on the device.  The certified cell passes
+        # through it with whatever its operand registers hold and drops the result: 64 of the ~1300 cycles the path saves.)
+        uid = len(p.ins)
+        L_cert, L_cert2, L_ones, L_vdone = f"L_cert_{uid}", f"L_cert2_{uid}", f"L_ones_{uid}", f"L_vdone_{uid}"
+        p.salu("s_and_b32", self.s_tmp[0], self.s_scur, CERT_BIT)
+        p.s_branch("s_cbranch_scc1", L_cert)
         # ---- y0 in place (p1 <- re, p3 <- im), sums for the spectral bound ----
         facc, gacc, cacc = vp.alloc(), vp.alloc(), vp.alloc()        # f0..f3, g0..g3, column sums (4 streams)
         for acc in (facc, gacc, cacc):
@@ -901,7 +917,10 @@ class Gen:
         lo, hi = dbits(1.0)
         p.valu("v_mov_b32", ones.sub(0), lo)
         p.valu("v_mov_b32", ones.sub(1), hi)
+        p.label(L_ones)
         p.mfma(ct, ones, cs, 0)
+        p.salu("s_and_b32", self.s_tmp[0], self.s_scur, CERT_BIT)
+        p.s_branch("s_cbranch_scc1", L_cert2)
         tmp = cacc.d(2)
         self.wave_reduce(f, tmp, "v_add_f64")
         self.wave_reduce(g_, tmp, "v_add_f64")
@@ -976,6 +995,20 @@ class Gen:
         p.salu("s_mov_b64", EXEC, self.s_save)
         for t in (vtf, vtg, vt2, vz):
             vp.free(t)
+        p.s_branch("s_branch", L_vdone)
+        p.label(L_cert)
+        # (the hazard tracker of gcn.py follows the list, not the jumps: the wait states between the matrix instructions on
+        # either side of this path and the vector instructions next to them are padded by hand -- 12 behind the last product's
+        # results, 19 behind the matrix instruction of the bound before anything may touch its result registers)
+        p.nop(gcn_wait_valu)
+        in_place_y(range(4))                            # (the same three subtractions per element, in the same order)
+        p.s_branch("s_branch", L_ones)
+        p.label(L_cert2)
+        p.nop(gcn_wait_mem)
+        p.s_waitcnt(lgkm=0)
+        p.s_barrier()                                   # everybody is done reading the planes
+        p.salu("s_and_b32", self.s_prop, self.s_prop, 1)                 # the verdict is "ok": bit 1 stays clear
+        p.label(L_vdone)
         # ================= y1 = (y0 + c3 A2 + c4 A)(y0 + c5 A2) + c6 y0 + c7 A2 ======================================
         # planes <- y0 + c3 A2 + c4 A; right operand y0 + c5 A2; start values c6 y0 + c7 A2; A2 parked in the accumulation half
         self.A2p_re, self.A2p_im = ap.alloc(4), ap.alloc(4)
@@ -1122,7 +1155,7 @@ class Gen:
         Un = vp.alloc(8, at=self.UT)
         uid = len(p.ins)
         L_sq, L_sq_loop, L_res = f"L_sq_{uid}", f"L_sq_loop_{uid}", f"L_res_{uid}"
-        p.s_cmp("s_cmp_lg_u32", self.s_scur, 0)
+        p.salu("s_and_b32", self.s_tmp[0], self.s_scur, SQ_MASK)         # (scc: squarings are planned)
         p.s_branch("s_cbranch_scc1", L_sq)
         streams = []
         for sl in range(4):
@@ -1143,7 +1176,7 @@ class Gen:
         vp.free(Un)                                     # (generator bookkeeping: on this path the result tiles are taken at the end)
         in_place_y(range(4))
         p.s_barrier()                                   # everybody is done reading the planes
-        p.salu("s_mov_b32", self.s_sqc, self.s_scur)
+        p.salu("s_and_b32", self.s_sqc, self.s_scur, SQ_MASK)
         p.label(L_sq_loop)
         Q2 = [[vp.alloc() for _ in range(3)] for _ in range(4)]
 

@@ -21,6 +21,7 @@
 #include "grape_lindblad_batch.hip.h"
 #include "grape_lindblad_rc.hip.h"
 #include "grape_devmem.h"
+#include "grape_cert.hip.h"
 
 #include <rccl/rccl.h>
 #include <dlfcn.h>
@@ -136,6 +137,12 @@ struct grape_handle {
     bool t16 = true;
     double *d_gram = nullptr;           // [KC][(L + 1)^2] Re tr(O_a^dagger O_b), O = (H0_k, H_1 .. H_L) of every generator class
     int *d_celllist = nullptr;          // [KC * N_T] the listed cells (counter: d_flags[4])
+    // trace tables of the generator classes (grape_cert.hip.h): tr H^8 | tr H^6 as polynomials in the pulse values.  The plan
+    // certifies from them, before the launch, the cells whose spectrum is inside the range of the four products; such a cell
+    // skips the in-cell bound (asm/gen_t16.py).  Assembly route, 1 <= L <= 4; GRAPE_EXPM_CERT=0: no tables, every cell decides itself
+    double *d_cert = nullptr;           // [KC][cert_n8 + cert_n6] coefficients
+    int *d_cert_exp = nullptr;          // [cert_n8 + cert_n6] exponents of e_1 .. e_L of every coefficient, 4 bits each
+    int cert_n8 = 0, cert_n6 = 0;
     // the four-product route as hand-allocated assembly (asm/gen_t16.py; GRAPE_EXPM_ASM=0: the C++ kernel): four tiles
     // per side, Hermitian generators, controls shared by the trajectories
     bool asm16 = false;
@@ -148,7 +155,7 @@ struct grape_handle {
     // trajectory along while the cell's result is in registers -- Psi upwards from t = 0, conj(chi~) downwards from t = T
     // (d_xinit: the two start vectors of every trajectory) -- and report how far each end got (d_prog[2][K]); the sweep
     // kernel behind picks up from there.  GRAPE_EXPM_WALK=0: the kernel only exponentiates (A/B timing, parity twin).
-    int *d_wgtab = nullptr, *d_prog = nullptr, *d_splan = nullptr;   // d_splan: squarings planned per cell (scaling and squaring around the four products)
+    int *d_wgtab = nullptr, *d_prog = nullptr, *d_splan = nullptr;   // d_splan: plan word per cell: squarings (scaling and squaring around the four products) | certified bit
     double2 *d_xinit = nullptr;
     int asm_blocks = 0;
     int last_walk_fuse = 0;      // which ends the walks of the LAST evaluation carried (grape_get_work[17] counts their steps from d_prog)
@@ -2994,6 +3001,40 @@ int grape_create(grape_handle **out, const grape_problem *p) try {
         });
         CCHK(h->mem.alloc(&h->d_gram, gram.size()));
         CCHK(hipMemcpy(h->d_gram, gram.data(), gram.size() * 8, hipMemcpyHostToDevice));
+        // ... and the trace tables of the same operators (grape_cert.hip.h; like the Gram matrices they do not depend on dt)
+        const char *envc = getenv("GRAPE_EXPM_CERT");
+        if (h->asm16 && L >= 1 && L <= GRAPE_CERT_LMAX && !(envc && atoi(envc) == 0)) {
+            const CertPlan pl(L);
+            const int nt = pl.n8 + pl.n6;
+            h->cert_n8 = pl.n8; h->cert_n6 = pl.n6;
+            CCHK(h->mem.alloc(&h->d_cert, (size_t)KCn * nt));
+            CCHK(h->mem.alloc(&h->d_cert_exp, (size_t)nt));
+            CCHK(hipMemcpy(h->d_cert_exp, pl.exps.data(), (size_t)nt * sizeof(int), hipMemcpyHostToDevice));
+            DeviceBufs tmp;   // (scratch of the build: released when it is done)
+            int *d_job[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+            const std::vector<int> *job[6] = {&pl.mm2.row, &pl.mm2.pair, &pl.mm34.row, &pl.mm34.pair, &pl.tr.row, &pl.tr.pair};
+            for (int i = 0; i < 6; ++i) {
+                CCHK(tmp.alloc(&d_job[i], job[i]->size()));
+                CCHK(hipMemcpy(d_job[i], job[i]->data(), job[i]->size() * sizeof(int), hipMemcpyHostToDevice));
+            }
+            // classes per pass: 64 MB of coefficient matrices at a time
+            const size_t per_class = (size_t)pl.nmat * N * N;
+            const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)KCn, ((size_t)64 << 20) / (per_class * sizeof(double2))));
+            double2 *d_scr = nullptr;
+            CCHK(tmp.alloc(&d_scr, per_class * chunk));
+            for (int kc0 = 0; kc0 < KCn; kc0 += chunk) {
+                const unsigned nc = (unsigned)std::min(chunk, KCn - kc0);
+                hipLaunchKernelGGL(cert_load_kernel, dim3((unsigned)pl.M, nc), dim3(256), 0, 0, (const double *)h->d_H0f, (const double *)h->d_Hcf,
+                                   (const int *)h->d_rep, kc0, p->hc_per_traj ? 1 : 0, L, N, NP, pl.nmat, d_scr);
+                hipLaunchKernelGGL(cert_mm_kernel, dim3((unsigned)pl.n2, nc), dim3(256), 0, 0, d_scr, pl.nmat, N, pl.M, (const int *)d_job[0], (const int *)d_job[1]);
+                hipLaunchKernelGGL(cert_mm_kernel, dim3((unsigned)(pl.n3 + pl.n4), nc), dim3(256), 0, 0, d_scr, pl.nmat, N, pl.M + pl.n2, (const int *)d_job[2],
+                                   (const int *)d_job[3]);
+                hipLaunchKernelGGL(cert_trace_kernel, dim3((unsigned)nt, nc), dim3(256), 0, 0, (const double2 *)d_scr, pl.nmat, N, (const int *)d_job[4],
+                                   (const int *)d_job[5], nt, h->d_cert + (size_t)kc0 * nt);
+                CCHK(hipGetLastError());
+            }
+            CCHK(hipDeviceSynchronize());
+        }
     }
     if (h->large && h->series) {
         // cooperative polynomial sweeps (grape_cheby.hip.h): S = NP / 16 siblings per trajectory on one XCD, at most one
@@ -3139,7 +3180,10 @@ int grape_forward_device(grape_handle *h, const double *d_pulsevals, double *d_o
                     T16PlanArgs pa{};
                     pa.gram = h->d_gram; pa.eps = h->d_eps; pa.shape = h->d_shape; pa.dts = h->d_dts; pa.flags = h->d_flags;
                     pa.KC = h->KC; pa.L = h->L; pa.N_T = h->N_T; pa.N = h->N;
-                    pa.splan = (h->asm16 && h->asm_sq) ? h->d_splan : nullptr;
+                    pa.splan = (h->asm16 && (h->asm_sq || h->d_cert)) ? h->d_splan : nullptr;
+                    pa.sq_on = h->asm_sq ? 1 : 0;
+                    pa.cert = h->d_cert; pa.cert_exp = h->d_cert_exp; pa.n8 = h->cert_n8; pa.n6 = h->cert_n6;
+                    pa.verdict = h->d_cellflag;
                     hipLaunchKernelGGL(t16_plan_kernel, dim3((unsigned)((ncell + 255) / 256)), dim3(256), 0, s, pa);
                     HIPCHK(h, hipGetLastError());
                 }
@@ -4283,10 +4327,10 @@ int grape_get_work(grape_handle *h, double *out, int n) try {
     if (!h || !out || n < 4) return GRAPE_ERR_INVALID;
     if (h->open) return open_work(h, out, n);
     if (!h->shards.empty()) {   // every entry is a count: the shards add up
-        const int m = n < 19 ? n : 19;
+        const int m = n < 20 ? n : 20;
         std::fill(out, out + m, 0.0);
         for (grape_handle *c : h->shards) {
-            double cw[19] = {0.};
+            double cw[20] = {0.};
             const int rc = grape_get_work(c, cw, m);
             if (rc < 0) return multi_fail(h, c, rc);
             for (int i = 0; i < m; ++i) out[i] = (i == 15 || i == 16 || i == 18) ? cw[i] : out[i] + cw[i];   // ([15], [16]: kernel ids, the same in every shard)
@@ -4362,7 +4406,38 @@ int grape_get_work(grape_handle *h, double *out, int n) try {
         out[17] = carried;
     }
     if (n > 18) out[18] = h->scan16 ? (double)h->scan_Bk : 0.0;   // block length of the scanned sweeps (N <= 16), 0: sequential sweeps
+    // cells of the last evaluation whose spectrum was certified before the launch (trace tables, t16_plan_kernel): the bits are
+    // still in the plan; an evaluation whose plan skipped the four-product route used none of them
+    if (n > 19) {
+        double certified = 0.0;
+        if (h->d_cert && h->d_splan && !h->series) {
+            const size_t ncell = (size_t)h->KC * h->N_T;
+            std::vector<int> plan(ncell);
+            int fl[8];
+            HIPCHK(h, hipMemcpy(plan.data(), h->d_splan, ncell * sizeof(int), hipMemcpyDeviceToHost));
+            HIPCHK(h, hipMemcpy(fl, h->d_flags, sizeof(fl), hipMemcpyDeviceToHost));
+            if (!(4L * fl[6] > (long)ncell))
+                for (int w : plan) certified += (w & T16_PLAN_CERT) ? 1.0 : 0.0;
+        }
+        out[19] = certified;
+    }
     return 4;
+}
+GRAPE_BARRIER(h ? &h->err : &g_create_error)
+
+int grape_get_cert_table(grape_handle *h, int *dims, double *coef, int *exps) try {
+    if (!h || !dims) return GRAPE_ERR_INVALID;
+    if (h->open || !h->shards.empty()) {
+        h->err = "grape_get_cert_table: a closed handle on one device";
+        return GRAPE_ERR_INVALID;
+    }
+    const int nt = h->cert_n8 + h->cert_n6;
+    dims[0] = h->KC; dims[1] = h->cert_n8; dims[2] = h->cert_n6;
+    if (!h->d_cert || !nt) { dims[1] = dims[2] = 0; return GRAPE_OK; }
+    HIPCHK(h, hipSetDevice(h->device));
+    if (coef) HIPCHK(h, hipMemcpy(coef, h->d_cert, (size_t)h->KC * nt * sizeof(double), hipMemcpyDeviceToHost));
+    if (exps) HIPCHK(h, hipMemcpy(exps, h->d_cert_exp, (size_t)nt * sizeof(int), hipMemcpyDeviceToHost));
+    return GRAPE_OK;
 }
 GRAPE_BARRIER(h ? &h->err : &g_create_error)
 

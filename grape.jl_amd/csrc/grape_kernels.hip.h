@@ -13,6 +13,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "grape_t18_coeffs.h"   // T16_THETA (t16_certified)
+
 typedef double d4 __attribute__((ext_vector_type(4)));
 
 #define MFMA64(a, b, c) __builtin_amdgcn_mfma_f64_16x16x4f64((a), (b), (c), 0, 0, 0)
@@ -108,7 +110,43 @@ struct T16PlanArgs {
     int *flags;
     int KC, L, N_T, N;
     int *splan;           // nullptr or [KC * N_T]: squarings planned for every cell (0 where the cell is left to its own bound)
+    int sq_on;            // 0: no squarings are planned (GRAPE_EXPM_SQ=0), the plan words carry the certified bit only
+    // the certificate (trace tables of grape_create, see t16_certified): nullptr / 0 on handles without tables
+    const double *cert;   // [KC][n8 + n6]
+    const int *cert_exp;  // [n8 + n6]
+    int n8, n6;
+    int *verdict;         // [KC * N_T]: 0 is written for a certified cell, which does not write it itself
 };
+// splan[cell]: bits 0..7 the planned squarings, bit 8 the cell's spectrum was certified before the launch
+#define T16_PLAN_SQ_MASK 0xFF
+#define T16_PLAN_CERT 0x100
+// Is the spectrum of A / 2^s, A = -i dt (H0 + sum_l e_l C_l), certainly inside the range of the four products?  The cell
+// itself (asm/gen_t16.py) tests m8 (1 + 1e-9) <= theta^8 and m6 >= 0 on m8 = dt^8 tr H^8 / 2^(8s), m6 = dt^6 tr H^6 / 2^(6s)
+// taken from its products, or the 1-norm of A^2.  tr H^8 and tr H^6 are polynomials in e with the coefficients t8 | t6 of
+// the generator class; here they are evaluated as p8, p6 together with S8 = sum |t8[al]| |e^al|, which bounds everything
+// rounding can do to p8 (the table agrees with the moments of the eigenvalues to 1e-14 relative, the sum of 45 terms
+// adds 1e-15 S8: 2^-30 S8 is five orders above both), and the test is
+//     (p8 + 2^-30 S8) dt^8 (1 + 1e-6) <= (theta 2^s)^8   and   p6 >= 0            (NaN fails)
+// -- the cell's own inequality with a margin a thousand times its own, so a cell certified here is one the cell would
+// have passed: the results are the same bits with and without the certificate.  Cells only the 1-norm would pass are left to
+// the cell.
+__device__ __forceinline__ bool t16_certified(const double *t, const int *ex, const int n8, const int n6, const int L, const double *e,
+                                              const double dt, const int sq) {
+    double p[2] = {0., 0.}, S8 = 0.;
+    for (int i = 0; i < n8 + n6; ++i) {
+        unsigned x = (unsigned)ex[i];
+        double mono = 1.0;
+        for (int l = 0; l < L; ++l, x >>= 4)
+            for (unsigned q = x & 15u; q > 0; --q) mono *= e[l];
+        const double c = t[i];
+        p[i < n8 ? 0 : 1] += c * mono;
+        if (i < n8) S8 += fabs(c) * fabs(mono);
+    }
+    const double dt2 = dt * dt, dt8 = (dt2 * dt2) * (dt2 * dt2);
+    constexpr double th2 = T16_THETA * T16_THETA, th8 = (th2 * th2) * (th2 * th2);
+    const double lhs = (p[0] + 0x1p-30 * S8) * dt8 * (1.0 + 1e-6), rhs = ldexp(th8, 8 * sq);
+    return lhs <= rhs && p[1] >= 0.0;
+}
 __global__ void __launch_bounds__(256) t16_plan_kernel(T16PlanArgs a) {
     const int cell = blockIdx.x * 256 + threadIdx.x;
     bool out = false;
@@ -129,13 +167,17 @@ __global__ void __launch_bounds__(256) t16_plan_kernel(T16PlanArgs a) {
         out = !(r <= T16_PLAN_R);
         if (a.splan) {
             int sq = 0;
-            if (out) {
+            if (out && a.sq_on) {
                 double rs = r;
                 while (sq < T16_PLAN_SMAX && !(rs <= T16_PLAN_RS)) { rs *= 0.5; ++sq; }
                 out = !(rs <= T16_PLAN_RS);      // (NaN included)
                 if (out) sq = 0;
             }
-            a.splan[cell] = sq;
+            // the certificate of the cell as it will be exponentiated (A / 2^sq); the estimate above keeps its two roles, the
+            // squaring plan and the "more than a quarter out of range" rule
+            const bool cert = a.cert && t16_certified(a.cert + (size_t)kc * (a.n8 + a.n6), a.cert_exp, a.n8, a.n6, a.L, e + 1, dt, sq);
+            if (cert) a.verdict[cell] = 0;
+            a.splan[cell] = sq | (cert ? T16_PLAN_CERT : 0);
         }
     }
     const unsigned long long m = __ballot(out);
@@ -3452,7 +3494,7 @@ __global__ void deriv_econ_kernel(DerivEconArgs a) {
         int d;
         if (a.cell_deg) d = a.cell_deg[cell];
         else {
-            const int sq = a.splan ? a.splan[cell] : 0;    // (the compiled four-product kernel plans no squarings)
+            const int sq = a.splan ? (a.splan[cell] & T16_PLAN_SQ_MASK) : 0;    // (the compiled four-product kernel plans no squarings)
             d = a.verdict[cell] != 0 ? 0 : sq == 0 ? a.deg0 : sq == 1 ? a.deg1 : 0;
         }
         ok = d > 0;

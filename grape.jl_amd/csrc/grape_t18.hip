@@ -120,7 +120,7 @@ struct T16AsmArgs {           // kernel argument block of expm_t16_asm (gen_t16.
     double2 *fw, *bw;           // [K][N_T + 1][64] stored states
     int *prog;                  // [2][K] steps each end of each trajectory was propagated by the walks
     int K, s_per_cell;          // s_per_cell: Sf is [KC][N_T] (control operators per trajectory) instead of [N_T]
-    const int *splan;           // [KC * N_T] squarings planned per cell (t16_plan_kernel): the cell exponentiates A / 2^s
+    const int *splan;           // [KC * N_T] plan words (t16_plan_kernel): bits 0..7 squarings s, the cell exponentiates A / 2^s; bit 8 certified before the launch
 };
 static_assert(sizeof(T16AsmArgs) == 136, "argument block of the assembly kernel");
 
@@ -166,7 +166,7 @@ __global__ void __launch_bounds__(256) t16_post_kernel(ExpmArgs a, const int *ve
     if (valid && !ok) a.cell_list[atomicAdd(&a.flags[4], 1)] = cell;   // to be redone by the five-product launch
     const unsigned long long m_ok = __ballot(ok), m_valid = __ballot(valid);
     {   // the squarings the kernel executed (whatever the verdict): 192 matrix instructions per wave each
-        unsigned long long sq = valid ? (unsigned long long)splan[cell] : 0ull;
+        unsigned long long sq = valid ? (unsigned long long)(splan[cell] & T16_PLAN_SQ_MASK) : 0ull;
         unsigned long long sq_ok = ok ? sq : 0ull;
         for (int off = 32; off >= 1; off >>= 1) { sq += __shfl_xor(sq, off, 64); sq_ok += __shfl_xor(sq_ok, off, 64); }
         if (lane == 0 && sq) stat_add(a.stats, 12, sq * 4ull * 192ull);
@@ -174,6 +174,7 @@ __global__ void __launch_bounds__(256) t16_post_kernel(ExpmArgs a, const int *ve
     }
     if (lane == 0 && m_valid) {
         // executed matrix instructions of the assembly kernel: four waves x (120 + 3 * 192 + 1 for the column sums) per cell
+        // (a cell certified before the launch still issues that one instruction: gen_t16.py, "certified")
         stat_add(a.stats, 12, (unsigned long long)__popcll(m_valid) * 4ull * (unsigned long long)(T16Count<4>::CELL + 1));
         if (m_ok) {
             stat_add(a.stats, 14, (unsigned long long)__popcll(m_ok));

@@ -307,8 +307,20 @@ int grape_reset_timings(grape_handle *h);
  * [17] the steps of the two sweeps that the walks of the exponential kernel carried in the last evaluation (the sweep
  * launch did the remaining 2 K N_T - [17]), [18] the block length of the scanned sweeps of N <= 16 (round 6: the time axis is
  * cut into blocks whose propagators are formed first; 0: sequential sweeps; GRAPE_SCAN16=0 / 1 forces)
+ * [19] the cells of the last evaluation whose spectrum was certified before the launch of the four-product assembly kernel:
+ * tr H^8 and tr H^6 of H = H0_k + sum_l e_l C_l are polynomials in the pulse values whose coefficients grape_create tabulates
+ * per generator class (Hermitian generators, 1 <= L <= 4, assembly route); the plan of an evaluation tests
+ * (p8 + 2^-30 S8) dt^8 (1 + 1e-6) <= (1.36 * 2^s)^8 and p6 >= 0 on them and a cell that passes skips the spectral bound it
+ * would otherwise compute from its own products -- the same inequality with a narrower margin, so the results are the same
+ * bits.  0 on handles without tables, with GRAPE_EXPM_CERT=0, and when the plan skipped the route
  * (entries beyond n are not written). */
 int grape_get_work(grape_handle *h, double *out, int n);
+
+/* The trace tables behind grape_get_work[19] (diagnostics, tests).  dims [3] = KC, n8, n6: generator classes, coefficients of
+ * tr H^8 and of tr H^6 (45 and 28 at L = 2; both 0: this handle has no tables).  coef (NULL: not wanted) [KC][n8 + n6]: t8 | t6
+ * of every class; exps (NULL: not wanted) [n8 + n6]: the exponents of e_1 .. e_L of the monomial a coefficient multiplies, four
+ * bits each, e_1 lowest (e_l = pulse value times shape).  GRAPE_ERR_INVALID: h or dims NULL, an open handle, several devices. */
+int grape_get_cert_table(grape_handle *h, int *dims, double *coef, int *exps);
 
 /* ABI v7.  Derivative of J with respect to the time steps dt_n = tlist[n+1] - tlist[n] (0-based n < N_T), for the duration
  * loop around GRAPE (INTEGRATION.md "Optimising the duration").  For piecewise-constant generators dU_n/d(dt_n) = -i H_n U_n:
