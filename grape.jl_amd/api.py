@@ -35,7 +35,8 @@ EXPORTS = ["grape_create", "grape_destroy", "grape_eval", "grape_forward", "grap
            "grape_get_final_states", "grape_backward_chi",
            "grape_get_time_gradient", "grape_set_tlist", "grape_eval_batch", "grape_get_batch_info", "grape_create_open",
            "grape_hvp", "grape_get_hvp_info", "grape_open_time_gradient", "grape_open_hvp", "grape_get_open_hvp_info",
-           "grape_open_eval_batch", "grape_get_open_batch_info", "grape_open_set_running_cost", "grape_open_backward_xi"]
+           "grape_open_eval_batch", "grape_get_open_batch_info", "grape_open_set_running_cost", "grape_open_backward_xi",
+           "grape_hvp_forward", "grape_hvp_backward", "grape_hvp_backward_chi"]
 
 
 class GrapeHipError(RuntimeError):
@@ -103,7 +104,7 @@ def build_asm(verbose: bool = False, workdir: str | None = None) -> str:
 def _sources():
     srcs = [os.path.join(_CSRC, f) for f in ("grape_hip.hip", "grape_t18.hip", "grape_kernels.hip.h", "grape_large.hip.h",
                                              "grape_series.hip.h", "grape_cheby.hip.h", "grape_t18.hip.h", "grape_t18_coeffs.h",
-                                             "grape_deriv3.hip.h", "grape_timegrad.hip.h", "grape_batch.hip.h", "grape_lindblad.hip.h", "grape_lindblad_tg.hip.h", "grape_hvp.hip.h", "grape_lindblad_hvp.hip.h", "grape_lindblad_batch.hip.h", "grape_lindblad_rc.hip.h", "grape_devmem.h", "grape_cert.hip.h", os.path.join("asm", "gen_t16.py"), os.path.join("asm", "gen_t16p.py"), os.path.join("asm", "gen_t18g.py"), os.path.join("asm", "gen_t18gp.py"), os.path.join("asm", "gen_d3.py"), os.path.join("asm", "gen_d3s.py"), os.path.join("asm", "gen_lg.py"), os.path.join("asm", "gen_d4.py"), os.path.join("asm", "gcn.py"))]
+                                             "grape_deriv3.hip.h", "grape_timegrad.hip.h", "grape_batch.hip.h", "grape_lindblad.hip.h", "grape_lindblad_tg.hip.h", "grape_hvp.hip.h", "grape_hvp_split.hip.h", "grape_lindblad_hvp.hip.h", "grape_lindblad_batch.hip.h", "grape_lindblad_rc.hip.h", "grape_devmem.h", "grape_cert.hip.h", os.path.join("asm", "gen_t16.py"), os.path.join("asm", "gen_t16p.py"), os.path.join("asm", "gen_t18g.py"), os.path.join("asm", "gen_t18gp.py"), os.path.join("asm", "gen_d3.py"), os.path.join("asm", "gen_d3s.py"), os.path.join("asm", "gen_lg.py"), os.path.join("asm", "gen_d4.py"), os.path.join("asm", "gcn.py"))]
     return srcs, os.path.join(_HERE, "..", "include", "grape_hip.h")
 
 
@@ -217,6 +218,9 @@ def load_library():
     lib.grape_get_batch_info.argtypes = [vp, vp, ip]
     lib.grape_hvp.argtypes = [vp, ip, vp, vp]
     lib.grape_get_hvp_info.argtypes = [vp, vp, ip]
+    lib.grape_hvp_forward.argtypes = [vp, ip, vp, vp, vp, vp]
+    lib.grape_hvp_backward.argtypes = [vp, ip, vp, vp, vp]
+    lib.grape_hvp_backward_chi.argtypes = [vp, ip, vp, vp, vp]
     lib.grape_open_hvp.argtypes = [vp, ip, vp, vp]
     lib.grape_get_open_hvp_info.argtypes = [vp, vp, ip]
     lib.grape_open_eval_batch.argtypes = [vp, ip, vp, vp, vp, vp]
@@ -460,6 +464,59 @@ class GrapeHip:
         self._lib.grape_get_hvp_info(self._h, out.ctypes.data, 7)
         return dict(series_terms=int(out[0]), series_steps=int(out[1]), dirs_per_group=int(out[2]), bytes=int(out[3]), ms=float(out[4]),
                     terms_forward=int(out[5]), terms_backward=int(out[6]))
+
+    def _hvp_dirs(self, V):
+        v = np.ascontiguousarray(V, dtype=np.float64)
+        LN = self.L * self.N_T
+        if v.ndim not in (1, 2) or v.shape[-1] != LN or v.size == 0:
+            raise ValueError(f"V must be [L*N_T] = [{LN}] or [nv, {LN}] with nv >= 1, got {v.shape}")
+        return v, (1 if v.ndim == 1 else v.shape[0])
+
+    def hvp_forward(self, V, final_states=False):
+        """First half of a split Hessian-vector product (grape_hvp_forward): the tangent forward sweep of ``V`` [nv, L*N_T]
+        at the pulses of the last evaluation.  Returns ``(dtau [nv, K], dsums [nv] complex)`` -- tau'_k and this handle's
+        sum_k w_k tau'_k, which a sharded caller all-reduces -- and with ``final_states=True`` also ``dpsiT [nv, K, N]``, the
+        derivative of Psi_k(T) along each direction.  A single direction given as a vector [L*N_T] returns them without the
+        leading axis.  All directions stay on the device for ``hvp_backward`` / ``hvp_backward_chi``."""
+        v, nv = self._hvp_dirs(V)
+        dtau = np.empty((nv, self.K), dtype=np.complex128)
+        dsums = np.empty(nv, dtype=np.complex128)
+        dpsi = np.empty((nv, self.K, self.N), dtype=np.complex128) if final_states else None
+        self._chk(self._lib.grape_hvp_forward(self._h, nv, v.ctypes.data, dtau.ctypes.data, dsums.ctypes.data,
+                                              dpsi.ctypes.data if final_states else None))
+        if v.ndim == 1:
+            dtau, dsums, dpsi = dtau[0], dsums[0], (dpsi[0] if final_states else None)
+        return (dtau, dsums, dpsi) if final_states else (dtau, dsums)
+
+    def hvp_backward(self, f_total, df_total):
+        """Second half for the built-in functional (grape_hvp_backward): ``f_total`` the all-reduced sum_k w_k tau_k (complex,
+        as for ``backward``), ``df_total`` [nv] complex the all-reduced ``dsums`` of ``hvp_forward`` (a scalar for a single
+        direction given as a vector).  Returns this handle's H v [nv, L*N_T] (or [L*N_T]): the partial sum over its
+        trajectories, the full product when K == K_total."""
+        one = np.ndim(df_total) == 0
+        df = np.ascontiguousarray(df_total, dtype=np.complex128)   # (at least one-dimensional)
+        if np.ndim(df_total) > 1 or df.size == 0:
+            raise ValueError(f"df_total must be a complex scalar or [nv] with nv >= 1, got {np.shape(df_total)}")
+        nv = df.size
+        out = np.empty((nv, self.L * self.N_T))
+        f = np.array([complex(f_total).real, complex(f_total).imag], dtype=np.float64)
+        self._chk(self._lib.grape_hvp_backward(self._h, nv, f.ctypes.data, df.ctypes.data, out.ctypes.data))
+        return out[0] if one else out
+
+    def hvp_backward_chi(self, chi, dchi):
+        """Second half for a caller's functional (grape_hvp_backward_chi): ``chi`` [K, N] as for ``backward_chi`` (not
+        normalised), ``dchi`` [nv, K, N] its derivative along each direction of the last ``hvp_forward`` ([K, N] for a single
+        direction given as a vector).  Returns this handle's H v [nv, L*N_T] (or [L*N_T])."""
+        chi = np.ascontiguousarray(chi, dtype=np.complex128)
+        d = np.ascontiguousarray(dchi, dtype=np.complex128)
+        if chi.shape != (self.K, self.N):
+            raise ValueError(f"chi must be [K, N] = [{self.K}, {self.N}], got {chi.shape}")
+        if d.ndim not in (2, 3) or d.shape[-2:] != (self.K, self.N) or d.size == 0:
+            raise ValueError(f"dchi must be [K, N] = [{self.K}, {self.N}] or [nv, {self.K}, {self.N}] with nv >= 1, got {d.shape}")
+        nv = 1 if d.ndim == 2 else d.shape[0]
+        out = np.empty((nv, self.L * self.N_T))
+        self._chk(self._lib.grape_hvp_backward_chi(self._h, nv, chi.ctypes.data, d.ctypes.data, out.ctypes.data))
+        return out[0] if d.ndim == 2 else out
 
     def set_tlist(self, tlist):
         """Replace the time grid of this handle (same N_T; grape_set_tlist).  A refused grid leaves the handle unchanged."""

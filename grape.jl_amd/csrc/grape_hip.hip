@@ -17,6 +17,7 @@
 #include "grape_lindblad.hip.h"
 #include "grape_lindblad_tg.hip.h"
 #include "grape_hvp.hip.h"
+#include "grape_hvp_split.hip.h"
 #include "grape_lindblad_hvp.hip.h"
 #include "grape_lindblad_batch.hip.h"
 #include "grape_lindblad_rc.hip.h"
@@ -319,6 +320,21 @@ struct grape_handle {
         unsigned long long *d_hvstats = nullptr;   // [4 cap K] statistics of the workgroups, then the flag word
         double info[7] = {0., 0., 0., 0., 0., 0., 0.};   // grape_get_hvp_info
     } hvp;
+    // grape_hvp_forward / grape_hvp_backward / grape_hvp_backward_chi (grape_hvp_split.hip.h): the two halves
+    // share the tangent storage above; what only they need lives here, allocated by the first split call, so that a handle
+    // which never makes one holds -- and reports -- what it held before.
+    struct HvpSplit {
+        enum { NONE = 0, READY, EVAL, TLIST, BATCH, HVP, FAILED };
+        DeviceBufs mem;
+        int cap = 0;               // directions the extras hold
+        double2 *d_chi = nullptr, *d_dchi = nullptr, *d_ztarget = nullptr;   // chi~ [K][NP] | chi~' [cap][K][NP] | zeros [K][N]
+        double2 *d_dpsiT = nullptr;                                          // Psi~'(T) [cap][K][N], packed for the host
+        double *d_ftot = nullptr, *d_dftot = nullptr, *d_psums = nullptr;     // f_total [2] | f'_total [cap][2] | partial sums [cap][2]
+        int state = NONE, nv = 0;  // what came since the last successful forward half, and its directions
+        double terms_fw = 0., steps_fw = 0.;
+        std::vector<double> stage; // host staging of chi~, chi~'
+        void came(int what) { if (state != NONE) state = what; }
+    } hvs;
     // grape_create_open (grape_lindblad.hip.h): the states are d x d density matrices under a Lindblad
     // generator.  Such a handle owns none of the buffers above: everything it holds hangs off this pointer, and the entry
     // points dispatch on it.
@@ -2135,7 +2151,7 @@ void grape_destroy(grape_handle *h) {
     }
     hipSetDevice(h->device);
     if (h->stream) hipStreamSynchronize(h->stream);
-    h->batch.store.release(); h->hvp.store.release(); h->mem.release();
+    h->batch.store.release(); h->hvp.store.release(); h->hvs.mem.release(); h->mem.release();
     for (auto &ring : h->ph)
         for (auto &p : ring) {
             if (p.e0) hipEventDestroy(p.e0);
@@ -3291,6 +3307,7 @@ int grape_forward_device(grape_handle *h, const double *d_pulsevals, double *d_o
 #endif
     h->last_walk_fuse = walk_fuse;
     h->tg_state = h->want_bw ? 2 : 1;
+    h->hvs.came(grape_handle::HvpSplit::EVAL);
     // ---- phase 1: forward sweep + tau ----
     SweepArgs sa{};
     sa.U = h->d_U; sa.cls = h->d_cls; sa.psi0 = h->d_psi0; sa.target = h->d_target; sa.weights = h->d_weights;
@@ -4093,6 +4110,7 @@ int grape_eval(grape_handle *h, const double *pulsevals, double *J, double *G, d
                 h->foreign_stream = false; h->have_forward = true; h->bw_done = false;
                 h->bw_unit = h->graph_bw_unit; h->z_valid = h->graph_z_valid; h->credit_pending = h->graph_credit;
                 h->tg_state = 3; h->tg_unit = h->graph_tg_unit; h->tg_xi_user = false;
+                h->hvs.came(grape_handle::HvpSplit::EVAL);
                 replayed = true;
             }
         }
@@ -4579,6 +4597,7 @@ int grape_set_tlist(grape_handle *h, const double *tlist) try {
         }
     if (h->open) return open_set_tlist(h, tlist);
     h->tg_state = 0;
+    h->hvs.came(grape_handle::HvpSplit::TLIST);
     h->have_forward = false;
     if (!h->shards.empty()) {
         for (grape_handle *c : h->shards) {
@@ -4761,6 +4780,7 @@ int batch_group(grape_handle *h, const BatchStrides &st, int p0, int Pg, const d
 // the stored states no longer belong to "the last evaluation": grape_get_time_gradient refuses until the next ordinary one
 void batch_invalidate(grape_handle *h) {
     h->tg_state = 0;
+    h->hvs.came(grape_handle::HvpSplit::BATCH);
     for (grape_handle *c : h->shards) c->tg_state = 0;
     if (h->open) { h->open->tg_state = OpenCtx::TG_BATCH; h->open->hv_state = OpenCtx::HV_BATCH; }
 }
@@ -4880,6 +4900,7 @@ int grape_hvp(grape_handle *h, int nv, const double *V, double *HV) try {
     if (!h) { g_create_error = "grape_hvp: h == NULL"; return GRAPE_ERR_INVALID; }
     if (nv <= 0 || !V || !HV) { h->err = "grape_hvp: nv must be positive, V and HV must not be NULL"; return GRAPE_ERR_INVALID; }
     if (const char *why = hvp_refusal(h)) { h->err = std::string("grape_hvp: ") + why; return GRAPE_ERR_INVALID; }
+    h->hvs.came(grape_handle::HvpSplit::HVP);   // (the tangent storage of a forward half is overwritten)
     const auto t0 = std::chrono::steady_clock::now();
     HIPCHK(h, hipSetDevice(h->device));
     if (h->foreign_stream) HIPCHK(h, hipDeviceSynchronize());   // (see grape_get_time_gradient)
@@ -4943,6 +4964,284 @@ GRAPE_BARRIER(h ? &h->err : &g_create_error)
 int grape_get_hvp_info(grape_handle *h, double *out, int n) try {
     if (!h || !out) return GRAPE_ERR_INVALID;
     return copy_info(h->hvp.info, 7, out, n);
+}
+GRAPE_BARRIER(h ? &h->err : &g_create_error)
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------
+// grape_hvp_forward / grape_hvp_backward / grape_hvp_backward_chi: grape_hvp cut at its one cross-trajectory dependency
+// (grape_hvp_split.hip.h)
+// ---------------------------------------------------------------------------------------
+namespace {
+
+typedef grape_handle::HvpSplit HvpSplit;
+
+// why this handle cannot take a split call (nullptr: it can); every test precedes the first HIP call
+const char *hvp_split_refusal(const grape_handle *h, bool builtin) {
+    if (h->open) return "open-system handles are out of scope (DESIGN.md 20)";
+    if (!h->shards.empty() || h->p.ndev > 1) return "several devices behind one handle (ndev > 1) are out of scope";
+    if (h->N > 64) return "N > 64 is out of scope (the kernels work on at most four 16-wide tiles)";
+    if (builtin && h->no_target)
+        return "this handle has no target states (grape_problem.target == NULL): grape_hvp_backward_chi is the route";
+    if (h->have_gb || (h->p.Dpen && h->p.lambda_b != 0.0)) return "the built-in running cost (Dpen, lambda_b != 0) is out of scope";
+    if (h->tg_xi_user) return "the last backward half took a caller's xi (grape_backward_xi): running costs are out of scope";
+    return nullptr;
+}
+
+// the extras of the split calls for nv directions, in a store of their own
+int hvs_reserve(grape_handle *h, int nv) {
+    HvpSplit &x = h->hvs;
+    if (nv <= x.cap) return GRAPE_OK;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    x.mem.release(); x.cap = 0;
+    const size_t K = (size_t)h->K, NP = (size_t)h->NP, n = (size_t)nv;
+    hipError_t e = x.mem.alloc(&x.d_chi, K * NP);
+    if (e == hipSuccess) e = x.mem.alloc(&x.d_dchi, n * K * NP);
+    if (e == hipSuccess) e = x.mem.alloc(&x.d_ztarget, K * (size_t)h->N);
+    if (e == hipSuccess) e = x.mem.alloc(&x.d_dpsiT, n * K * (size_t)h->N);
+    if (e == hipSuccess) e = x.mem.alloc(&x.d_ftot, (size_t)2);
+    if (e == hipSuccess) e = x.mem.alloc(&x.d_dftot, 2 * n);
+    if (e == hipSuccess) e = x.mem.alloc(&x.d_psums, 2 * n);
+    if (e == hipSuccess) e = hipMemsetAsync(x.d_ztarget, 0, K * (size_t)h->N * 16, h->stream);
+    if (e != hipSuccess) {
+        x.mem.release();
+        (void)hipGetLastError();
+        h->err = std::string("grape_hvp_forward: storage of the split calls: ") + hipGetErrorString(e);
+        return GRAPE_ERR_HIP;
+    }
+    x.cap = nv;
+    return GRAPE_OK;
+}
+
+HvpArgs hvp_split_args(const grape_handle *h) {
+    HvpArgs a{};
+    a.H0f = h->d_H0f; a.Hcf = h->d_Hcf; a.eps = h->d_eps; a.shape = h->d_shape; a.dts = h->d_dts; a.rb = h->d_rb;
+    a.V = h->hvp.d_hvV; a.fw = h->d_fw; a.target = h->no_target ? h->hvs.d_ztarget : h->d_target; a.weights = h->d_weights;
+    a.tau = (const double2 *)h->d_out; a.f = h->hvs.d_ftot;
+    a.dpsi = h->hvp.d_hvdpsi; a.dtau = h->hvp.d_hvdtau; a.dcoef = h->hvp.d_hvdcoef; a.tg = h->hvp.d_hvtg; a.ws = h->hvp.d_hvws;
+    a.flags = (int *)(h->hvp.d_hvstats + 4 * (size_t)h->hvp.store.cap * h->K); a.stats = h->hvp.d_hvstats;
+    a.tol = h->series_tol; a.theta = h->series_theta;
+    a.K = h->K; a.K_total = h->K_total; a.L = h->L; a.N = h->N; a.N_T = h->N_T; a.functional = h->p.functional;
+    a.hc_per_traj = h->p.hc_per_traj;
+    return a;
+}
+
+template <int NP>
+void hvp_split_launch_chi(const HvpArgs &a, int nd, int nct, hipStream_t s, const double2 *chi, const double2 *dchi) {
+    const dim3 grid((unsigned)a.K, (unsigned)nd), blk(4 * NP);
+    if (nct == 1) hipLaunchKernelGGL((hvp_backward_chi_kernel<NP, 1>), grid, blk, 0, s, a, chi, dchi);
+    else hipLaunchKernelGGL((hvp_backward_chi_kernel<NP, 2>), grid, blk, 0, s, a, chi, dchi);
+}
+template <int NP>
+void hvp_split_launch_builtin(const HvpArgs &a, int nd, int nct, hipStream_t s) {
+    const dim3 grid((unsigned)a.K, (unsigned)nd), blk(4 * NP);
+    if (nct == 1) hipLaunchKernelGGL((hvp_backward_kernel<NP, 1>), grid, blk, 0, s, a);
+    else hipLaunchKernelGGL((hvp_backward_kernel<NP, 2>), grid, blk, 0, s, a);
+}
+
+// the statistics of one half (which = 0: forward workgroups, 1: backward workgroups) and the flag word
+int hvp_split_stats(grape_handle *h, const HvpArgs &a, int nv, int which, double *terms, double *steps, bool *taylor) {
+    const size_t n = 2 * (size_t)nv * h->K;
+    std::vector<unsigned long long> st(n + 1, 0ull);
+    HIPCHK(h, hipMemcpyAsync(st.data(), a.stats + (size_t)which * n, n * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(&st[n], a.flags, 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    *terms = 0.; *steps = 0.;
+    for (size_t q = 0; q < n / 2; ++q) { *terms += (double)st[2 * q]; *steps += (double)st[2 * q + 1]; }
+    *taylor = ((int)(st[n] & 0xffffffffull) & 16) != 0;
+    return GRAPE_OK;
+}
+
+int hvp_split_forward(grape_handle *h, int nv, const double *V, double *dtau, double *dsums, double *dpsiT) {
+    const auto t0 = std::chrono::steady_clock::now();
+    HvpSplit &x = h->hvs;
+    HIPCHK(h, hipSetDevice(h->device));
+    if (h->foreign_stream) HIPCHK(h, hipDeviceSynchronize());   // (see grape_get_time_gradient)
+    (void)hipGetLastError();
+    // all nv directions stay resident between the halves: the budget of grape_hvp decides how many that can be
+    int nd = 0;
+    const hipError_t ep = h->hvp.store.plan(nv, hvp_bytes_per_direction(h), 8.0 * 1073741824.0, &nd);
+    if (ep != hipSuccess) { h->err = std::string("hipMemGetInfo(&free_b, &total_b): ") + hipGetErrorString(ep); return GRAPE_ERR_HIP; }
+    if (nd < nv) {
+        h->err = "grape_hvp_forward: nv = " + std::to_string(nv) + " directions do not fit the storage budget of grape_hvp (8 GB, half of the "
+                 "free memory, GRAPE_HVP_DIRS): at most " + std::to_string(nd) + " stay resident between the halves; loop over groups of that size";
+        return GRAPE_ERR_INVALID;
+    }
+    x.state = HvpSplit::FAILED;   // (until this half has succeeded: the tangent storage is being overwritten)
+    int rc = hvp_reserve(h, nv, &nd);
+    if (rc) return rc;
+    rc = hvs_reserve(h, nv);
+    if (rc) return rc;
+    const size_t LN = (size_t)h->L * h->N_T, K = (size_t)h->K, N = (size_t)h->N;
+    hipStream_t s = h->stream;
+    const HvpArgs a = hvp_split_args(h);
+    HIPCHK(h, hipMemcpyAsync(h->hvp.d_hvV, V, (size_t)nv * LN * 8, hipMemcpyHostToDevice, s));
+    HIPCHK(h, hipMemsetAsync(h->hvp.d_hvstats, 0, (4 * (size_t)h->hvp.store.cap * K + 1) * 8, s));
+    {
+        const dim3 grid((unsigned)K, (unsigned)nv);
+        switch (h->NP) {
+            case 16: hipLaunchKernelGGL(hvp_forward_kernel<16>, grid, dim3(64), 0, s, a); break;
+            case 32: hipLaunchKernelGGL(hvp_forward_kernel<32>, grid, dim3(128), 0, s, a); break;
+            case 48: hipLaunchKernelGGL(hvp_forward_kernel<48>, grid, dim3(192), 0, s, a); break;
+            default: hipLaunchKernelGGL(hvp_forward_kernel<64>, grid, dim3(256), 0, s, a); break;
+        }
+    }
+    hipLaunchKernelGGL(hvp_partial_sum_kernel, dim3((unsigned)nv), dim3(64), 0, s, a, x.d_psums);
+    HIPCHK(h, hipGetLastError());
+    if (dtau) HIPCHK(h, hipMemcpyAsync(dtau, h->hvp.d_hvdtau, (size_t)nv * K * 16, hipMemcpyDeviceToHost, s));
+    if (dsums) HIPCHK(h, hipMemcpyAsync(dsums, x.d_psums, (size_t)nv * 16, hipMemcpyDeviceToHost, s));
+    if (dpsiT) {   // Psi~'_k(T): row N_T of every (direction, trajectory) block, packed on the device, one copy on this stream
+        hipLaunchKernelGGL(hvp_final_tangent_kernel, dim3((unsigned)((size_t)nv * K)), dim3(64), 0, s, a, h->NP, x.d_dpsiT);
+        HIPCHK(h, hipGetLastError());
+        HIPCHK(h, hipMemcpyAsync(dpsiT, x.d_dpsiT, (size_t)nv * K * N * 16, hipMemcpyDeviceToHost, s));
+    }
+    double terms = 0., steps = 0.;
+    bool taylor = false;
+    rc = hvp_split_stats(h, a, nv, 0, &terms, &steps, &taylor);
+    if (rc) return rc;
+    if (taylor) { h->err = "grape_hvp_forward: a series did not converge within 200 terms"; return GRAPE_ERR_TAYLOR; }
+    if (dpsiT && !h->bal.empty())   // the caller's frame: Psi' = D Psi~'
+        for (size_t r = 0; r < (size_t)nv * K; ++r)
+            for (size_t i = 0; i < N; ++i) { dpsiT[2 * (r * N + i)] *= h->bal[i]; dpsiT[2 * (r * N + i) + 1] *= h->bal[i]; }
+    if (h->no_target) {   // tau is NaN on such a handle (optimize.jl:753), so are its derivatives
+        const double nan = std::nan("");
+        if (dtau) std::fill(dtau, dtau + 2 * (size_t)nv * K, nan);
+        if (dsums) std::fill(dsums, dsums + 2 * (size_t)nv, nan);
+    }
+    x.state = HvpSplit::READY; x.nv = nv; x.terms_fw = terms; x.steps_fw = steps;
+    double *info = h->hvp.info;
+    info[0] = terms; info[1] = steps; info[2] = (double)nv; info[3] = (double)(h->hvp.store.mem.bytes() + x.mem.bytes());
+    info[4] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    info[5] = terms; info[6] = 0.;
+    return GRAPE_OK;
+}
+
+// is there a forward half whose tangent states a backward half of nv directions may read?  (no HIP call)
+int hvp_split_ready(grape_handle *h, const char *call, int nv) {
+    const HvpSplit &x = h->hvs;
+    const char *why = nullptr;
+    switch (x.state) {
+        case HvpSplit::READY: break;
+        case HvpSplit::NONE: why = "no grape_hvp_forward on this handle yet"; break;
+        case HvpSplit::EVAL: why = "a forward evaluation came since the last grape_hvp_forward"; break;
+        case HvpSplit::TLIST: why = "grape_set_tlist came since the last grape_hvp_forward"; break;
+        case HvpSplit::BATCH: why = "grape_eval_batch came since the last grape_hvp_forward"; break;
+        case HvpSplit::HVP: why = "grape_hvp came since the last grape_hvp_forward (it shares the tangent storage and overwrites it)"; break;
+        default: why = "the last grape_hvp_forward failed"; break;
+    }
+    if (why) { h->err = std::string(call) + ": " + why; return GRAPE_ERR_INVALID; }
+    if (h->tg_state < 1) { h->err = std::string(call) + ": no valid forward state on this time grid"; return GRAPE_ERR_INVALID; }
+    if (nv != x.nv) {
+        h->err = std::string(call) + ": nv = " + std::to_string(nv) + ", but the last grape_hvp_forward took nv = " + std::to_string(x.nv);
+        return GRAPE_ERR_INVALID;
+    }
+    return GRAPE_OK;
+}
+
+// either backward half: chi == nullptr is the built-in functional with the all-reduced f_total, df_total
+int hvp_split_backward(grape_handle *h, const char *call, int nv, const double *f_total, const double *df_total, const double *chi,
+                       const double *dchi, double *HV) {
+    const auto t0 = std::chrono::steady_clock::now();
+    HvpSplit &x = h->hvs;
+    HIPCHK(h, hipSetDevice(h->device));
+    if (h->foreign_stream) HIPCHK(h, hipDeviceSynchronize());
+    (void)hipGetLastError();
+    const size_t LN = (size_t)h->L * h->N_T, K = (size_t)h->K, N = (size_t)h->N, NP = (size_t)h->NP;
+    hipStream_t s = h->stream;
+    const HvpArgs a = hvp_split_args(h);
+    const int nct = 2 + 2 * h->L > 16 ? 2 : 1;
+    // (statistics and flag word of this half; those of the forward half are on the host already)
+    HIPCHK(h, hipMemsetAsync(h->hvp.d_hvstats, 0, (4 * (size_t)h->hvp.store.cap * K + 1) * 8, s));
+    if (chi) {
+        // chi~ = D chi, chi~' = D chi' (the backward recursion runs with U~^dagger = D U^dagger D^-1), zero-padded to NP
+        const size_t rows = (1 + (size_t)nv) * K;
+        x.stage.assign(2 * rows * NP, 0.0);
+        for (size_t r = 0; r < rows; ++r) {
+            const double *src = r < K ? chi + 2 * r * N : dchi + 2 * (r - K) * N;
+            double *dst = x.stage.data() + 2 * r * NP;
+            for (size_t i = 0; i < N; ++i) {
+                const double f = h->bal.empty() ? 1.0 : h->bal[i];
+                dst[2 * i] = f * src[2 * i]; dst[2 * i + 1] = f * src[2 * i + 1];
+            }
+        }
+        HIPCHK(h, hipMemcpyAsync(x.d_chi, x.stage.data(), K * NP * 16, hipMemcpyHostToDevice, s));
+        HIPCHK(h, hipMemcpyAsync(x.d_dchi, x.stage.data() + 2 * K * NP, (size_t)nv * K * NP * 16, hipMemcpyHostToDevice, s));
+        switch (h->NP) {
+            case 16: hvp_split_launch_chi<16>(a, nv, nct, s, x.d_chi, x.d_dchi); break;
+            case 32: hvp_split_launch_chi<32>(a, nv, nct, s, x.d_chi, x.d_dchi); break;
+            case 48: hvp_split_launch_chi<48>(a, nv, nct, s, x.d_chi, x.d_dchi); break;
+            default: hvp_split_launch_chi<64>(a, nv, nct, s, x.d_chi, x.d_dchi); break;
+        }
+    } else {
+        HIPCHK(h, hipMemcpyAsync(x.d_ftot, f_total, 16, hipMemcpyHostToDevice, s));
+        HIPCHK(h, hipMemcpyAsync(x.d_dftot, df_total, (size_t)nv * 16, hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(hvp_coef_total_kernel, dim3((unsigned)nv), dim3(64), 0, s, a, (const double *)x.d_dftot);
+        switch (h->NP) {
+            case 16: hvp_split_launch_builtin<16>(a, nv, nct, s); break;
+            case 32: hvp_split_launch_builtin<32>(a, nv, nct, s); break;
+            case 48: hvp_split_launch_builtin<48>(a, nv, nct, s); break;
+            default: hvp_split_launch_builtin<64>(a, nv, nct, s); break;
+        }
+    }
+    HIPCHK(h, hipGetLastError());
+    // (H v)_j = -2 Re sum_k of the per-trajectory terms: the gradient's reduction, fixed order
+    for (int j = 0; j < nv; ++j)
+        hipLaunchKernelGGL(grad_reduce_kernel, dim3((unsigned)((LN + 15) / 16)), dim3(256), 0, s, h->hvp.d_hvtg + (size_t)j * K * LN, h->K,
+                           (int)LN, h->hvp.d_hvout + (size_t)j * LN, (const double2 *)nullptr);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipMemcpyAsync(HV, h->hvp.d_hvout, (size_t)nv * LN * 8, hipMemcpyDeviceToHost, s));
+    double terms = 0., steps = 0.;
+    bool taylor = false;
+    const int rc = hvp_split_stats(h, a, nv, 1, &terms, &steps, &taylor);
+    if (rc) return rc;
+    if (taylor) { h->err = std::string(call) + ": a series did not converge within 200 terms"; return GRAPE_ERR_TAYLOR; }
+    double *info = h->hvp.info;
+    info[0] = x.terms_fw + terms; info[1] = x.steps_fw + steps; info[2] = (double)nv;
+    info[3] = (double)(h->hvp.store.mem.bytes() + x.mem.bytes());
+    info[4] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    info[5] = x.terms_fw; info[6] = terms;
+    return GRAPE_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int grape_hvp_forward(grape_handle *h, int nv, const double *V, double *dtau, double *dsums, double *dpsiT) try {
+    if (!h) { g_create_error = "grape_hvp_forward: h == NULL"; return GRAPE_ERR_INVALID; }
+    if (nv <= 0 || !V) { h->err = "grape_hvp_forward: nv must be positive, V must not be NULL"; return GRAPE_ERR_INVALID; }
+    if (const char *why = hvp_split_refusal(h, false)) { h->err = std::string("grape_hvp_forward: ") + why; return GRAPE_ERR_INVALID; }
+    if (h->tg_state < 1) {
+        h->err = "grape_hvp_forward: no valid forward state on this time grid (no evaluation yet, the last one failed, grape_set_tlist "
+                 "came since, or the last call was grape_eval_batch)";
+        return GRAPE_ERR_INVALID;
+    }
+    return hvp_split_forward(h, nv, V, dtau, dsums, dpsiT);
+}
+GRAPE_BARRIER(h ? &h->err : &g_create_error)
+
+int grape_hvp_backward(grape_handle *h, int nv, const double f_total[2], const double *df_total, double *HV) try {
+    if (!h) { g_create_error = "grape_hvp_backward: h == NULL"; return GRAPE_ERR_INVALID; }
+    if (nv <= 0 || !f_total || !df_total || !HV) {
+        h->err = "grape_hvp_backward: nv must be positive, f_total, df_total and HV must not be NULL";
+        return GRAPE_ERR_INVALID;
+    }
+    if (const char *why = hvp_split_refusal(h, true)) { h->err = std::string("grape_hvp_backward: ") + why; return GRAPE_ERR_INVALID; }
+    if (const int rc = hvp_split_ready(h, "grape_hvp_backward", nv)) return rc;
+    return hvp_split_backward(h, "grape_hvp_backward", nv, f_total, df_total, nullptr, nullptr, HV);
+}
+GRAPE_BARRIER(h ? &h->err : &g_create_error)
+
+int grape_hvp_backward_chi(grape_handle *h, int nv, const double *chi, const double *dchi, double *HV) try {
+    if (!h) { g_create_error = "grape_hvp_backward_chi: h == NULL"; return GRAPE_ERR_INVALID; }
+    if (nv <= 0 || !chi || !dchi || !HV) {
+        h->err = "grape_hvp_backward_chi: nv must be positive, chi, dchi and HV must not be NULL";
+        return GRAPE_ERR_INVALID;
+    }
+    if (const char *why = hvp_split_refusal(h, false)) { h->err = std::string("grape_hvp_backward_chi: ") + why; return GRAPE_ERR_INVALID; }
+    if (const int rc = hvp_split_ready(h, "grape_hvp_backward_chi", nv)) return rc;
+    return hvp_split_backward(h, "grape_hvp_backward_chi", nv, nullptr, nullptr, chi, dchi, HV);
 }
 GRAPE_BARRIER(h ? &h->err : &g_create_error)
 

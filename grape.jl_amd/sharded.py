@@ -50,6 +50,7 @@ class ShardedEvaluator:
         self.dist = dist  # torch.distributed module (initialised) or None for a single process
         self.device = device  # torch.device for the RCCL path, None for the host (gloo) path
         self._buf = None
+        self._f_total = None
 
     # -- host path (gloo / single process) ---------------------------------------------------
     def eval_host(self, pulsevals):
@@ -64,8 +65,27 @@ class ShardedEvaluator:
         G = torch.from_numpy(self.h.backward(complex(sums[0].item(), sums[1].item())))
         if self.dist is not None:
             self.dist.all_reduce(G)
+        self._f_total = complex(sums[0].item(), sums[1].item())   # (hvp_host: the boundary of the backward half)
         J = functional_value(self.functional, sums.tolist(), self.K_total, getattr(self.h, "lambda_b", 0.0))
         return J, G.numpy(), tau
+
+    def hvp_host(self, V):
+        """Exact Hessian-vector products over all shards at the pulses of the last ``eval_host``: ``V`` [nv, L*N_T] (or
+        [L*N_T]) -> H v of the same shape.  The split-phase calls of the handle with the one cross-trajectory reduction of
+        the product between them -- all-reduce(sum) of ``sum_k w_k tau'_k`` per direction -- and the all-reduce of the
+        partial H v at the end, as for the gradient."""
+        import torch
+        if getattr(self, "_f_total", None) is None:
+            raise RuntimeError("hvp_host needs an eval_host first (the all-reduced f of that evaluation)")
+        _, dsums = self.h.hvp_forward(V)
+        ds = torch.from_numpy(np.array(dsums, dtype=np.complex128).reshape(-1).view(np.float64).copy())
+        if self.dist is not None:
+            self.dist.all_reduce(ds)
+        df = ds.numpy().view(np.complex128)
+        HV = torch.from_numpy(np.array(self.h.hvp_backward(self._f_total, df if np.ndim(dsums) else df[0]), dtype=np.float64))
+        if self.dist is not None:
+            self.dist.all_reduce(HV)
+        return HV.numpy()
 
     def time_gradient(self):
         """dJ/d(dt_n) of the last evaluation: this shard's partial sum, all-reduced like the gradient."""

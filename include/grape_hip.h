@@ -439,6 +439,49 @@ int grape_hvp(grape_handle *h, int nv, const double *V, double *HV);
  * Returns the number of entries written (at most n). */
 int grape_get_hvp_info(grape_handle *h, double *out, int n);
 
+/* grape_hvp in two halves, cut at its one cross-trajectory dependency (entry points only, the ABI version stays 7;
+ * csrc/grape_hvp_split.hip.h).  What grape_hvp refuses -- a trajectory shard (K < K_total) and a caller's
+ * functional, handles without targets included -- goes through these, as the gradient goes through grape_forward +
+ * grape_backward / grape_backward_chi.  grape_hvp itself and its refusals are unchanged.
+ *
+ * grape_hvp_forward: the tangent forward sweep of nv directions V [nv][L*N_T] at the pulses of the last evaluation.  It
+ * leaves Psi'_k(t_n) of ALL nv directions on the device and returns, each where the pointer is not NULL,
+ *     dtau  [nv][K] complex     tau'_k = <tgt_k | Psi'_k(T)>
+ *     dsums [nv][2]             sum over THIS handle's k of w_k tau'_k -- what the host all-reduces between the halves
+ *     dpsiT [nv][K][N] complex  Psi'_k(T) in the caller's frame (what a caller's chi' is formed from)
+ * It needs what grape_hvp needs: a successful evaluation that ran the forward half on the current time grid.  On a handle
+ * without targets dtau and dsums come back NaN, as tau does.
+ *
+ * grape_hvp_backward: the built-in functional.  f_total is the all-reduced sum_k w_k tau_k (as for grape_backward),
+ * df_total [nv][2] the all-reduced dsums.  It uses K_total and the handle's weights.  On an unsharded handle
+ * grape_hvp_forward + grape_hvp_backward(grape_get_sums()[0:2], dsums) gives the bits of grape_hvp.
+ *
+ * grape_hvp_backward_chi: a caller's functional.  chi [K][N] complex = chi_k(T) as for grape_backward_chi, dchi [nv][K][N]
+ * its derivative along V[j] (both in the caller's frame; not normalised, no chi_min_norm guard: everything is linear in
+ * chi).  It reads neither targets, weights, tau, f nor the functional.
+ *
+ *   - HV [nv][L*N_T] is the sum over this handle's trajectories: the full product when K == K_total, otherwise the partial
+ *     sum the caller all-reduces like G.
+ *   - A backward half needs a successful grape_hvp_forward with the same nv since the last of: any forward evaluation,
+ *     grape_set_tlist, grape_eval_batch, grape_hvp (it shares the tangent storage and overwrites it).  Otherwise
+ *     GRAPE_ERR_INVALID with a message that names which of these came between; the handle stays usable.  Any number of
+ *     backward halves, of either kind, may follow one forward half.
+ *   - All nv directions stay resident between the halves: an nv beyond the storage budget of grape_hvp (8 GB, half of the
+ *     free memory) or beyond GRAPE_HVP_DIRS is GRAPE_ERR_INVALID, the message names the largest nv that fits; the caller
+ *     loops.  What only the split calls need is allocated by the first of them, in a store of its own.
+ *   - A direction's result does not depend on nv or on its position, and two calls give the same bits.  Nothing an
+ *     evaluation, grape_get_time_gradient or grape_hvp reads is touched.
+ *   - grape_get_hvp_info: after a forward half [5] = [0] = its series terms and [6] = 0; after a backward half [6] and
+ *     [0] = [5] + [6]; [1] the (sub-)steps of both halves; [4] the milliseconds of the last call.
+ *   - A series that does not converge within 200 terms: GRAPE_ERR_TAYLOR, as in grape_hvp.
+ *   - GRAPE_ERR_INVALID with a message that names the reason, before the first HIP call: h == NULL (message:
+ *     grape_last_error(NULL)); a NULL V / HV / chi / dchi / f_total / df_total; nv <= 0; an open-system handle; N > 64;
+ *     ndev > 1; the built-in running cost (Dpen, lambda_b != 0) or a handle whose last backward half took a caller's xi;
+ *     grape_hvp_backward on a handle without targets (grape_hvp_backward_chi is the route). */
+int grape_hvp_forward(grape_handle *h, int nv, const double *V, double *dtau, double *dsums, double *dpsiT);
+int grape_hvp_backward(grape_handle *h, int nv, const double f_total[2], const double *df_total, double *HV);
+int grape_hvp_backward_chi(grape_handle *h, int nv, const double *chi, const double *dchi, double *HV);
+
 /* Exact Hessian-vector products on an open-system handle (grape_create_open; entry points only, the ABI version stays 7;
  * csrc/grape_lindblad_hvp.hip.h):
  *   HV[j] = (d^2 J / d eps^2) V[j],  j < nv,  at the pulses of the last evaluation;  V, HV: [nv][L*N_T], control-major.

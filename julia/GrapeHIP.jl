@@ -450,6 +450,64 @@ function hvp_info(h::Handle)
     return (terms = Int(out[1]), steps = Int(out[2]), dirs_per_group = Int(out[3]), bytes = Int(out[4]), ms = out[5])
 end
 
+"""
+    hvp_forward!(h, V; dtau=nothing, dsums=nothing, dpsiT=nothing)
+
+First half of a split Hessian-vector product (grape_hvp_forward): the tangent forward sweep of the columns of the `L*N_T × nv`
+matrix `V` at the pulses of the last evaluation.  All directions stay on the device for `hvp_backward!` / `hvp_backward_chi!`.
+Filled where given: `dtau` (`K × nv` complex, `τ′ₖ = ⟨tgtₖ|Ψ′ₖ(T)⟩`), `dsums` (`nv` complex, `Σₖ wₖ τ′ₖ` over THIS handle's
+trajectories: what a sharded caller all-reduces) and `dpsiT` (`N × K × nv` complex, `Ψ′ₖ(T)`: what a caller's `χ′` is formed
+from).  This is the route for trajectory shards (`K < K_total`) and for a functional of the caller's, which `hvp!` refuses.
+"""
+function hvp_forward!(h::Handle, V::VecOrMat{Float64}; dtau::Union{Nothing,VecOrMat{ComplexF64}}=nothing,
+                      dsums::Union{Nothing,Vector{ComplexF64}}=nothing, dpsiT::Union{Nothing,Array{ComplexF64}}=nothing)
+    isempty(h.fixed) || error("GrapeHIP.hvp_forward!: handles with pseudo-controls are not supported (the directions have no entries for them)")
+    size(V, 1) == h.L * h.N_T || throw(DimensionMismatch("V must be L*N_T = $(h.L * h.N_T) × nv"))
+    nv = size(V, 2)
+    nv >= 1 || throw(DimensionMismatch("V must hold at least one direction"))
+    isnothing(dtau) || length(dtau) == h.K * nv || throw(DimensionMismatch("dtau must be K × nv"))
+    isnothing(dsums) || length(dsums) == nv || throw(DimensionMismatch("dsums must hold nv sums"))
+    isnothing(dpsiT) || length(dpsiT) == h.N * h.K * nv || throw(DimensionMismatch("dpsiT must be N × K × nv"))
+    ptr(a) = isnothing(a) ? Ptr{ComplexF64}(C_NULL) : pointer(a)
+    check(h, GC.@preserve V dtau dsums dpsiT ccall((:grape_hvp_forward, libgrape), Cint,
+          (Ptr{Cvoid}, Cint, Ptr{Float64}, Ptr{ComplexF64}, Ptr{ComplexF64}, Ptr{ComplexF64}), h.ptr, nv, V, ptr(dtau), ptr(dsums), ptr(dpsiT)))
+    return nothing
+end
+
+"""
+    hvp_backward!(HV, h, f_total, df_total)
+
+Second half for the built-in functional (grape_hvp_backward): `f_total` the all-reduced `Σₖ wₖ τₖ` of the evaluation (as for
+`grape_backward`), `df_total` (`nv` complex) the all-reduced `dsums` of `hvp_forward!`.  `HV` (`L*N_T × nv`) is the sum over
+this handle's trajectories: all-reduce it like the gradient when `K < K_total`.
+"""
+function hvp_backward!(HV::VecOrMat{Float64}, h::Handle, f_total::Number, df_total::Vector{ComplexF64})
+    size(HV, 1) == h.L * h.N_T || throw(DimensionMismatch("HV must be L*N_T = $(h.L * h.N_T) × nv"))
+    nv = size(HV, 2)
+    length(df_total) == nv || throw(DimensionMismatch("df_total must hold nv = $nv sums"))
+    f = ComplexF64[f_total]
+    check(h, GC.@preserve HV f df_total ccall((:grape_hvp_backward, libgrape), Cint,
+          (Ptr{Cvoid}, Cint, Ptr{ComplexF64}, Ptr{ComplexF64}, Ptr{Float64}), h.ptr, nv, f, df_total, HV))
+    return HV
+end
+
+"""
+    hvp_backward_chi!(HV, h, chi, dchi)
+
+Second half for a functional of the caller's (grape_hvp_backward_chi): `chi` (`N × K`) as for `grape_backward_chi`, not
+normalised, and `dchi` (`N × K × nv`) its derivative along each direction of the last `hvp_forward!` -- from AD of `χ` along
+`Ψ′ₖ(T)`, as `χ` itself usually comes from AD of `J_T`.  The only route on handles without targets.
+"""
+function hvp_backward_chi!(HV::VecOrMat{Float64}, h::Handle, chi::Matrix{ComplexF64}, dchi::Array{ComplexF64})
+    size(HV, 1) == h.L * h.N_T || throw(DimensionMismatch("HV must be L*N_T = $(h.L * h.N_T) × nv"))
+    nv = size(HV, 2)
+    size(chi) == (h.N, h.K) || throw(DimensionMismatch("chi must be N × K"))
+    length(dchi) == h.N * h.K * nv || throw(DimensionMismatch("dchi must be N × K × nv"))
+    check(h, GC.@preserve HV chi dchi ccall((:grape_hvp_backward_chi, libgrape), Cint,
+          (Ptr{Cvoid}, Cint, Ptr{ComplexF64}, Ptr{ComplexF64}, Ptr{Float64}), h.ptr, nv, chi, dchi, HV))
+    return HV
+end
+
 
 # ---- open quantum systems (include/grape_hip.h: grape_create_open; INTEGRATION.md 3d) ---------------------------------------
 
