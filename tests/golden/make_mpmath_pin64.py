@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Regenerates tests/golden/mpmath_pin_herm64.json and mpmath_pin_herm100.json: ABSOLUTE pins at the sizes of the HEADLINE
 kernels (N = 64: expm_t16_asm + deriv3_asm; N = 100: the blocked path, lg_gemm_asm + deriv4_asm_128) -- the pins of
-make_mpmath_pin.py have N = 4 and reach none of them (round-5 review, "missing" 1).
+make_mpmath_pin.py have N = 4 and reach none of them (round-5 review, "missing" 1).  Also mpmath_pin_gen64.json (general generators) and
+mpmath_pin_edge64.json: cells at the edges of the four-product range, with the 50-digit distance of every cell from its edge
+(`python tests/golden/make_mpmath_pin64.py edge64` regenerates that file alone, two minutes).
 
 The literal route of the reference (a dense (L+1)N block exponential per backward step, /root/reference/src/optimize.jl:881,
 docs/src/background.md:467-477) is out of reach of mpmath at these sizes, so the SAME quantities are evaluated by another
@@ -131,6 +133,12 @@ def evaluate_all(pr, general=False):
         G = [[-2 * mp.re(sum(tau_grads[k][l][n] for k in range(K))) for n in range(N_T)] for l in range(L)]
         out[functional] = (J, tau, G, [storage[k][N_T] for k in range(K)], tau_grads)
         print(f"  functional {functional}: J = {mp.nstr(J, 30)}", flush=True)
+    if "edge" in pr:
+        # inputs at the edges of the four-product range (pin64_inputs.py, "edge64"): distance of every cell from the edge,
+        # delta = sum lam^8 dt^8 / (theta 2^s)^8 - 1 with theta the double 1.36 and s the squarings the edge of step n belongs to
+        theta = mp.mpf(1.36)
+        out["edge_delta"] = [[sum(x ** 8 for x in cells[(k, n)][0]) * (tl[n + 1] - tl[n]) ** 8 / (theta * 2 ** pr["edge"][n]) ** 8 - 1
+                              for n in range(N_T)] for k in range(K)]
     return out, resid
 
 
@@ -148,6 +156,9 @@ def main():
         out = dict(note="inputs: tests/golden/pin64_inputs.py (dyadic rationals from a written-out LCG); outputs: 50-digit mpmath "
                         "evaluation by Hermitian eigendecomposition + Daleckii-Krein (tests/golden/make_mpmath_pin64.py), printed to 40 digits",
                    name=name, N=pr["N"], L=pr["L"], N_T=pr["N_T"], K=pr["K"], eig_residual=mp.nstr(resid, 5), functionals={})
+        if "edge_delta" in res:
+            out["edge_squarings"] = list(pr["edge"])
+            out["edge_delta"] = [[mp.nstr(d, 50) for d in row] for row in res.pop("edge_delta")]
         for functional, (J, tau, G, psiT, tg) in res.items():
             out["functionals"][str(functional)] = dict(
                 J=s(J), tau=[[s(mp.re(t)), s(mp.im(t))] for t in tau],

@@ -6,7 +6,14 @@ import numpy as np
 
 SHAPES = {"herm64": dict(N=64, L=2, N_T=4, K=2, seed=0x6772617065_64), "herm100": dict(N=100, L=2, N_T=2, K=1, seed=0x6772617065_100),
           # general (non-Hermitian) generators: expm_t18g_asm + deriv3g_asm
-          "gen64": dict(N=64, L=2, N_T=3, K=1, seed=0x6772617065_65, general=True)}
+          "gen64": dict(N=64, L=2, N_T=3, K=1, seed=0x6772617065_65, general=True),
+          # cells at the edges of the four-product range (tests/t16_route_reference.py): a weak drift, a rank-one control at pulse
+          # value 1 (one outlier eigenvalue near 1), a weak second control at 0.1.  Steps 0 .. 2 put trajectory 1 at
+          # delta = m8 dt^8 / (1.36 * 2^s)^8 - 1 = -1e-5 (s = 0), -1e-5 (s = 1), +1e-3 (s = 0); step 3 is interior; trajectory 0 stays 0.6 % inside.  The steps are
+          # written-out doubles (computed once from the eigenvalues in double precision); the 50-digit delta of every cell is
+          # recorded in the pin file.
+          "edge64": dict(N=64, L=2, N_T=4, K=2, seed=0x6772617065_66, edge=(0, 1, 0, 0),
+                         steps=("0x1.57f1309d60515p+0", "0x1.57f1309d60515p+1", "0x1.57fc4d22e6703p+0", "0x1.0000000000000p+0"))}
 
 
 class Lcg:
@@ -38,6 +45,22 @@ def make_inputs(name):
         return (X + X.conj().T) / 2
 
     s0 = 1.0 / (2.0 * np.sqrt(N))                  # spectral radius of the drift ~ 1, of a control ~ 0.5
+    if "edge" in sh:
+        H0 = np.stack([herm(0.3 * s0) for _ in range(K)])
+        C2 = herm(0.3 * s0)
+        a = [int(x) for x in g.ints(N, -4096, 4096)]
+        b = [int(x) for x in g.ints(N, -4096, 4096)]
+        n2 = sum(x * x + y * y for x, y in zip(a, b))             # (integers: exact)
+        # C1 = |u><u|, u = (a + i b) / sqrt(n2): the entries (a_i + i b_i)(a_j - i b_j) are exact integers, one rounding each
+        C1 = np.array([[complex(a[i] * a[j] + b[i] * b[j], b[i] * a[j] - a[i] * b[j]) for j in range(N)] for i in range(N)]) / float(n2)
+        Hc = np.stack([C1, C2])
+        psi0 = np.stack([(g.ints(N, -4096, 4096) + 1j * g.ints(N, -4096, 4096)) / q / np.sqrt(2.0 * N) * np.sqrt(3.0) for _ in range(K)])
+        target = np.stack([(g.ints(N, -4096, 4096) + 1j * g.ints(N, -4096, 4096)) / q / np.sqrt(2.0 * N) * np.sqrt(3.0) for _ in range(K)])
+        steps = np.array([float.fromhex(x) for x in sh["steps"]])
+        tlist = np.concatenate([[0.0], np.cumsum(steps)])
+        pulse = np.array([1.0] * N_T + [0.1] * N_T)
+        return dict(N=N, L=L, N_T=N_T, K=K, H0=H0, Hc=Hc, psi0=psi0, target=target, tlist=tlist, pulsevals=pulse,
+                    weights=np.array([0.75, 1.25][:K]), steps=steps, edge=sh["edge"])
     H0 = np.stack([herm(s0) for _ in range(K)])
     Hc = np.stack([herm(0.5 * s0) for _ in range(L)])
 

@@ -73,7 +73,7 @@ def test_monomial_counts():
     assert [len(monomials(5, d)) for d in (2, 3, 4, 6, 8)] == [15, 35, 70, 210, 495]
 
 
-@pytest.mark.parametrize("N,L", list(itertools.product((8, 64), (1, 2, 3))))
+@pytest.mark.parametrize("N,L", list(itertools.product((8, 64), (1, 2, 3))) + [(8, 4)])   # L = 4: GRAPE_CERT_LMAX, 495 + 210 coefficients
 def test_tables_against_the_moments_of_the_eigenvalues(N, L):
     pr = synth.make_problem(N, L, 4, 2, seed=900 + N + L)
     rng = np.random.default_rng(N + L)
