@@ -36,7 +36,8 @@ EXPORTS = ["grape_create", "grape_destroy", "grape_eval", "grape_forward", "grap
            "grape_get_time_gradient", "grape_set_tlist", "grape_eval_batch", "grape_get_batch_info", "grape_create_open",
            "grape_hvp", "grape_get_hvp_info", "grape_open_time_gradient", "grape_open_hvp", "grape_get_open_hvp_info",
            "grape_open_eval_batch", "grape_get_open_batch_info", "grape_open_set_running_cost", "grape_open_backward_xi",
-           "grape_hvp_forward", "grape_hvp_backward", "grape_hvp_backward_chi"]
+           "grape_hvp_forward", "grape_hvp_backward", "grape_hvp_backward_chi",
+           "grape_open_hvp_forward", "grape_open_hvp_backward", "grape_open_hvp_backward_chi"]
 
 
 class GrapeHipError(RuntimeError):
@@ -104,7 +105,7 @@ def build_asm(verbose: bool = False, workdir: str | None = None) -> str:
 def _sources():
     srcs = [os.path.join(_CSRC, f) for f in ("grape_hip.hip", "grape_t18.hip", "grape_kernels.hip.h", "grape_large.hip.h",
                                              "grape_series.hip.h", "grape_cheby.hip.h", "grape_t18.hip.h", "grape_t18_coeffs.h",
-                                             "grape_deriv3.hip.h", "grape_timegrad.hip.h", "grape_batch.hip.h", "grape_lindblad.hip.h", "grape_lindblad_tg.hip.h", "grape_hvp.hip.h", "grape_hvp_split.hip.h", "grape_lindblad_hvp.hip.h", "grape_lindblad_batch.hip.h", "grape_lindblad_rc.hip.h", "grape_devmem.h", "grape_cert.hip.h", os.path.join("asm", "gen_t16.py"), os.path.join("asm", "gen_t16p.py"), os.path.join("asm", "gen_t18g.py"), os.path.join("asm", "gen_t18gp.py"), os.path.join("asm", "gen_d3.py"), os.path.join("asm", "gen_d3s.py"), os.path.join("asm", "gen_lg.py"), os.path.join("asm", "gen_d4.py"), os.path.join("asm", "gcn.py"))]
+                                             "grape_deriv3.hip.h", "grape_timegrad.hip.h", "grape_batch.hip.h", "grape_lindblad.hip.h", "grape_lindblad_tg.hip.h", "grape_hvp.hip.h", "grape_hvp_split.hip.h", "grape_lindblad_hvp.hip.h", "grape_lindblad_hvp_split.hip.h", "grape_lindblad_batch.hip.h", "grape_lindblad_rc.hip.h", "grape_devmem.h", "grape_cert.hip.h", os.path.join("asm", "gen_t16.py"), os.path.join("asm", "gen_t16p.py"), os.path.join("asm", "gen_t18g.py"), os.path.join("asm", "gen_t18gp.py"), os.path.join("asm", "gen_d3.py"), os.path.join("asm", "gen_d3s.py"), os.path.join("asm", "gen_lg.py"), os.path.join("asm", "gen_d4.py"), os.path.join("asm", "gcn.py"))]
     return srcs, os.path.join(_HERE, "..", "include", "grape_hip.h")
 
 
@@ -223,6 +224,9 @@ def load_library():
     lib.grape_hvp_backward_chi.argtypes = [vp, ip, vp, vp, vp]
     lib.grape_open_hvp.argtypes = [vp, ip, vp, vp]
     lib.grape_get_open_hvp_info.argtypes = [vp, vp, ip]
+    lib.grape_open_hvp_forward.argtypes = [vp, ip, vp, vp, vp, vp]
+    lib.grape_open_hvp_backward.argtypes = [vp, ip, vp, vp, vp]
+    lib.grape_open_hvp_backward_chi.argtypes = [vp, ip, vp, vp, vp]
     lib.grape_open_eval_batch.argtypes = [vp, ip, vp, vp, vp, vp]
     lib.grape_get_open_batch_info.argtypes = [vp, vp, ip]
     lib.grape_open_set_running_cost.argtypes = [vp, vp, ip, C.c_double]
@@ -622,7 +626,8 @@ class GrapeHipOpen(GrapeHip):
     backward_chi);  row-major numpy in, transposed on the way as ``GrapeHip`` does.  ``final_states()`` returns [K, d, d],
     ``storage()`` [K, N_T+1, d, d], ``backward_chi`` takes [K, d, d].  tau_k = tr(target_k^dagger rho_k(T)).
     ``time_gradient()`` is grape_open_time_gradient, ``open_hvp()`` / ``open_hvp_info()`` are grape_open_hvp /
-    grape_get_open_hvp_info, ``open_eval_batch()`` / ``open_batch_info()`` grape_open_eval_batch / grape_get_open_batch_info
+    grape_get_open_hvp_info, ``open_hvp_forward()`` / ``open_hvp_backward()`` / ``open_hvp_backward_chi()`` its two halves for
+    trajectory shards and a caller's functional, ``open_eval_batch()`` / ``open_batch_info()`` grape_open_eval_batch / grape_get_open_batch_info
     (the inherited ``eval_batch`` stays the loop over ``eval`` it is on such a handle).  ``set_running_cost()`` /
     ``open_backward_xi()`` are grape_open_set_running_cost / grape_open_backward_xi, the state running costs.  Not available (GrapeHipError, the handle stays usable): propagator, storage(1), backward_xi, the
     device-pointer calls, and the inherited ``hvp()`` (grape_hvp keeps its defined refusal of open handles; its message names
@@ -747,6 +752,58 @@ class GrapeHipOpen(GrapeHip):
         self._lib.grape_get_open_hvp_info(self._h, out.ctypes.data, 7)
         return dict(series_terms=int(out[0]), series_steps=int(out[1]), dirs_per_group=int(out[2]), bytes=int(out[3]), ms=float(out[4]),
                     terms_forward=int(out[5]), terms_backward=int(out[6]))
+
+    def open_hvp_forward(self, V, final_states=False):
+        """First half of a split Hessian-vector product (grape_open_hvp_forward): the tangent forward sweep of ``V``
+        [nv, L*N_T] at the pulses of the last forward half.  Returns ``(dtau [nv, K], dsums [nv] complex)`` -- tau'_k and this
+        handle's sum_k w_k tau'_k, which a sharded caller all-reduces -- and with ``final_states=True`` also
+        ``drhoT [nv, K, d, d]``, the derivative of rho_k(T) along each direction.  A single direction given as a vector [L*N_T]
+        returns them without the leading axis.  All directions stay on the device for ``open_hvp_backward`` /
+        ``open_hvp_backward_chi``."""
+        v, nv = self._hvp_dirs(V)
+        dtau = np.empty((nv, self.K), dtype=np.complex128)
+        dsums = np.empty(nv, dtype=np.complex128)
+        drho = np.empty((nv, self.K, self.N, self.N), dtype=np.complex128) if final_states else None
+        self._chk(self._lib.grape_open_hvp_forward(self._h, nv, v.ctypes.data, dtau.ctypes.data, dsums.ctypes.data,
+                                                   drho.ctypes.data if final_states else None))
+        if final_states:
+            drho = np.swapaxes(drho, -1, -2).copy()
+        if v.ndim == 1:
+            dtau, dsums, drho = dtau[0], dsums[0], (drho[0] if final_states else None)
+        return (dtau, dsums, drho) if final_states else (dtau, dsums)
+
+    def open_hvp_backward(self, f_total, df_total):
+        """Second half for the built-in functional (grape_open_hvp_backward): ``f_total`` the all-reduced sum_k w_k tau_k
+        (complex, as for ``backward``), ``df_total`` [nv] complex the all-reduced ``dsums`` of ``open_hvp_forward`` (a scalar
+        for a single direction given as a vector).  Returns this handle's H v [nv, L*N_T] (or [L*N_T]): the partial sum over
+        its trajectories, the full product when K == K_total."""
+        one = np.ndim(df_total) == 0
+        df = np.ascontiguousarray(df_total, dtype=np.complex128)   # (at least one-dimensional)
+        if np.ndim(df_total) > 1 or df.size == 0:
+            raise ValueError(f"df_total must be a complex scalar or [nv] with nv >= 1, got {np.shape(df_total)}")
+        nv = df.size
+        out = np.empty((nv, self.L * self.N_T))
+        f = np.array([complex(f_total).real, complex(f_total).imag], dtype=np.float64)
+        self._chk(self._lib.grape_open_hvp_backward(self._h, nv, f.ctypes.data, df.ctypes.data, out.ctypes.data))
+        return out[0] if one else out
+
+    def open_hvp_backward_chi(self, chi, dchi):
+        """Second half for a caller's functional (grape_open_hvp_backward_chi): ``chi`` [K, d, d] as for ``backward_chi`` (not
+        normalised), ``dchi`` [nv, K, d, d] its derivative along each direction of the last ``open_hvp_forward`` ([K, d, d]
+        for a single direction given as a vector).  Returns this handle's H v [nv, L*N_T] (or [L*N_T])."""
+        chi = np.asarray(chi)
+        d = np.asarray(dchi)
+        mat = (self.K, self.N, self.N)
+        if chi.shape != mat:
+            raise ValueError(f"chi must be [K, d, d] = {list(mat)}, got {chi.shape}")
+        if d.ndim not in (3, 4) or d.shape[-3:] != mat or d.size == 0:
+            raise ValueError(f"dchi must be [K, d, d] = {list(mat)} or [nv, K, d, d] with nv >= 1, got {d.shape}")
+        nv = 1 if d.ndim == 3 else d.shape[0]
+        chi = _c128(np.swapaxes(chi, -1, -2), mat)
+        dc = _c128(np.swapaxes(d, -1, -2))
+        out = np.empty((nv, self.L * self.N_T))
+        self._chk(self._lib.grape_open_hvp_backward_chi(self._h, nv, chi.ctypes.data, dc.ctypes.data, out.ctypes.data))
+        return out[0] if d.ndim == 3 else out
 
     def open_eval_batch(self, pulsevals, gradient=True):
         """P pulse vectors through this handle's problem side by side on the GPU (grape_open_eval_batch): ``pulsevals``

@@ -19,6 +19,7 @@
 #include "grape_hvp.hip.h"
 #include "grape_hvp_split.hip.h"
 #include "grape_lindblad_hvp.hip.h"
+#include "grape_lindblad_hvp_split.hip.h"
 #include "grape_lindblad_batch.hip.h"
 #include "grape_lindblad_rc.hip.h"
 #include "grape_devmem.h"
@@ -1531,6 +1532,21 @@ struct OpenCtx {
         unsigned long long *d_hvstats = nullptr;
         double info[7] = {0., 0., 0., 0., 0., 0., 0.};   // grape_get_open_hvp_info
     } hv;
+    // grape_open_hvp_forward / grape_open_hvp_backward / grape_open_hvp_backward_chi (grape_lindblad_hvp_split.hip.h,
+    // DESIGN.md 22): the two halves share the tangent storage above; what only they need lives here, allocated by the first
+    // split call, so that a handle which never makes one holds -- and reports -- what it held before.
+    struct HvpSplit {
+        enum { NONE = 0, READY, EVAL, TLIST, BATCH, COST, HVP, FAILED };
+        DeviceBufs mem;
+        int cap = 0;               // directions the extras hold
+        double *d_chi = nullptr, *d_dchi = nullptr, *d_ztarget = nullptr;   // chi [K] | chi' [cap][K] | zeros [K] matrices (2 NP^2 doubles)
+        double *d_drhoT = nullptr;                                          // rho'(T) [cap][K] matrices, packed for the host
+        double *d_ftot = nullptr, *d_dftot = nullptr, *d_psums = nullptr;   // f_total [2] | f'_total [cap][2] | partial sums [cap][2]
+        int state = NONE, nv = 0;  // what came since the last successful forward half, and its directions
+        double terms_fw = 0., steps_fw = 0.;
+        std::vector<double> stage; // host staging of chi, chi', rho'(T)
+        void came(int what) { if (state != NONE) state = what; }
+    } hvs;
     // grape_open_eval_batch (grape_lindblad_batch.hip.h): every per-set buffer belongs to the call -- pulses, stored
     // states, workspaces, tau | sums, ||chi||, tau_grads, G, flags, statistics.  Allocated by the first call, grows with the sets
     // of a launch group.  Nothing an ordinary evaluation or a getter reads is touched, no state word changes.
@@ -1563,7 +1579,7 @@ void open_destroy(grape_handle *h) {
     OpenCtx *o = h->open;
     hipSetDevice(h->device);
     if (h->stream) hipStreamSynchronize(h->stream);
-    o->hv.store.release(); o->ob.store.release(); o->mem.release();
+    o->hv.store.release(); o->hvs.mem.release(); o->ob.store.release(); o->mem.release();
     for (hipEvent_t e : o->ev)
         if (e) hipEventDestroy(e);
     if (h->stream) hipStreamDestroy(h->stream);
@@ -1656,6 +1672,7 @@ int open_forward(grape_handle *h, const double *pulsevals, double *tau) {
     o->have_bwd = false;
     o->tg_state = OpenCtx::TG_FAILED;   // (until this sweep has succeeded)
     o->hv_state = OpenCtx::HV_FAILED;
+    o->hvs.came(OpenCtx::HvpSplit::EVAL);
     HIPCHK(h, hipMemcpyAsync(o->d_eps, pulsevals, nl * 8, hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemsetAsync(o->d_flags, 0, 8 * sizeof(int), h->stream));
     HIPCHK(h, hipMemsetAsync(o->d_stats, 0, 2 * (K + K * h->L) * sizeof(unsigned long long), h->stream));
@@ -1835,6 +1852,7 @@ int open_set_tlist(grape_handle *h, const double *tlist) {
     o->have_bwd = false;
     o->tg_state = OpenCtx::TG_NEW_GRID;
     o->hv_state = OpenCtx::HV_NEW_GRID;
+    o->hvs.came(OpenCtx::HvpSplit::TLIST);
     return GRAPE_OK;
 }
 
@@ -1919,6 +1937,7 @@ int open_hvp(grape_handle *h, int nv, const double *V, double *HV) {
     case OpenCtx::HV_BATCH: OPEN_HV_REFUSE("no valid forward state: the last call was grape_eval_batch, the stored states are not those of one defined evaluation");
     default: OPEN_HV_REFUSE("no valid forward state: the last forward sweep failed");
     }
+    o->hvs.came(OpenCtx::HvpSplit::HVP);   // (the tangent storage of a forward half is overwritten)
     const auto t0 = std::chrono::steady_clock::now();
     HIPCHK(h, hipSetDevice(h->device));
     (void)hipGetLastError();
@@ -1969,6 +1988,221 @@ int open_hvp(grape_handle *h, int nv, const double *V, double *HV) {
     o->hv.info[0] = terms_fw + terms_bw; o->hv.info[1] = substeps; o->hv.info[2] = (double)nd; o->hv.info[3] = (double)o->hv.store.mem.bytes();
     o->hv.info[4] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     o->hv.info[5] = terms_fw; o->hv.info[6] = terms_bw;
+    return GRAPE_OK;
+}
+
+// ---------------------------------------------------------------------------------------
+// grape_open_hvp_forward / grape_open_hvp_backward / grape_open_hvp_backward_chi: grape_open_hvp cut at its one
+// cross-trajectory dependency (grape_lindblad_hvp_split.hip.h)
+// ---------------------------------------------------------------------------------------
+typedef OpenCtx::HvpSplit OpenHvpSplit;
+
+// why this handle cannot take a split call (nullptr: it can); every test precedes the first HIP call
+const char *open_hvs_refusal(const grape_handle *h, bool builtin) {
+    if (!h->open)
+        return "not an open-system handle (grape_create_open); grape_hvp_forward / grape_hvp_backward / grape_hvp_backward_chi are the "
+               "calls for a closed one";
+    if (h->open->rc_set)
+        return "a state running cost is set on this handle (grape_open_set_running_cost): its second-order terms are not carried";
+    if (builtin && h->no_target)
+        return "this handle has no target states (grape_problem.target == NULL): grape_open_hvp_backward_chi is the route";
+    return nullptr;
+}
+
+// the extras of the split calls for nv directions, in a store of their own
+int open_hvs_reserve(grape_handle *h, int nv) {
+    OpenHvpSplit &x = h->open->hvs;
+    if (nv <= x.cap) return GRAPE_OK;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    x.mem.release(); x.cap = 0;
+    const size_t K = (size_t)h->K, m2 = 2 * (size_t)h->NP * h->NP, n = (size_t)nv;
+    hipError_t e = x.mem.alloc(&x.d_chi, K * m2);
+    if (e == hipSuccess) e = x.mem.alloc(&x.d_dchi, n * K * m2);
+    if (e == hipSuccess) e = x.mem.alloc(&x.d_ztarget, K * m2);
+    if (e == hipSuccess) e = x.mem.alloc(&x.d_drhoT, n * K * m2);
+    if (e == hipSuccess) e = x.mem.alloc(&x.d_ftot, (size_t)2);
+    if (e == hipSuccess) e = x.mem.alloc(&x.d_dftot, 2 * n);
+    if (e == hipSuccess) e = x.mem.alloc(&x.d_psums, 2 * n);
+    if (e == hipSuccess) e = hipMemsetAsync(x.d_ztarget, 0, K * m2 * 8, h->stream);
+    if (e != hipSuccess) {
+        x.mem.release();
+        (void)hipGetLastError();
+        h->err = std::string("grape_open_hvp_forward: storage of the split calls: ") + hipGetErrorString(e);
+        return GRAPE_ERR_HIP;
+    }
+    x.cap = nv;
+    return GRAPE_OK;
+}
+
+LindHvpArgs open_hvs_args(const grape_handle *h, int nv) {
+    const OpenCtx *o = h->open;
+    LindHvpArgs q{};
+    q.a = open_args(h);
+    q.a.f = o->hvs.d_ftot;   // the all-reduced sum_k w_k tau_k the caller passes
+    if (h->no_target) q.a.target = o->hvs.d_ztarget;
+    q.a.ws = nullptr; q.a.tg = nullptr; q.a.stats = nullptr; q.a.rho = nullptr;
+    q.V = o->hv.d_hvV; q.dstore = o->hv.d_hvds; q.dtau = o->hv.d_hvdtau; q.dcoef = o->hv.d_hvdcoef; q.tg = o->hv.d_hvtg; q.ws = o->hv.d_hvws;
+    q.stats = o->hv.d_hvstats;
+    q.nd = nv;
+    return q;
+}
+
+// the statistics of one half (which = 0: the nv K forward workgroups, 1: the nv K L backward workgroups) and the flag word
+int open_hvs_stats(grape_handle *h, int nv, int which, double *terms, double *steps, bool *taylor) {
+    OpenCtx *o = h->open;
+    const size_t nf = (size_t)nv * h->K, n = which ? nf * h->L : nf;
+    std::vector<unsigned long long> st(2 * n, 0ull);
+    int flags[8] = {0};
+    HIPCHK(h, hipMemcpyAsync(st.data(), o->hv.d_hvstats + (which ? 2 * nf : 0), 2 * n * sizeof(unsigned long long), hipMemcpyDeviceToHost,
+                             h->stream));
+    HIPCHK(h, hipMemcpyAsync(flags, o->d_flags, sizeof(flags), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    *terms = 0.; *steps = 0.;
+    for (size_t w = 0; w < n; ++w) { *terms += (double)st[2 * w]; *steps += (double)st[2 * w + 1]; }
+    *taylor = (flags[0] & 16) != 0;
+    return GRAPE_OK;
+}
+
+int open_hvs_forward(grape_handle *h, int nv, const double *V, double *dtau, double *dsums, double *drhoT) {
+    OpenCtx *o = h->open;
+    OpenHvpSplit &x = o->hvs;
+    const char *why = nullptr;
+    switch (o->hv_state) {
+    case OpenCtx::HV_READY: break;
+    case OpenCtx::HV_NONE: why = "no evaluation on this handle yet"; break;
+    case OpenCtx::HV_NEW_GRID: why = "grape_set_tlist came after the last evaluation, the stored states belong to the previous grid"; break;
+    case OpenCtx::HV_NEW_COST: why = "grape_open_set_running_cost came after the last evaluation"; break;
+    case OpenCtx::HV_BATCH: why = "the last call was grape_eval_batch, the stored states are not those of one defined evaluation"; break;
+    default: why = "the last forward sweep failed"; break;
+    }
+    if (why) { h->err = std::string("grape_open_hvp_forward: no valid forward state: ") + why; return GRAPE_ERR_INVALID; }
+    const auto t0 = std::chrono::steady_clock::now();
+    HIPCHK(h, hipSetDevice(h->device));
+    (void)hipGetLastError();
+    // all nv directions stay resident between the halves: the budget of grape_open_hvp decides how many that can be
+    int nd = 0;
+    const hipError_t ep = o->hv.store.plan(nv, open_hvp_bytes_per_direction(h), 8.0 * 1073741824.0, &nd);
+    if (ep != hipSuccess) { h->err = std::string("hipMemGetInfo(&free_b, &total_b): ") + hipGetErrorString(ep); return GRAPE_ERR_HIP; }
+    if (nd < nv) {
+        h->err = "grape_open_hvp_forward: nv = " + std::to_string(nv) + " directions do not fit the storage budget of grape_open_hvp (8 GB, "
+                 "half of the free memory, GRAPE_HVP_DIRS): at most " + std::to_string(nd) + " stay resident between the halves; loop over "
+                 "groups of that size";
+        return GRAPE_ERR_INVALID;
+    }
+    x.state = OpenHvpSplit::FAILED;   // (until this half has succeeded: the tangent storage is being overwritten)
+    int rc = open_hvp_reserve(h, nv, &nd);
+    if (rc) return rc;
+    rc = open_hvs_reserve(h, nv);
+    if (rc) return rc;
+    const size_t K = (size_t)h->K, L = (size_t)h->L, LN = L * h->N_T, m2 = 2 * (size_t)h->NP * h->NP, nn = (size_t)h->N * h->N;
+    hipStream_t s = h->stream;
+    const LindHvpArgs q = open_hvs_args(h, nv);
+    HIPCHK(h, hipMemcpyAsync(o->hv.d_hvV, V, (size_t)nv * LN * 8, hipMemcpyHostToDevice, s));
+    HIPCHK(h, hipMemsetAsync(o->d_flags, 0, 8 * sizeof(int), s));
+    HIPCHK(h, hipMemsetAsync(o->hv.d_hvstats, 0, 2 * (size_t)nv * (K + K * L) * sizeof(unsigned long long), s));
+    OPEN_LAUNCH(lind_hvp_forward_kernel, dim3((unsigned)K, (unsigned)nv), OPEN_HVF_THREADS, q)
+    hipLaunchKernelGGL(lind_hvp_partial_sum_kernel, dim3((unsigned)nv), dim3(64), 0, s, q, x.d_psums);
+    HIPCHK(h, hipGetLastError());
+    if (dtau) HIPCHK(h, hipMemcpyAsync(dtau, o->hv.d_hvdtau, (size_t)nv * K * 16, hipMemcpyDeviceToHost, s));
+    if (dsums) HIPCHK(h, hipMemcpyAsync(dsums, x.d_psums, (size_t)nv * 16, hipMemcpyDeviceToHost, s));
+    if (drhoT) {   // rho'_k(T): row N_T of every (direction, trajectory) block, packed on the device, one copy on this stream
+        hipLaunchKernelGGL(lind_hvp_final_tangent_kernel, dim3((unsigned)((size_t)nv * K)), dim3(256), 0, s, q, (int)m2, x.d_drhoT);
+        HIPCHK(h, hipGetLastError());
+        x.stage.resize((size_t)nv * K * m2);
+        HIPCHK(h, hipMemcpyAsync(x.stage.data(), x.d_drhoT, (size_t)nv * K * m2 * 8, hipMemcpyDeviceToHost, s));
+    }
+    double terms = 0., steps = 0.;
+    bool taylor = false;
+    rc = open_hvs_stats(h, nv, 0, &terms, &steps, &taylor);
+    if (rc) return rc;
+    if (taylor) { h->err = "grape_open_hvp_forward: a series did not converge within 200 terms"; return GRAPE_ERR_TAYLOR; }
+    if (drhoT)
+        for (size_t r = 0; r < (size_t)nv * K; ++r) open_from_planar(x.stage.data() + r * m2, h->N, h->NP, drhoT + 2 * r * nn);
+    if (h->no_target) {   // tau is NaN on such a handle, so are its derivatives
+        const double nan = std::nan("");
+        if (dtau) std::fill(dtau, dtau + 2 * (size_t)nv * K, nan);
+        if (dsums) std::fill(dsums, dsums + 2 * (size_t)nv, nan);
+    }
+    x.state = OpenHvpSplit::READY; x.nv = nv; x.terms_fw = terms; x.steps_fw = steps;
+    double *info = o->hv.info;
+    info[0] = terms; info[1] = steps; info[2] = (double)nv; info[3] = (double)(o->hv.store.mem.bytes() + x.mem.bytes());
+    info[4] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    info[5] = terms; info[6] = 0.;
+    return GRAPE_OK;
+}
+
+// is there a forward half whose tangent states a backward half of nv directions may read?  (no HIP call)
+int open_hvs_ready(grape_handle *h, const char *call, int nv) {
+    const OpenHvpSplit &x = h->open->hvs;
+    const char *why = nullptr;
+    switch (x.state) {
+        case OpenHvpSplit::READY: break;
+        case OpenHvpSplit::NONE: why = "no grape_open_hvp_forward on this handle yet"; break;
+        case OpenHvpSplit::EVAL: why = "a forward evaluation came since the last grape_open_hvp_forward"; break;
+        case OpenHvpSplit::TLIST: why = "grape_set_tlist came since the last grape_open_hvp_forward"; break;
+        case OpenHvpSplit::BATCH: why = "grape_eval_batch came since the last grape_open_hvp_forward"; break;
+        case OpenHvpSplit::COST: why = "grape_open_set_running_cost came since the last grape_open_hvp_forward"; break;
+        case OpenHvpSplit::HVP:
+            why = "grape_open_hvp came since the last grape_open_hvp_forward (it shares the tangent storage and overwrites it)";
+            break;
+        default: why = "the last grape_open_hvp_forward failed"; break;
+    }
+    if (why) { h->err = std::string(call) + ": " + why; return GRAPE_ERR_INVALID; }
+    if (h->open->hv_state != OpenCtx::HV_READY) { h->err = std::string(call) + ": no valid forward state on this time grid"; return GRAPE_ERR_INVALID; }
+    if (nv != x.nv) {
+        h->err = std::string(call) + ": nv = " + std::to_string(nv) + ", but the last grape_open_hvp_forward took nv = " + std::to_string(x.nv);
+        return GRAPE_ERR_INVALID;
+    }
+    return GRAPE_OK;
+}
+
+// either backward half: chi == nullptr is the built-in functional with the all-reduced f_total, df_total
+int open_hvs_backward(grape_handle *h, const char *call, int nv, const double *f_total, const double *df_total, const double *chi,
+                      const double *dchi, double *HV) {
+    const auto t0 = std::chrono::steady_clock::now();
+    OpenCtx *o = h->open;
+    OpenHvpSplit &x = o->hvs;
+    HIPCHK(h, hipSetDevice(h->device));
+    (void)hipGetLastError();
+    const size_t K = (size_t)h->K, L = (size_t)h->L, LN = L * h->N_T, m2 = 2 * (size_t)h->NP * h->NP, nn = (size_t)h->N * h->N;
+    hipStream_t s = h->stream;
+    const LindHvpArgs q = open_hvs_args(h, nv);
+    // (statistics of this half and the flag word; those of the forward half are on the host already)
+    HIPCHK(h, hipMemsetAsync(o->d_flags, 0, 8 * sizeof(int), s));
+    HIPCHK(h, hipMemsetAsync(o->hv.d_hvstats + 2 * (size_t)nv * K, 0, 2 * (size_t)nv * K * L * sizeof(unsigned long long), s));
+    const dim3 grid((unsigned)K, (unsigned)L, (unsigned)nv);
+    if (chi) {
+        // planar row-major, zero padded to NP, as grape_backward_chi stages chi on an open handle
+        const size_t mats = (1 + (size_t)nv) * K;
+        x.stage.resize(mats * m2);
+        for (size_t r = 0; r < mats; ++r)
+            open_to_planar(r < K ? chi + 2 * r * nn : dchi + 2 * (r - K) * nn, h->N, h->NP, x.stage.data() + r * m2);
+        HIPCHK(h, hipMemcpyAsync(x.d_chi, x.stage.data(), K * m2 * 8, hipMemcpyHostToDevice, s));
+        HIPCHK(h, hipMemcpyAsync(x.d_dchi, x.stage.data() + K * m2, (size_t)nv * K * m2 * 8, hipMemcpyHostToDevice, s));
+        OPEN_LAUNCH(lind_hvp_backward_chi_kernel, grid, OPEN_BWD_THREADS, q, (const double *)x.d_chi, (const double *)x.d_dchi)
+    } else {
+        HIPCHK(h, hipMemcpyAsync(x.d_ftot, f_total, 16, hipMemcpyHostToDevice, s));
+        HIPCHK(h, hipMemcpyAsync(x.d_dftot, df_total, (size_t)nv * 16, hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(lind_hvp_coef_total_kernel, dim3((unsigned)nv), dim3(64), 0, s, q, (const double *)x.d_dftot);
+        OPEN_LAUNCH(lind_hvp_backward_kernel, grid, OPEN_BWD_THREADS, q)
+    }
+    HIPCHK(h, hipGetLastError());
+    // (H v)_j = -2 Re sum_k of the per-trajectory terms: the gradient's reduction, fixed order
+    for (int j = 0; j < nv; ++j)
+        hipLaunchKernelGGL(grad_reduce_kernel, dim3((unsigned)((LN + 15) / 16)), dim3(256), 0, s, o->hv.d_hvtg + (size_t)j * K * LN, h->K,
+                           (int)LN, o->hv.d_hvout + (size_t)j * LN, (const double2 *)nullptr);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipMemcpyAsync(HV, o->hv.d_hvout, (size_t)nv * LN * 8, hipMemcpyDeviceToHost, s));
+    double terms = 0., steps = 0.;
+    bool taylor = false;
+    const int rc = open_hvs_stats(h, nv, 1, &terms, &steps, &taylor);
+    if (rc) return rc;
+    if (taylor) { h->err = std::string(call) + ": a series did not converge within 200 terms"; return GRAPE_ERR_TAYLOR; }
+    double *info = o->hv.info;
+    info[0] = x.terms_fw + terms; info[1] = x.steps_fw + steps; info[2] = (double)nv;
+    info[3] = (double)(o->hv.store.mem.bytes() + x.mem.bytes());
+    info[4] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    info[5] = x.terms_fw; info[6] = terms;
     return GRAPE_OK;
 }
 
@@ -2085,6 +2319,7 @@ int open_set_running_cost(grape_handle *h, const double *D, int d_per_traj, doub
     o->have_bwd = false;
     o->tg_state = OpenCtx::TG_NEW_COST;
     o->hv_state = OpenCtx::HV_NEW_COST;
+    o->hvs.came(OpenCtx::HvpSplit::COST);
     o->rc_set = false; o->rc_lambda = 0.0; o->rc_per_traj = 0;
     if (!D || lambda_b == 0.0) return GRAPE_OK;
     int rc;
@@ -4547,6 +4782,38 @@ int grape_get_open_hvp_info(grape_handle *h, double *out, int n) try {
 }
 GRAPE_BARRIER(h ? &h->err : &g_create_error)
 
+int grape_open_hvp_forward(grape_handle *h, int nv, const double *V, double *dtau, double *dsums, double *drhoT) try {
+    if (!h) { g_create_error = "grape_open_hvp_forward: h == NULL"; return GRAPE_ERR_INVALID; }
+    if (nv <= 0 || !V) { h->err = "grape_open_hvp_forward: nv must be positive, V must not be NULL"; return GRAPE_ERR_INVALID; }
+    if (const char *why = open_hvs_refusal(h, false)) { h->err = std::string("grape_open_hvp_forward: ") + why; return GRAPE_ERR_INVALID; }
+    return open_hvs_forward(h, nv, V, dtau, dsums, drhoT);
+}
+GRAPE_BARRIER(h ? &h->err : &g_create_error)
+
+int grape_open_hvp_backward(grape_handle *h, int nv, const double f_total[2], const double *df_total, double *HV) try {
+    if (!h) { g_create_error = "grape_open_hvp_backward: h == NULL"; return GRAPE_ERR_INVALID; }
+    if (nv <= 0 || !f_total || !df_total || !HV) {
+        h->err = "grape_open_hvp_backward: nv must be positive, f_total, df_total and HV must not be NULL";
+        return GRAPE_ERR_INVALID;
+    }
+    if (const char *why = open_hvs_refusal(h, true)) { h->err = std::string("grape_open_hvp_backward: ") + why; return GRAPE_ERR_INVALID; }
+    if (const int rc = open_hvs_ready(h, "grape_open_hvp_backward", nv)) return rc;
+    return open_hvs_backward(h, "grape_open_hvp_backward", nv, f_total, df_total, nullptr, nullptr, HV);
+}
+GRAPE_BARRIER(h ? &h->err : &g_create_error)
+
+int grape_open_hvp_backward_chi(grape_handle *h, int nv, const double *chi, const double *dchi, double *HV) try {
+    if (!h) { g_create_error = "grape_open_hvp_backward_chi: h == NULL"; return GRAPE_ERR_INVALID; }
+    if (nv <= 0 || !chi || !dchi || !HV) {
+        h->err = "grape_open_hvp_backward_chi: nv must be positive, chi, dchi and HV must not be NULL";
+        return GRAPE_ERR_INVALID;
+    }
+    if (const char *why = open_hvs_refusal(h, false)) { h->err = std::string("grape_open_hvp_backward_chi: ") + why; return GRAPE_ERR_INVALID; }
+    if (const int rc = open_hvs_ready(h, "grape_open_hvp_backward_chi", nv)) return rc;
+    return open_hvs_backward(h, "grape_open_hvp_backward_chi", nv, nullptr, nullptr, chi, dchi, HV);
+}
+GRAPE_BARRIER(h ? &h->err : &g_create_error)
+
 int grape_open_eval_batch(grape_handle *h, int P, const double *pulsevals, double *J, double *G, double *tau) try {
     if (!h) { g_create_error = "grape_open_eval_batch: h == NULL"; return GRAPE_ERR_INVALID; }
     if (P <= 0) OPEN_OB_REFUSE("P must be positive");
@@ -4782,7 +5049,10 @@ void batch_invalidate(grape_handle *h) {
     h->tg_state = 0;
     h->hvs.came(grape_handle::HvpSplit::BATCH);
     for (grape_handle *c : h->shards) c->tg_state = 0;
-    if (h->open) { h->open->tg_state = OpenCtx::TG_BATCH; h->open->hv_state = OpenCtx::HV_BATCH; }
+    if (h->open) {
+        h->open->tg_state = OpenCtx::TG_BATCH; h->open->hv_state = OpenCtx::HV_BATCH;
+        h->open->hvs.came(OpenCtx::HvpSplit::BATCH);
+    }
 }
 
 }  // namespace

@@ -73,16 +73,19 @@ class ShardedEvaluator:
         """Exact Hessian-vector products over all shards at the pulses of the last ``eval_host``: ``V`` [nv, L*N_T] (or
         [L*N_T]) -> H v of the same shape.  The split-phase calls of the handle with the one cross-trajectory reduction of
         the product between them -- all-reduce(sum) of ``sum_k w_k tau'_k`` per direction -- and the all-reduce of the
-        partial H v at the end, as for the gradient."""
+        partial H v at the end, as for the gradient.  An open-system handle (``GrapeHipOpen``) goes through its
+        ``open_hvp_forward`` / ``open_hvp_backward``."""
         import torch
         if getattr(self, "_f_total", None) is None:
             raise RuntimeError("hvp_host needs an eval_host first (the all-reduced f of that evaluation)")
-        _, dsums = self.h.hvp_forward(V)
+        forward = getattr(self.h, "open_hvp_forward", None) or self.h.hvp_forward
+        backward = getattr(self.h, "open_hvp_backward", None) or self.h.hvp_backward
+        _, dsums = forward(V)
         ds = torch.from_numpy(np.array(dsums, dtype=np.complex128).reshape(-1).view(np.float64).copy())
         if self.dist is not None:
             self.dist.all_reduce(ds)
         df = ds.numpy().view(np.complex128)
-        HV = torch.from_numpy(np.array(self.h.hvp_backward(self._f_total, df if np.ndim(dsums) else df[0]), dtype=np.float64))
+        HV = torch.from_numpy(np.array(backward(self._f_total, df if np.ndim(dsums) else df[0]), dtype=np.float64))
         if self.dist is not None:
             self.dist.all_reduce(HV)
         return HV.numpy()

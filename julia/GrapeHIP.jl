@@ -608,6 +608,66 @@ function open_hvp_info(h::Handle)
 end
 
 """
+    open_hvp_forward!(h, V; dtau=nothing, dsums=nothing, drhoT=nothing)
+
+First half of a split Hessian-vector product on a handle made by `create_open` (grape_open_hvp_forward): the tangent forward
+sweep of the columns of the `L*N_T × nv` matrix `V` at the pulses of the last forward half.  All directions stay on the device
+for `open_hvp_backward!` / `open_hvp_backward_chi!`.  Filled where given: `dtau` (`K × nv` complex, `τ′ₖ = ⟨⟨σₖ|ρ′ₖ(T)⟩⟩`),
+`dsums` (`nv` complex, `Σₖ wₖ τ′ₖ` over THIS handle's trajectories: what a sharded caller all-reduces) and `drhoT`
+(`N × N × K × nv` complex, `ρ′ₖ(T)`: what a caller's `χ′` is formed from).  This is the route for trajectory shards
+(`K < K_total`) and for a functional of the caller's, which `open_hvp!` refuses.
+"""
+function open_hvp_forward!(h::Handle, V::VecOrMat{Float64}; dtau::Union{Nothing,VecOrMat{ComplexF64}}=nothing,
+                           dsums::Union{Nothing,Vector{ComplexF64}}=nothing, drhoT::Union{Nothing,Array{ComplexF64}}=nothing)
+    isempty(h.fixed) || error("GrapeHIP.open_hvp_forward!: handles with pseudo-controls are not supported (the directions have no entries for them)")
+    size(V, 1) == h.L * h.N_T || throw(DimensionMismatch("V must be L*N_T = $(h.L * h.N_T) × nv"))
+    nv = size(V, 2)
+    nv >= 1 || throw(DimensionMismatch("V must hold at least one direction"))
+    isnothing(dtau) || length(dtau) == h.K * nv || throw(DimensionMismatch("dtau must be K × nv"))
+    isnothing(dsums) || length(dsums) == nv || throw(DimensionMismatch("dsums must hold nv sums"))
+    isnothing(drhoT) || length(drhoT) == h.N * h.N * h.K * nv || throw(DimensionMismatch("drhoT must be N × N × K × nv"))
+    ptr(a) = isnothing(a) ? Ptr{ComplexF64}(C_NULL) : pointer(a)
+    check(h, GC.@preserve V dtau dsums drhoT ccall((:grape_open_hvp_forward, libgrape), Cint,
+          (Ptr{Cvoid}, Cint, Ptr{Float64}, Ptr{ComplexF64}, Ptr{ComplexF64}, Ptr{ComplexF64}), h.ptr, nv, V, ptr(dtau), ptr(dsums), ptr(drhoT)))
+    return nothing
+end
+
+"""
+    open_hvp_backward!(HV, h, f_total, df_total)
+
+Second half for the built-in functional (grape_open_hvp_backward): `f_total` the all-reduced `Σₖ wₖ τₖ` of the evaluation (as
+for `grape_backward`), `df_total` (`nv` complex) the all-reduced `dsums` of `open_hvp_forward!`.  `HV` (`L*N_T × nv`) is the sum
+over this handle's trajectories: all-reduce it like the gradient when `K < K_total`.
+"""
+function open_hvp_backward!(HV::VecOrMat{Float64}, h::Handle, f_total::Number, df_total::Vector{ComplexF64})
+    size(HV, 1) == h.L * h.N_T || throw(DimensionMismatch("HV must be L*N_T = $(h.L * h.N_T) × nv"))
+    nv = size(HV, 2)
+    length(df_total) == nv || throw(DimensionMismatch("df_total must hold nv = $nv sums"))
+    f = ComplexF64[f_total]
+    check(h, GC.@preserve HV f df_total ccall((:grape_open_hvp_backward, libgrape), Cint,
+          (Ptr{Cvoid}, Cint, Ptr{ComplexF64}, Ptr{ComplexF64}, Ptr{Float64}), h.ptr, nv, f, df_total, HV))
+    return HV
+end
+
+"""
+    open_hvp_backward_chi!(HV, h, chi, dchi)
+
+Second half for a functional of the caller's (grape_open_hvp_backward_chi): `chi` (`N × N × K`) as for `grape_backward_chi` on
+an open handle, not normalised, and `dchi` (`N × N × K × nv`) its derivative along each direction of the last
+`open_hvp_forward!` -- from AD of `χ` along `ρ′ₖ(T)`, as `χ` itself usually comes from AD of `J_T`.  The only route on handles
+without targets.
+"""
+function open_hvp_backward_chi!(HV::VecOrMat{Float64}, h::Handle, chi::Array{ComplexF64,3}, dchi::Array{ComplexF64})
+    size(HV, 1) == h.L * h.N_T || throw(DimensionMismatch("HV must be L*N_T = $(h.L * h.N_T) × nv"))
+    nv = size(HV, 2)
+    size(chi) == (h.N, h.N, h.K) || throw(DimensionMismatch("chi must be N × N × K"))
+    length(dchi) == h.N * h.N * h.K * nv || throw(DimensionMismatch("dchi must be N × N × K × nv"))
+    check(h, GC.@preserve HV chi dchi ccall((:grape_open_hvp_backward_chi, libgrape), Cint,
+          (Ptr{Cvoid}, Cint, Ptr{ComplexF64}, Ptr{ComplexF64}, Ptr{Float64}), h.ptr, nv, chi, dchi, HV))
+    return HV
+end
+
+"""
     open_eval_batch!(h, J, G, tau, pulsevals)
 
 `P = size(pulsevals, 2)` pulse vectors through the problem of a handle made by `create_open`, side by side on the GPU
