@@ -30,7 +30,7 @@ STATUS = {0: "GRAPE_OK", -1: "GRAPE_ERR_INVALID", -2: "GRAPE_ERR_HIP", -3: "GRAP
 # every symbol include/grape_hip.h declares (checked by tests/test_abi.py)
 EXPORTS = ["grape_create", "grape_destroy", "grape_eval", "grape_forward", "grape_backward",
            "grape_forward_device", "grape_backward_device", "grape_check", "grape_get_propagator",
-           "grape_get_tau_grads", "grape_get_storage", "grape_get_timings", "grape_reset_timings", "grape_get_work", "grape_get_cert_table",
+           "grape_get_tau_grads", "grape_get_storage", "grape_get_timings", "grape_reset_timings", "grape_get_work", "grape_get_cert_table", "grape_get_seg_table",
            "grape_last_error", "grape_abi_version", "grape_set_fused_sweeps", "grape_get_sums", "grape_backward_xi",
            "grape_get_final_states", "grape_backward_chi",
            "grape_get_time_gradient", "grape_set_tlist", "grape_eval_batch", "grape_get_batch_info", "grape_create_open",
@@ -105,7 +105,7 @@ def build_asm(verbose: bool = False, workdir: str | None = None) -> str:
 def _sources():
     srcs = [os.path.join(_CSRC, f) for f in ("grape_hip.hip", "grape_t18.hip", "grape_kernels.hip.h", "grape_large.hip.h",
                                              "grape_series.hip.h", "grape_cheby.hip.h", "grape_t18.hip.h", "grape_t18_coeffs.h",
-                                             "grape_deriv3.hip.h", "grape_timegrad.hip.h", "grape_batch.hip.h", "grape_lindblad.hip.h", "grape_lindblad_tg.hip.h", "grape_hvp.hip.h", "grape_hvp_split.hip.h", "grape_lindblad_hvp.hip.h", "grape_lindblad_hvp_split.hip.h", "grape_lindblad_batch.hip.h", "grape_lindblad_rc.hip.h", "grape_devmem.h", "grape_cert.hip.h", os.path.join("asm", "gen_t16.py"), os.path.join("asm", "gen_t16p.py"), os.path.join("asm", "gen_t18g.py"), os.path.join("asm", "gen_t18gp.py"), os.path.join("asm", "gen_d3.py"), os.path.join("asm", "gen_d3s.py"), os.path.join("asm", "gen_lg.py"), os.path.join("asm", "gen_d4.py"), os.path.join("asm", "gcn.py"))]
+                                             "grape_deriv3.hip.h", "grape_timegrad.hip.h", "grape_batch.hip.h", "grape_lindblad.hip.h", "grape_lindblad_tg.hip.h", "grape_hvp.hip.h", "grape_hvp_split.hip.h", "grape_lindblad_hvp.hip.h", "grape_lindblad_hvp_split.hip.h", "grape_lindblad_batch.hip.h", "grape_lindblad_rc.hip.h", "grape_devmem.h", "grape_cert.hip.h", "grape_econ_coeffs.h", os.path.join("asm", "gen_t16.py"), os.path.join("asm", "gen_t16p.py"), os.path.join("asm", "gen_t18g.py"), os.path.join("asm", "gen_t18gp.py"), os.path.join("asm", "gen_d3.py"), os.path.join("asm", "gen_d3s.py"), os.path.join("asm", "gen_lg.py"), os.path.join("asm", "gen_d4.py"), os.path.join("asm", "gcn.py"))]
     return srcs, os.path.join(_HERE, "..", "include", "grape_hip.h")
 
 
@@ -206,6 +206,7 @@ def load_library():
     lib.grape_get_timings.argtypes = [vp, vp, ip]
     lib.grape_get_work.argtypes = [vp, vp, ip]
     lib.grape_get_cert_table.argtypes = [vp, vp, vp, vp]
+    lib.grape_get_seg_table.argtypes = [vp, vp, vp, vp]
     lib.grape_reset_timings.argtypes = [vp]
     lib.grape_set_fused_sweeps.argtypes = [vp, ip]
     lib.grape_get_sums.argtypes = [vp, vp]
@@ -574,13 +575,13 @@ class GrapeHip:
         self._chk(self._lib.grape_reset_timings(self._h))
 
     def work(self):
-        w = np.zeros(20)
-        self._lib.grape_get_work(self._h, w.ctypes.data, 20)
+        w = np.zeros(21)
+        self._lib.grape_get_work(self._h, w.ctypes.data, 21)
         return dict(cells=w[0], squarings=w[1], flop_expm=w[2], flop_deriv=w[3], deriv_orders=w[4],
                     pivoted_cells=w[5], expm_cells=w[6], series_terms=w[7], series_steps=w[8],
                     t18_mfma_flop=w[9], t18_squarings=w[10], t18_cells=w[11], matrix_free_fallback=w[12], t16_cells=w[13],
                     asm_kernel=w[14], asm_deriv_kernel=w[15], asm_blocked_products=w[16],
-                    walk_steps=w[17], scan_block=w[18], t16_certified=w[19])
+                    walk_steps=w[17], scan_block=w[18], t16_certified=w[19], seg_certified=w[20])
 
     def cert_table(self):
         """trace tables of the generator classes (grape_get_cert_table): (t8 [KC][n8], t6 [KC][n6], exponents [n8 + n6][L]);
@@ -593,6 +594,19 @@ class GrapeHip:
             self._chk(self._lib.grape_get_cert_table(self._h, dims.ctypes.data, coef.ctypes.data, exps.ctypes.data))
         ex = np.stack([(exps >> (4 * l)) & 15 for l in range(self.L)], axis=1) if n8 + n6 else np.zeros((0, self.L), np.int32)
         return coef[:, :n8], coef[:, n8:], ex
+
+    def seg_table(self):
+        """tables of the segment certificate (grape_get_seg_table), as the plan reads them: (t4 [KC][n4], t8 [KC][n8],
+        t12 [KC][n12], exponents [n4 + n8 + n12][L]); empty arrays on a handle without them"""
+        dims = np.zeros(4, np.int32)
+        self._chk(self._lib.grape_get_seg_table(self._h, dims.ctypes.data, None, None))
+        KC, n4, n8, n12 = (int(x) for x in dims)
+        nt = n4 + n8 + n12
+        coef, exps = np.zeros((KC, nt)), np.zeros(nt, np.int32)
+        if nt:
+            self._chk(self._lib.grape_get_seg_table(self._h, dims.ctypes.data, coef.ctypes.data, exps.ctypes.data))
+        ex = np.stack([(exps >> (4 * l)) & 15 for l in range(self.L)], axis=1) if nt else np.zeros((0, self.L), np.int32)
+        return coef[:, :n4], coef[:, n4:n4 + n8], coef[:, n4 + n8:], ex
 
 
 def liouvillian(H, cops=()):

@@ -30,7 +30,9 @@ batch flags lies behind `batch_flag`: the degree M every cell of the batch is ce
 M - 1 orders if the Taylor terms are not below the tolerance by then, and pass 2 runs the SAME recursion with the scalars
 (omega_a, sigma_a) of a degree-M polynomial whose derivative is within 2e-16 of exp's on the certified segment (M = 16 for
 1.36: 31 applications of H where the Taylor sum takes 2 x 18..21).  Pass 2 reads its two scalars per order from a table of
-pairs behind 1 / m (Taylor: both 1 / (a + 1), the same bits as before)."""
+pairs behind 1 / m (Taylor: both 1 / (a + 1), the same bits as before).  The tables are indexed by M - ECON_MIN, the
+smallest degree of the header: 15, for cells the plan certifies for a spectral radius <= 1.11 from three trace moments
+(t16_seg_certified, grape_kernels.hip.h): 29 applications."""
 import os
 import struct
 import sys
@@ -46,7 +48,15 @@ NTILE = NT * (NT + 1) // 2
 MAT_B = NTILE * 2 * TILE_B       # bytes of an operator in LDS (43520)
 KERNARG = 160
 VPLANE_B = NP * 16 * 16          # bytes of one parked term (64 x 16 complex, interleaved)
-ECON_MIN = 16                    # smallest degree of an economized polynomial (grape_econ_coeffs.h: ECON_DEG; at most 31)
+
+def _econ_mindeg():
+    """ECON_MINDEG of grape_econ_coeffs.h (tools/econ_coeffs.py writes it): the tables are laid out from that degree on"""
+    import re
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "grape_econ_coeffs.h")) as f:
+        return int(re.search(r"#define ECON_MINDEG (\d+)", f.read()).group(1))
+
+
+ECON_MIN = _econ_mindeg()        # smallest degree of an economized polynomial (15); 16 tables: at most ECON_MIN + 15
 PAIRS_OFF = 32768                # the buffer behind `inv`: 1 / m (2048 doubles) | piece table of deriv3s_asm | at PAIRS_OFF the pairs
 ECON_OFF = 32768                 # (omega_a, sigma_a) of the Taylor series, a < 2048 | ECON_OFF further those of the economized
 ECON_TAB_B = 512                 # polynomial of degree M at (M - ECON_MIN) ECON_TAB_B (32 pairs each)

@@ -1,18 +1,23 @@
-// Trace tables of the generator classes: tr H^8 and tr H^6 as polynomials in the pulse values.
+// Trace tables of the generator classes: tr H^8, tr H^6 and -- for the segment certificate -- tr H^4, tr H^12 as polynomials
+// in the pulse values.
 //
 // The four-product cell (asm/gen_t16.py) certifies its spectrum by m8 = dt^8 tr H^8 <= theta^8 and m6 = dt^6 tr H^6 >= 0,
 // H = H0_k + sum_l e_l C_l.  Both traces are polynomials in e = (e_1 .. e_L) whose coefficients depend on the operators
 // alone, so t16_plan_kernel (grape_kernels.hip.h) can decide the same inequality -- with a wider margin -- from the
-// pulse values before the launch, and a cell it certifies skips the in-cell bound.  Built once per handle, next to the
-// Gram matrices, on the device, in plain HIP C++ (not on the timed path):
+// pulse values before the launch, and a cell it certifies skips the in-cell bound.  From m4, m8 and m12 the same kernel
+// certifies a cell for the segment of the shortest economized derivative series (t16_seg_certified).  Built once per handle,
+// next to the Gram matrices, on the device, in plain HIP C++ (not on the timed path):
 //
 //     H   = sum_a x_a O_a,  x_0 = 1, x_l = e_l,  O = (H0_k, C_1 .. C_L)         M = L + 1 variables, homogeneous
 //     H^2 = sum_|al|=2 x^al M2_al      M2_(a)+(b) += O_a O_b   (ordered products)
 //     H^3 = H^2 H,  H^4 = H^2 H^2      M3_al+(c) += M2_al O_c,  M4_al+be += M2_al M2_be
 //     t8[al + be] += Re tr(M4_al M4_be),   t6[al + be] += Re tr(M3_al M3_be)
+//     H^6 = H^3 H^3                    M6_al+be += M3_al M3_be                              (segment tables only)
+//     t4[al + be] += Re tr(M2_al M2_be),   t12[al + be] += Re tr(M6_al M6_be)
 //
-// At L = 2: 6 + 10 + 15 coefficient matrices from 9 + 18 + 36 products, 45 + 28 coefficients per class.  Every sum runs in
-// a fixed order (no atomics): the same operators give the same table.
+// At L = 2: 6 + 10 + 15 coefficient matrices from 9 + 18 + 36 products, 45 + 28 coefficients per class; with the segment
+// tables 28 more matrices from 100 products and 15 + 91 coefficients.  Every sum runs in a fixed order (no atomics): the same
+// operators give the same table, whichever of the two sets is built.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -54,19 +59,19 @@ struct CertJobs {
     }
 };
 
-// the jobs of one table (they depend on L alone)
+// the jobs of the tables (they depend on L alone); seg: those of the segment tables as well (M6, t4, t12)
 struct CertPlan {
-    int M, n2, n3, n4, n6, n8, nmat;   // nmat = M + n2 + n3 + n4 matrices of scratch per class
-    CertJobs mm2, mm34, tr;            // products: M2 | M3 and M4; traces: t8 | t6
-    std::vector<int> exps;             // [n8 + n6] exponents of e_1 .. e_L of every coefficient, 4 bits each
-    explicit CertPlan(int L) {
+    int M, n2, n3, n4, n6, n8, n12, nmat;   // nmat = M + n2 + n3 + n4 (+ n6) matrices of scratch per class
+    CertJobs mm2, mm34, mm6, tr;            // products: M2 | M3 and M4 | M6; traces: t8 | t6 | t4 | t12
+    std::vector<int> exps;                  // [n8 + n6 (+ n4 + n12)] exponents of e_1 .. e_L of every coefficient, 4 bits each
+    explicit CertPlan(int L, bool seg = false) {
         M = L + 1;
-        const CertMonomials m2(M, 2), m3(M, 3), m4(M, 4), m6(M, 6), m8(M, 8);
-        n2 = m2.size(); n3 = m3.size(); n4 = m4.size(); n6 = m6.size(); n8 = m8.size();
-        const int o2 = M, o3 = o2 + n2, o4 = o3 + n3;
-        nmat = o4 + n4;
-        auto var = [&](int a) { return (uint32_t)1 << (4 * a); };   // (sums of keys never carry: the degrees stay <= 8)
-        std::vector<std::vector<int>> l2(n2), l34(n3 + n4), lt(n8 + n6);
+        const CertMonomials m2(M, 2), m3(M, 3), m4(M, 4), m6(M, 6), m8(M, 8), m12(M, 12);
+        n2 = m2.size(); n3 = m3.size(); n4 = m4.size(); n6 = m6.size(); n8 = m8.size(); n12 = seg ? m12.size() : 0;
+        const int o2 = M, o3 = o2 + n2, o4 = o3 + n3, o6 = o4 + n4;
+        nmat = o6 + (seg ? n6 : 0);
+        auto var = [&](int a) { return (uint32_t)1 << (4 * a); };   // (sums of keys never carry: the degrees stay <= 12)
+        std::vector<std::vector<int>> l2(n2), l34(n3 + n4), l6(seg ? n6 : 0), lt(n8 + n6 + (seg ? n4 + n12 : 0));
         for (int a = 0; a < M; ++a)
             for (int b = 0; b < M; ++b) { auto &l = l2[m2.index.at(var(a) + var(b))]; l.push_back(a); l.push_back(b); }
         for (int i = 0; i < n2; ++i)
@@ -77,9 +82,21 @@ struct CertPlan {
             for (int j = 0; j < n4; ++j) { auto &l = lt[m8.index.at(m4.key[i] + m4.key[j])]; l.push_back(o4 + i); l.push_back(o4 + j); }
         for (int i = 0; i < n3; ++i)
             for (int j = 0; j < n3; ++j) { auto &l = lt[n8 + m6.index.at(m3.key[i] + m3.key[j])]; l.push_back(o3 + i); l.push_back(o3 + j); }
-        mm2.from(l2); mm34.from(l34); tr.from(lt);
+        if (seg) {
+            for (int i = 0; i < n3; ++i)
+                for (int j = 0; j < n3; ++j) { auto &l = l6[m6.index.at(m3.key[i] + m3.key[j])]; l.push_back(o3 + i); l.push_back(o3 + j); }
+            for (int i = 0; i < n2; ++i)
+                for (int j = 0; j < n2; ++j) { auto &l = lt[n8 + n6 + m4.index.at(m2.key[i] + m2.key[j])]; l.push_back(o2 + i); l.push_back(o2 + j); }
+            for (int i = 0; i < n6; ++i)
+                for (int j = 0; j < n6; ++j) { auto &l = lt[n8 + n6 + n4 + m12.index.at(m6.key[i] + m6.key[j])]; l.push_back(o6 + i); l.push_back(o6 + j); }
+        }
+        mm2.from(l2); mm34.from(l34); mm6.from(l6); tr.from(lt);
         for (int i = 0; i < n8; ++i) exps.push_back((int)(m8.key[i] >> 4));
         for (int i = 0; i < n6; ++i) exps.push_back((int)(m6.key[i] >> 4));
+        if (seg) {
+            for (int i = 0; i < n4; ++i) exps.push_back((int)(m4.key[i] >> 4));
+            for (int i = 0; i < n12; ++i) exps.push_back((int)(m12.key[i] >> 4));
+        }
     }
 };
 

@@ -231,7 +231,7 @@ __global__ void __launch_bounds__(256) deriv3_kernel(Deriv3Args g) {
             }
             if (!converged && capb != mcap) {   // certified: the deg - 1 orders formed are all the polynomial needs
                 M = deg; converged = 1;
-                pairs = a.econ_pairs + (size_t)(deg - 16) * 64;
+                pairs = a.econ_pairs + (size_t)(deg - ECON_MINDEG) * 64;
             }
             // ---- pass 2: w_{M-1} = chi(t_{n+1}), w_{a-1} = chi + (i dt / (a+1)) H^dagger w_a ----
             Strip<NT> chi;

@@ -145,6 +145,15 @@ struct grape_handle {
     double *d_cert = nullptr;           // [KC][cert_n8 + cert_n6] coefficients
     int *d_cert_exp = nullptr;          // [cert_n8 + cert_n6] exponents of e_1 .. e_L of every coefficient, 4 bits each
     int cert_n8 = 0, cert_n6 = 0;
+    // tables of the segment certificate: tr H^4 | tr H^12 (and tr H^8, the table above when the handle has it).  From three
+    // moments the plan certifies cells for the segment of the shortest economized derivative series (ECON_SEG_THETA,
+    // t16_seg_certified); deriv_econ_kernel gives those cells its degree.  Assembly route with the economized series,
+    // 1 <= L <= 2; GRAPE_DERIV_SEG=0: no tables, certified cells take the degree of their verdict
+    double *d_seg = nullptr;            // [KC][seg_n4 + seg_n12] coefficients
+    double *d_seg8 = nullptr;           // tr H^8 of class kc at d_seg8 + kc seg8_stride: d_cert, or a table of its own
+    int *d_seg_exp = nullptr;           // [seg_n8 | n6 of the plan | seg_n4 + seg_n12] exponents, laid out like CertPlan::exps
+    int seg_n8 = 0, seg_n4 = 0, seg_n12 = 0, seg8_stride = 0, seg_exp_off = 0;
+    int *d_segplan = nullptr;           // [KC * N_T] 1: the plan of the last evaluation certified the cell for ECON_SEG_THETA
     // the four-product route as hand-allocated assembly (asm/gen_t16.py; GRAPE_EXPM_ASM=0: the C++ kernel): four tiles
     // per side, Hermitian generators, controls shared by the trajectories
     bool asm16 = false;
@@ -242,9 +251,10 @@ struct grape_handle {
     // four-product exponential kernel of THIS evaluation has certified (verdict 0 without scaling: spectral radius <= 1.36)
     // take a degree-16 polynomial whose derivative is within 2e-16 of exp's on that segment where the Taylor sum needs
     // 19-21 terms.  Exact-derivative route only (:taylor is the reference's recursion, term by term), default tolerance
-    // or looser... a tighter one keeps the Taylor sum.  GRAPE_DERIV_ECON=0: off.
+    // or looser... a tighter one keeps the Taylor sum.  GRAPE_DERIV_ECON=0: off.  Cells the plan certifies for 1.11 as well
+    // (d_segplan above) take degree 15.
     bool deriv_econ = false;
-    const double *d_econ_pairs = nullptr;   // device: (omega, sigma) of the economized polynomials, degree M at 64 (M - 16) doubles
+    const double *d_econ_pairs = nullptr;   // device: (omega, sigma) of the economized polynomials, degree M at 64 (M - ECON_MINDEG) doubles
     int *d_celldeg = nullptr;    // blocked path: [KC * N_T] degree named by lg_t18_decide_kernel for every cell
     double sub_theta = 0.0;      // threshold of deriv_substeps (0: off, gradient_method = :taylor mirrors the reference)
     int sq_plan = 2;             // blocked path: squaring launches issued per chunk (adapted by grape_check, see expm_large)
@@ -3160,6 +3170,8 @@ int grape_create(grape_handle **out, const grape_problem *p) try {
         grape_t16_walks(h->KC, N_T, h->asm_blocks, tab.data());
         CCHK(h->mem.alloc(&h->d_wgtab, tab.size()));
         CCHK(h->mem.alloc(&h->d_splan, (size_t)ncell));
+        // (zero for good on a handle whose plan writes no plan words -- GRAPE_EXPM_CERT=0 with GRAPE_EXPM_SQ=0 -- : the
+        // assembly cells, deriv_econ_kernel and grape_get_work read "no squarings, not certified" from it)
         CCHK(hipMemset(h->d_splan, 0, (size_t)ncell * sizeof(int)));
         CCHK(hipMemcpy(h->d_wgtab, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice));
         const char *envw = getenv("GRAPE_EXPM_WALK"), *envq = getenv("GRAPE_EXPM_SQ");
@@ -3253,19 +3265,35 @@ int grape_create(grape_handle **out, const grape_problem *p) try {
         CCHK(h->mem.alloc(&h->d_gram, gram.size()));
         CCHK(hipMemcpy(h->d_gram, gram.data(), gram.size() * 8, hipMemcpyHostToDevice));
         // ... and the trace tables of the same operators (grape_cert.hip.h; like the Gram matrices they do not depend on dt)
-        const char *envc = getenv("GRAPE_EXPM_CERT");
-        if (h->asm16 && L >= 1 && L <= GRAPE_CERT_LMAX && !(envc && atoi(envc) == 0)) {
-            const CertPlan pl(L);
-            const int nt = pl.n8 + pl.n6;
-            h->cert_n8 = pl.n8; h->cert_n6 = pl.n6;
-            CCHK(h->mem.alloc(&h->d_cert, (size_t)KCn * nt));
-            CCHK(h->mem.alloc(&h->d_cert_exp, (size_t)nt));
-            CCHK(hipMemcpy(h->d_cert_exp, pl.exps.data(), (size_t)nt * sizeof(int), hipMemcpyHostToDevice));
+        // (the tables of the segment certificate come out of the same build; each set has its own switch)
+        const char *envc = getenv("GRAPE_EXPM_CERT"), *envg = getenv("GRAPE_DERIV_SEG");
+        static_assert(T16_PLAN_LMAX == GRAPE_CERT_LMAX, "power table of t16_plan_kernel");
+        const bool want_cert = h->asm16 && L >= 1 && L <= GRAPE_CERT_LMAX && !(envc && atoi(envc) == 0);
+        const bool want_seg = h->asm16 && h->deriv_econ && L >= 1 && L <= 2 && !(envg && atoi(envg) == 0);
+        if (want_cert || want_seg) {
+            const CertPlan pl(L, want_seg);
+            const int nt = pl.n8 + pl.n6, ns = pl.n4 + pl.n12;
+            if (want_cert) {
+                h->cert_n8 = pl.n8; h->cert_n6 = pl.n6;
+                CCHK(h->mem.alloc(&h->d_cert, (size_t)KCn * nt));
+                CCHK(h->mem.alloc(&h->d_cert_exp, (size_t)nt));
+                CCHK(hipMemcpy(h->d_cert_exp, pl.exps.data(), (size_t)nt * sizeof(int), hipMemcpyHostToDevice));
+            }
+            if (want_seg) {
+                h->seg_n8 = pl.n8; h->seg_n4 = pl.n4; h->seg_n12 = pl.n12; h->seg_exp_off = nt;
+                CCHK(h->mem.alloc(&h->d_seg, (size_t)KCn * ns));
+                CCHK(h->mem.alloc(&h->d_seg_exp, pl.exps.size()));
+                CCHK(hipMemcpy(h->d_seg_exp, pl.exps.data(), pl.exps.size() * sizeof(int), hipMemcpyHostToDevice));
+                if (want_cert) { h->d_seg8 = h->d_cert; h->seg8_stride = nt; }
+                else { CCHK(h->mem.alloc(&h->d_seg8, (size_t)KCn * pl.n8)); h->seg8_stride = pl.n8; }
+                CCHK(h->mem.alloc(&h->d_segplan, (size_t)KCn * N_T));
+                CCHK(hipMemset(h->d_segplan, 0, (size_t)KCn * N_T * sizeof(int)));
+            }
             DeviceBufs tmp;   // (scratch of the build: released when it is done)
-            int *d_job[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-            const std::vector<int> *job[6] = {&pl.mm2.row, &pl.mm2.pair, &pl.mm34.row, &pl.mm34.pair, &pl.tr.row, &pl.tr.pair};
-            for (int i = 0; i < 6; ++i) {
-                CCHK(tmp.alloc(&d_job[i], job[i]->size()));
+            int *d_job[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+            const std::vector<int> *job[8] = {&pl.mm2.row, &pl.mm2.pair, &pl.mm34.row, &pl.mm34.pair, &pl.tr.row, &pl.tr.pair, &pl.mm6.row, &pl.mm6.pair};
+            for (int i = 0; i < 8; ++i) {
+                CCHK(tmp.alloc(&d_job[i], std::max<size_t>(1, job[i]->size())));
                 CCHK(hipMemcpy(d_job[i], job[i]->data(), job[i]->size() * sizeof(int), hipMemcpyHostToDevice));
             }
             // classes per pass: 64 MB of coefficient matrices at a time
@@ -3280,8 +3308,19 @@ int grape_create(grape_handle **out, const grape_problem *p) try {
                 hipLaunchKernelGGL(cert_mm_kernel, dim3((unsigned)pl.n2, nc), dim3(256), 0, 0, d_scr, pl.nmat, N, pl.M, (const int *)d_job[0], (const int *)d_job[1]);
                 hipLaunchKernelGGL(cert_mm_kernel, dim3((unsigned)(pl.n3 + pl.n4), nc), dim3(256), 0, 0, d_scr, pl.nmat, N, pl.M + pl.n2, (const int *)d_job[2],
                                    (const int *)d_job[3]);
-                hipLaunchKernelGGL(cert_trace_kernel, dim3((unsigned)nt, nc), dim3(256), 0, 0, (const double2 *)d_scr, pl.nmat, N, (const int *)d_job[4],
-                                   (const int *)d_job[5], nt, h->d_cert + (size_t)kc0 * nt);
+                // t8 | t6 into the certificate's table, or t8 alone into the segment tables' own; the same sums either way
+                if (want_cert)
+                    hipLaunchKernelGGL(cert_trace_kernel, dim3((unsigned)nt, nc), dim3(256), 0, 0, (const double2 *)d_scr, pl.nmat, N, (const int *)d_job[4],
+                                       (const int *)d_job[5], nt, h->d_cert + (size_t)kc0 * nt);
+                else
+                    hipLaunchKernelGGL(cert_trace_kernel, dim3((unsigned)pl.n8, nc), dim3(256), 0, 0, (const double2 *)d_scr, pl.nmat, N, (const int *)d_job[4],
+                                       (const int *)d_job[5], pl.n8, h->d_seg8 + (size_t)kc0 * pl.n8);
+                if (want_seg) {
+                    hipLaunchKernelGGL(cert_mm_kernel, dim3((unsigned)pl.n6, nc), dim3(256), 0, 0, d_scr, pl.nmat, N, pl.M + pl.n2 + pl.n3 + pl.n4,
+                                       (const int *)d_job[6], (const int *)d_job[7]);
+                    hipLaunchKernelGGL(cert_trace_kernel, dim3((unsigned)ns, nc), dim3(256), 0, 0, (const double2 *)d_scr, pl.nmat, N,
+                                       (const int *)d_job[4] + nt, (const int *)d_job[5], ns, h->d_seg + (size_t)kc0 * ns);
+                }
                 CCHK(hipGetLastError());
             }
             CCHK(hipDeviceSynchronize());
@@ -3435,7 +3474,18 @@ int grape_forward_device(grape_handle *h, const double *d_pulsevals, double *d_o
                     pa.sq_on = h->asm_sq ? 1 : 0;
                     pa.cert = h->d_cert; pa.cert_exp = h->d_cert_exp; pa.n8 = h->cert_n8; pa.n6 = h->cert_n6;
                     pa.verdict = h->d_cellflag;
-                    hipLaunchKernelGGL(t16_plan_kernel, dim3((unsigned)((ncell + 255) / 256)), dim3(256), 0, s, pa);
+                    pa.seg = h->d_seg; pa.seg8 = h->d_seg8; pa.seg8_stride = h->seg8_stride; pa.seg8_exp = h->d_seg_exp;
+                    pa.seg_exp = h->d_seg_exp ? h->d_seg_exp + h->seg_exp_off : nullptr;
+                    pa.s8 = h->seg_n8; pa.n4 = h->seg_n4; pa.n12 = h->seg_n12; pa.segplan = h->d_segplan;
+                    const unsigned plan_blocks = (unsigned)(h->KC * ((h->N_T + T16_PLAN_TPB - 1) / T16_PLAN_TPB));
+                    const size_t plan_lds = t16_plan_lds(pa);
+                    switch (plan_lds ? h->L : 0) {   // (tables: 1 <= L <= T16_PLAN_LMAX)
+                        case 1: hipLaunchKernelGGL(t16_plan_kernel<1>, dim3(plan_blocks), dim3(T16_PLAN_TPB), plan_lds, s, pa); break;
+                        case 2: hipLaunchKernelGGL(t16_plan_kernel<2>, dim3(plan_blocks), dim3(T16_PLAN_TPB), plan_lds, s, pa); break;
+                        case 3: hipLaunchKernelGGL(t16_plan_kernel<3>, dim3(plan_blocks), dim3(T16_PLAN_TPB), plan_lds, s, pa); break;
+                        case 4: hipLaunchKernelGGL(t16_plan_kernel<4>, dim3(plan_blocks), dim3(T16_PLAN_TPB), plan_lds, s, pa); break;
+                        default: hipLaunchKernelGGL(t16_plan_kernel<0>, dim3(plan_blocks), dim3(T16_PLAN_TPB), 0, s, pa); break;
+                    }
                     HIPCHK(h, hipGetLastError());
                 }
                 // (three tiles per side, four-product variant: 256 registers and 72 KB -- two workgroups per CU)
@@ -3497,8 +3547,9 @@ int grape_forward_device(grape_handle *h, const double *d_pulsevals, double *d_o
             DerivEconArgs ec{};
             ec.verdict = h->d_cellflag; ec.splan = h->d_splan; ec.cls = h->d_cls; ec.flags = h->d_flags;
             ec.cell_deg = h->large ? h->d_celldeg : nullptr;
-            ec.deg0 = ECON_DEG[0]; ec.deg1 = ECON_DEG[ECON_NSETS - 1];
-            static_assert(ECON_NSETS == 4, "segments 1.36 (verdict), 1.6, 2.0 (blocked path), 2.72 (one planned squaring)");
+            ec.deg0 = ECON_DEG[ECON_VERDICT_SET]; ec.deg1 = ECON_DEG[ECON_NSETS - 1];
+            ec.segplan = h->large ? nullptr : h->d_segplan; ec.deg_seg = ECON_DEG[0];
+            static_assert(ECON_NSETS == 5, "segments 1.11 (three-moment certificate), 1.36 (verdict), 1.6, 2.0 (blocked path), 2.72 (one planned squaring)");
             ec.K = h->K; ec.KC = h->KC; ec.N_T = h->N_T; ec.batches_per_k = (h->N_T + 15) / 16;
             ec.nbatch_total = h->K * ec.batches_per_k; ec.batch_econ = h->d_batchflag + ec.nbatch_total;
             hipLaunchKernelGGL(deriv_econ_kernel, dim3((unsigned)((ec.nbatch_total + 255) / 256)), dim3(256), 0, s, ec);
@@ -4580,10 +4631,10 @@ int grape_get_work(grape_handle *h, double *out, int n) try {
     if (!h || !out || n < 4) return GRAPE_ERR_INVALID;
     if (h->open) return open_work(h, out, n);
     if (!h->shards.empty()) {   // every entry is a count: the shards add up
-        const int m = n < 20 ? n : 20;
+        const int m = n < 21 ? n : 21;
         std::fill(out, out + m, 0.0);
         for (grape_handle *c : h->shards) {
-            double cw[20] = {0.};
+            double cw[21] = {0.};
             const int rc = grape_get_work(c, cw, m);
             if (rc < 0) return multi_fail(h, c, rc);
             for (int i = 0; i < m; ++i) out[i] = (i == 15 || i == 16 || i == 18) ? cw[i] : out[i] + cw[i];   // ([15], [16]: kernel ids, the same in every shard)
@@ -4660,19 +4711,35 @@ int grape_get_work(grape_handle *h, double *out, int n) try {
     }
     if (n > 18) out[18] = h->scan16 ? (double)h->scan_Bk : 0.0;   // block length of the scanned sweeps (N <= 16), 0: sequential sweeps
     // cells of the last evaluation whose spectrum was certified before the launch (trace tables, t16_plan_kernel): the bits are
-    // still in the plan; an evaluation whose plan skipped the four-product route used none of them
+    // still in the plan; an evaluation whose plan skipped the four-product route used none of them.  [20]: cells (per
+    // trajectory) that qualified for the shortest economized derivative series: verdict 0, no planned squarings, certified
+    // for ECON_SEG_THETA by the plan (deriv_econ_kernel's rule, counted from the same arrays).  One copy of the plan words
+    // and the flags serves both.
     if (n > 19) {
-        double certified = 0.0;
-        if (h->d_cert && h->d_splan && !h->series) {
+        double certified = 0.0, seg = 0.0;
+        const bool want_seg = n > 20 && h->d_segplan && h->deriv_econ;
+        if ((h->d_cert || want_seg) && h->d_splan && !h->series) {
             const size_t ncell = (size_t)h->KC * h->N_T;
             std::vector<int> plan(ncell);
             int fl[8];
             HIPCHK(h, hipMemcpy(plan.data(), h->d_splan, ncell * sizeof(int), hipMemcpyDeviceToHost));
             HIPCHK(h, hipMemcpy(fl, h->d_flags, sizeof(fl), hipMemcpyDeviceToHost));
-            if (!(4L * fl[6] > (long)ncell))
+            const bool tried = !(4L * fl[6] > (long)ncell);
+            if (tried && h->d_cert)
                 for (int w : plan) certified += (w & T16_PLAN_CERT) ? 1.0 : 0.0;
+            if (tried && want_seg) {
+                std::vector<int> sp(ncell), verdict(ncell);
+                HIPCHK(h, hipMemcpy(sp.data(), h->d_segplan, ncell * sizeof(int), hipMemcpyDeviceToHost));
+                HIPCHK(h, hipMemcpy(verdict.data(), h->d_cellflag, ncell * sizeof(int), hipMemcpyDeviceToHost));
+                for (int k = 0; k < h->K; ++k) {
+                    const size_t c0 = (size_t)(h->cls.empty() ? k : h->cls[k]) * h->N_T;
+                    for (int i = 0; i < h->N_T; ++i)
+                        seg += (sp[c0 + i] && verdict[c0 + i] == 0 && (plan[c0 + i] & T16_PLAN_SQ_MASK) == 0) ? 1.0 : 0.0;
+                }
+            }
         }
         out[19] = certified;
+        if (n > 20) out[20] = seg;
     }
     return 4;
 }
@@ -4690,6 +4757,33 @@ int grape_get_cert_table(grape_handle *h, int *dims, double *coef, int *exps) tr
     HIPCHK(h, hipSetDevice(h->device));
     if (coef) HIPCHK(h, hipMemcpy(coef, h->d_cert, (size_t)h->KC * nt * sizeof(double), hipMemcpyDeviceToHost));
     if (exps) HIPCHK(h, hipMemcpy(exps, h->d_cert_exp, (size_t)nt * sizeof(int), hipMemcpyDeviceToHost));
+    return GRAPE_OK;
+}
+GRAPE_BARRIER(h ? &h->err : &g_create_error)
+
+int grape_get_seg_table(grape_handle *h, int *dims, double *coef, int *exps) try {
+    if (!h || !dims) return GRAPE_ERR_INVALID;
+    if (h->open || !h->shards.empty()) {
+        h->err = "grape_get_seg_table: a closed handle on one device";
+        return GRAPE_ERR_INVALID;
+    }
+    const int n4 = h->seg_n4, n8 = h->seg_n8, n12 = h->seg_n12, nt = n4 + n8 + n12;
+    dims[0] = h->KC; dims[1] = n4; dims[2] = n8; dims[3] = n12;
+    if (!h->d_seg || !nt) { dims[1] = dims[2] = dims[3] = 0; return GRAPE_OK; }
+    HIPCHK(h, hipSetDevice(h->device));
+    if (coef) {   // t4 | t8 | t12 of every class, t8 from where the plan reads it (the certificate's table or the own copy)
+        HIPCHK(h, hipMemcpy2D(coef, (size_t)nt * sizeof(double), h->d_seg, (size_t)(n4 + n12) * sizeof(double), (size_t)n4 * sizeof(double),
+                              (size_t)h->KC, hipMemcpyDeviceToHost));
+        HIPCHK(h, hipMemcpy2D(coef + n4, (size_t)nt * sizeof(double), h->d_seg8, (size_t)h->seg8_stride * sizeof(double), (size_t)n8 * sizeof(double),
+                              (size_t)h->KC, hipMemcpyDeviceToHost));
+        HIPCHK(h, hipMemcpy2D(coef + n4 + n8, (size_t)nt * sizeof(double), h->d_seg + n4, (size_t)(n4 + n12) * sizeof(double), (size_t)n12 * sizeof(double),
+                              (size_t)h->KC, hipMemcpyDeviceToHost));
+    }
+    if (exps) {   // ... and the exponent words the plan reads with them
+        HIPCHK(h, hipMemcpy(exps, h->d_seg_exp + h->seg_exp_off, (size_t)n4 * sizeof(int), hipMemcpyDeviceToHost));
+        HIPCHK(h, hipMemcpy(exps + n4, h->d_seg_exp, (size_t)n8 * sizeof(int), hipMemcpyDeviceToHost));
+        HIPCHK(h, hipMemcpy(exps + n4 + n8, h->d_seg_exp + h->seg_exp_off + n4, (size_t)n12 * sizeof(int), hipMemcpyDeviceToHost));
+    }
     return GRAPE_OK;
 }
 GRAPE_BARRIER(h ? &h->err : &g_create_error)

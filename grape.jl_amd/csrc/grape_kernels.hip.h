@@ -14,6 +14,7 @@
 #include <stdint.h>
 
 #include "grape_t18_coeffs.h"   // T16_THETA (t16_certified)
+#include "grape_econ_coeffs.h"  // ECON_MINDEG, ECON_THETAS (t16_seg_certified, the readers of econ_pairs)
 
 typedef double d4 __attribute__((ext_vector_type(4)));
 
@@ -116,10 +117,53 @@ struct T16PlanArgs {
     const int *cert_exp;  // [n8 + n6]
     int n8, n6;
     int *verdict;         // [KC * N_T]: 0 is written for a certified cell, which does not write it itself
+    // the segment certificate (t16_seg_certified): nullptr / 0 on handles without its tables
+    const double *seg;    // [KC][n4 + n12]
+    const double *seg8;   // t8 of class kc at seg8 + kc seg8_stride (the table above on handles that have it)
+    const int *seg_exp;   // [n4 + n12]
+    const int *seg8_exp;  // [s8]
+    int seg8_stride, s8, n4, n12;
+    int *segplan;         // [KC * N_T]: 1 for a cell with no planned squarings whose spectral radius is certified <= ECON_THETAS[0]
 };
 // splan[cell]: bits 0..7 the planned squarings, bit 8 the cell's spectrum was certified before the launch
 #define T16_PLAN_SQ_MASK 0xFF
 #define T16_PLAN_CERT 0x100
+#define T16_PLAN_TPB 128    // cells per workgroup
+#define T16_PLAN_LMAX 4     // controls the trace tables are built for (GRAPE_CERT_LMAX)
+#define T16_PLAN_PMAX 12    // largest power of a pulse value in a monomial (tr H^12)
+typedef double T16PlanPowers[T16_PLAN_PMAX + 1][T16_PLAN_TPB];   // [l][j][thread] = e_l^j of the thread's cell (LDS)
+// p = sum_i t[i] e^ex[i] and S = sum_i |t[i]| |e^ex[i]|, which bounds everything rounding and cancellation can do to p.  The
+// monomials are products of LT entries of the power table; t and ex are the workgroup's copies in LDS.  The whole launch is
+// two waves per SIMD, so what a term costs is the latency of its dependent loads (exponent word, then the powers): eight
+// terms are fetched at a time -- a term beyond the table repeats the last one with weight zero -- and added in table order
+// (notebook 4.1d and 11.11: one term at a time took 30 us for 73 terms in the parent and 77 .. 150 us for 179).
+template <int LT>
+__device__ __forceinline__ void t16_trace_poly(const double *t, const int *ex, const int n, const T16PlanPowers *pw, double &p, double &S) {
+    const int tid = threadIdx.x;
+    double sp = 0., sa = 0.;
+    for (int i0 = 0; i0 < n; i0 += 8) {
+        unsigned x[8];
+        double c[8], mono[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            const int i = min(i0 + u, n - 1);
+            x[u] = (unsigned)ex[i];
+            c[u] = i0 + u < n ? t[i] : 0.0;
+        }
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            mono[u] = pw[0][x[u] & 15u][tid];
+#pragma unroll
+            for (int l = 1; l < LT; ++l) mono[u] *= pw[l][(x[u] >> (4 * l)) & 15u][tid];
+        }
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            sp += c[u] * mono[u];
+            sa += fabs(c[u]) * fabs(mono[u]);
+        }
+    }
+    p = sp; S = sa;
+}
 // Is the spectrum of A / 2^s, A = -i dt (H0 + sum_l e_l C_l), certainly inside the range of the four products?  The cell
 // itself (asm/gen_t16.py) tests m8 (1 + 1e-9) <= theta^8 and m6 >= 0 on m8 = dt^8 tr H^8 / 2^(8s), m6 = dt^6 tr H^6 / 2^(6s)
 // taken from its products, or the 1-norm of A^2.  tr H^8 and tr H^6 are polynomials in e with the coefficients t8 | t6 of
@@ -130,28 +174,74 @@ struct T16PlanArgs {
 // -- the cell's own inequality with a margin a thousand times its own, so a cell certified here is one the cell would
 // have passed: the results are the same bits with and without the certificate.  Cells only the 1-norm would pass are left to
 // the cell.
-__device__ __forceinline__ bool t16_certified(const double *t, const int *ex, const int n8, const int n6, const int L, const double *e,
-                                              const double dt, const int sq) {
-    double p[2] = {0., 0.}, S8 = 0.;
-    for (int i = 0; i < n8 + n6; ++i) {
-        unsigned x = (unsigned)ex[i];
-        double mono = 1.0;
-        for (int l = 0; l < L; ++l, x >>= 4)
-            for (unsigned q = x & 15u; q > 0; --q) mono *= e[l];
-        const double c = t[i];
-        p[i < n8 ? 0 : 1] += c * mono;
-        if (i < n8) S8 += fabs(c) * fabs(mono);
-    }
+__device__ __forceinline__ bool t16_certified(const double p8, const double S8, const double p6, const double dt, const int sq) {
     const double dt2 = dt * dt, dt8 = (dt2 * dt2) * (dt2 * dt2);
     constexpr double th2 = T16_THETA * T16_THETA, th8 = (th2 * th2) * (th2 * th2);
-    const double lhs = (p[0] + 0x1p-30 * S8) * dt8 * (1.0 + 1e-6), rhs = ldexp(th8, 8 * sq);
-    return lhs <= rhs && p[1] >= 0.0;
+    const double lhs = (p8 + 0x1p-30 * S8) * dt8 * (1.0 + 1e-6), rhs = ldexp(th8, 8 * sq);
+    return lhs <= rhs && p6 >= 0.0;
 }
-__global__ void __launch_bounds__(256) t16_plan_kernel(T16PlanArgs a) {
-    const int cell = blockIdx.x * 256 + threadIdx.x;
+// Is the spectral radius rho of A = -i dt H certainly at most theta = ECON_THETAS[0], the segment of the shortest economized
+// derivative series (tools/econ_coeffs.py)?  With the eigenvalues lam_i of H dt and m_p = sum lam_i^p (p even: every term
+// is >= 0) take one eigenvalue of modulus rho out of the sums; Cauchy-Schwarz on the others gives
+//     (m8 - rho^8)^2 <= (m4 - rho^4)(m12 - rho^12),     i.e.  f(rho) <= m12,   f(r) = r^12 + (m8 - r^8)^2 / (m4 - r^4).
+// f'(r) = 4 r^3 (3 r^4 - q)(r^4 - q) with q(r) = (m8 - r^8) / (m4 - r^4), and q' = 4 r^3 (q - 2 r^4) / (m4 - r^4): q falls
+// wherever q < 2 r^4.  So if q(theta) < theta^4, which is m8 < theta^4 m4, then q < r^4 and f rises on [theta, m4^(1/4)),
+// where rho must lie if it is not below theta (rho^4 <= m4; rho^4 = m4 means m8 = m4^2 >= theta^4 m4).  Then
+// f(theta) > m12 excludes rho >= theta.  The test:
+//     m4 <= theta^4                                                       (rho^4 <= m4: nothing else to show)   or
+//     m8 < theta^4 m4   and   (m12 - theta^12)(m4 - theta^4) < (m8 - theta^8)^2.
+// (A factor of the left side that is not positive says m12 <= theta^12 or m4 <= theta^4: rho <= theta again.)  The moments
+// come from the trace tables as m_p = dt^p (p_p +- 2^-30 S_p), S_p the sum of the absolute terms; every inequality is
+// taken at the unfavourable ends of these intervals with a relative 1e-6 on top, and NaN fails.  Three moments place the
+// bound within 0.1 % of m16^(1/16), 7 % below m12^(1/12) alone and 17 % below the m8^(1/8) of the cell's own verdict
+// (notebook 11.11).
+__device__ __forceinline__ bool t16_seg_certified(const double p4, const double S4, const double p8, const double S8, const double p12,
+                                                  const double S12, const double dt) {
+    constexpr double th = ECON_SEG_THETA, th2 = th * th, th4 = th2 * th2, th8 = th4 * th4, th12 = th8 * th4;
+    const double dt2 = dt * dt, dt4 = dt2 * dt2, dt8 = dt4 * dt4, dt12 = dt8 * dt4;
+    const double m4lo = (p4 - 0x1p-30 * S4) * dt4, m4hi = (p4 + 0x1p-30 * S4) * dt4;
+    const double m8lo = (p8 - 0x1p-30 * S8) * dt8, m8hi = (p8 + 0x1p-30 * S8) * dt8;
+    const double m12hi = (p12 + 0x1p-30 * S12) * dt12;
+    if (m4hi * (1.0 + 1e-6) <= th4) return true;
+    if (!(m8hi * (1.0 + 1e-6) < th4 * m4lo)) return false;
+    const double lo = m8lo - th8, hi = m8hi - th8;
+    const double gap = lo > 0.0 ? lo : hi < 0.0 ? -hi : 0.0;     // least |m8 - theta^8| over the interval of m8
+    const double lhs = (m12hi - th12) * (m4hi - th4);
+    return (lhs > 0.0 ? lhs * (1.0 + 1e-6) : lhs) < gap * gap;
+}
+// one thread per cell, the cells of a workgroup belong to one generator class: its tables are copied into LDS once, behind
+// the power table.  Dynamic LDS: t16_plan_lds() bytes; the launch and the kernel take the layout from T16PlanLds.
+struct T16PlanLds {
+    int nc, n8own, ns;   // staged entries: t8 | t6 of the certificate, a t8 of the segment tables' own when there is no certificate, t4 | t12
+    __host__ __device__ explicit T16PlanLds(const T16PlanArgs &a)
+        : nc(a.cert ? a.n8 + a.n6 : 0), n8own((a.seg && !a.cert) ? a.s8 : 0), ns(a.seg ? a.n4 + a.n12 : 0) {}
+    __host__ __device__ int entries() const { return nc + n8own + ns; }
+};
+__host__ __device__ inline size_t t16_plan_lds(const T16PlanArgs &a) {
+    if (!(a.cert || a.seg) || a.L > T16_PLAN_LMAX) return 0;
+    return (size_t)a.L * sizeof(T16PlanPowers) + (size_t)T16PlanLds(a).entries() * (sizeof(double) + sizeof(int));
+}
+// LT: the controls L of a handle with tables (1 .. T16_PLAN_LMAX), 0: no tables
+template <int LT>
+__global__ void __launch_bounds__(T16_PLAN_TPB) t16_plan_kernel(T16PlanArgs a) {
+    extern __shared__ __attribute__((aligned(16))) double plan_sm[];   // powers [L] | coefficients | exponents
+    const int tid = threadIdx.x, nbx = (a.N_T + T16_PLAN_TPB - 1) / T16_PLAN_TPB;
+    const int kc = blockIdx.x / nbx, n = (blockIdx.x - kc * nbx) * T16_PLAN_TPB + tid;
+    constexpr bool tables = LT > 0;
+    T16PlanPowers *pw = (T16PlanPowers *)plan_sm;
+    const T16PlanLds ly(a);
+    const int nc = ly.nc, n8own = ly.n8own, ns = ly.ns;
+    double *tt = plan_sm + (size_t)LT * (T16_PLAN_PMAX + 1) * T16_PLAN_TPB;
+    int *tx = (int *)(tt + ly.entries());
+    if (tables) {
+        for (int i = tid; i < nc; i += T16_PLAN_TPB) { tt[i] = a.cert[(size_t)kc * nc + i]; tx[i] = a.cert_exp[i]; }
+        for (int i = tid; i < n8own; i += T16_PLAN_TPB) { tt[nc + i] = a.seg8[(size_t)kc * a.seg8_stride + i]; tx[nc + i] = a.seg8_exp[i]; }
+        for (int i = tid; i < ns; i += T16_PLAN_TPB) { tt[nc + n8own + i] = a.seg[(size_t)kc * ns + i]; tx[nc + n8own + i] = a.seg_exp[i]; }
+        __syncthreads();
+    }
     bool out = false;
-    if (cell < a.KC * a.N_T) {
-        const int kc = cell / a.N_T, n = cell - kc * a.N_T, M = a.L + 1;
+    if (n < a.N_T) {
+        const int cell = kc * a.N_T + n, M = a.L + 1;
         const double *G = a.gram + (size_t)kc * (M * M + M), *kap = G + M * M;
         double e[9];
         e[0] = 1.0;
@@ -165,19 +255,45 @@ __global__ void __launch_bounds__(256) t16_plan_kernel(T16PlanArgs a) {
         const double dt = a.dts[n];
         const double r = 2.0 * fabs(dt) * sqrt(fmax(m2, 0.0) / (double)a.N) * (w > 0.0 ? wk / w : 1.0);
         out = !(r <= T16_PLAN_R);
-        if (a.splan) {
-            int sq = 0;
-            if (out && a.sq_on) {
-                double rs = r;
-                while (sq < T16_PLAN_SMAX && !(rs <= T16_PLAN_RS)) { rs *= 0.5; ++sq; }
-                out = !(rs <= T16_PLAN_RS);      // (NaN included)
-                if (out) sq = 0;
+        int sq = 0;
+        if (a.splan && out && a.sq_on) {
+            double rs = r;
+            while (sq < T16_PLAN_SMAX && !(rs <= T16_PLAN_RS)) { rs *= 0.5; ++sq; }
+            out = !(rs <= T16_PLAN_RS);      // (NaN included)
+            if (out) sq = 0;
+        }
+        if (tables)
+            for (int l = 0; l < LT; ++l) {
+                double x = 1.0;
+                for (int j = 0; j <= T16_PLAN_PMAX; ++j, x *= e[1 + l]) pw[l][j][tid] = x;
             }
+        double p8 = 0., S8 = 0.;
+        const bool have8 = a.splan && a.cert;
+        if (a.splan) {
             // the certificate of the cell as it will be exponentiated (A / 2^sq); the estimate above keeps its two roles, the
             // squaring plan and the "more than a quarter out of range" rule
-            const bool cert = a.cert && t16_certified(a.cert + (size_t)kc * (a.n8 + a.n6), a.cert_exp, a.n8, a.n6, a.L, e + 1, dt, sq);
+            bool cert = false;
+            if (tables && a.cert) {
+                double p6, S6;
+                t16_trace_poly<LT>(tt, tx, a.n8, pw, p8, S8);
+                t16_trace_poly<LT>(tt + a.n8, tx + a.n8, a.n6, pw, p6, S6);
+                cert = t16_certified(p8, S8, p6, dt, sq);
+            }
             if (cert) a.verdict[cell] = 0;
             a.splan[cell] = sq | (cert ? T16_PLAN_CERT : 0);
+        }
+        if (tables && a.seg) {
+            bool seg = false;
+            if (sq == 0) {
+                const double *t = tt + nc + n8own;
+                const int *x = tx + nc + n8own;
+                double p4, S4, p12, S12;
+                if (!have8) t16_trace_poly<LT>(a.cert ? tt : tt + nc, a.cert ? tx : tx + nc, a.s8, pw, p8, S8);
+                t16_trace_poly<LT>(t, x, a.n4, pw, p4, S4);
+                t16_trace_poly<LT>(t + a.n4, x + a.n4, a.n12, pw, p12, S12);
+                seg = t16_seg_certified(p4, S4, p8, S8, p12, S12, dt);
+            }
+            a.segplan[cell] = seg ? 1 : 0;
         }
     }
     const unsigned long long m = __ballot(out);
@@ -3472,7 +3588,8 @@ __global__ void deriv_flag_kernel(DerivFlagArgs a) {
 // EVERY cell of the batch is certified for, 0: none.  Certificates of this evaluation's exponential kernels:
 //   * four-product assembly kernels (asm/gen_t16.py): verdict 0 = spectral radius of the exponentiated matrix <= T16_THETA
 //     = 1.36; a cell exponentiated as A / 2 (one planned squaring) is certified for 2.72; more squarings: none.  A route
-//     that was not tried in this evaluation has written no verdicts.
+//     that was not tried in this evaluation has written no verdicts.  A cell with verdict 0 and no squarings that the plan
+//     has certified for the shortest segment (segplan, t16_seg_certified) takes that segment's degree.
 //   * blocked path, Hermitian generators (lg_t18_decide_kernel): cell_deg, from the norms of A^2 and A^6.
 // Of the degrees of a batch's cells the largest (its segment holds the others).
 struct DerivEconArgs {
@@ -3481,6 +3598,8 @@ struct DerivEconArgs {
     int K, KC, N_T, batches_per_k, nbatch_total;
     int deg0, deg1;                             // degrees of the segments 1.36 and 2.72 (grape_econ_coeffs.h)
     int *batch_econ;                            // [nbatch_total]
+    const int *segplan;                         // nullptr or [KC * N_T]: cells certified for the segment of degree deg_seg
+    int deg_seg;
 };
 __global__ void deriv_econ_kernel(DerivEconArgs a) {
     const int batch = blockIdx.x * blockDim.x + threadIdx.x;
@@ -3496,6 +3615,7 @@ __global__ void deriv_econ_kernel(DerivEconArgs a) {
         else {
             const int sq = a.splan ? (a.splan[cell] & T16_PLAN_SQ_MASK) : 0;    // (the compiled four-product kernel plans no squarings)
             d = a.verdict[cell] != 0 ? 0 : sq == 0 ? a.deg0 : sq == 1 ? a.deg1 : 0;
+            if (d == a.deg0 && sq == 0 && a.segplan && a.segplan[cell]) d = a.deg_seg;
         }
         ok = d > 0;
         deg = max(deg, d);
@@ -3779,7 +3899,7 @@ struct Deriv2Args {
     int deep_redo;
     // round 6: the degrees of the economized series lie behind the batch flags, batch_flag[nbatch_total + batch]
     // (deriv_econ_kernel; Hermitian operators only).  The assembly kernels find the tables behind their 1 / m; the
-    // compiled ones (deriv3_kernel, deriv2_kernel) through econ_pairs: degree M at 64 (M - 16) doubles, (omega_a, sigma_a)
+    // compiled ones (deriv3_kernel, deriv2_kernel) through econ_pairs: degree M at 64 (M - ECON_MINDEG) doubles, (omega_a, sigma_a)
     int batch_econ;
     const double *econ_pairs;
 #ifdef GRAPE_DIAG
@@ -4006,7 +4126,7 @@ __global__ void __launch_bounds__((NP / 16 <= 8 ? NP / 16 : 8) * 64) deriv2_kern
         }
         if (!converged && capb != mcap) {   // certified: the deg - 1 orders formed are all the polynomial needs
             M = deg; converged = 1;
-            pairs = a.econ_pairs + (size_t)(deg - 16) * 64;
+            pairs = a.econ_pairs + (size_t)(deg - ECON_MINDEG) * 64;
         }
         }   // !use_g
         // orders a = 0..M-1 enter the sum; u_M is below the tolerance (or the cap was hit: flagged below)

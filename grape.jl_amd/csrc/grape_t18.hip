@@ -295,15 +295,15 @@ hipError_t asm_function(int dev, hipFunction_t *fn, hipFunction_t *fn_d3 = nullp
         // them the piece table of the streamed kernel (gen_d3s.py piece_table: source offset of piece 4 tile + 2 plane + half)
         // round 6: at D3_PAIRS_OFF bytes the scalars (omega_a, sigma_a) of pass 2, a < D3_INV_TABLE, of the Taylor series (both
         // 1 / (a + 1)); D3_ECON_OFF bytes further those of the economized series (grape_econ_coeffs.h, tools/econ_coeffs.py)
-        static_assert(D3_PAIRS_OFF >= (D3_INV_TABLE + 20) * 8 && D3_ECON_OFF == D3_INV_TABLE * 16 && ECON_MAXDEG <= 31, "layout of gen_d3.py");
+        static_assert(D3_PAIRS_OFF >= (D3_INV_TABLE + 20) * 8 && D3_ECON_OFF == D3_INV_TABLE * 16 && ECON_MAXDEG - ECON_MINDEG <= 15, "layout of gen_d3.py");
         std::vector<double> tab((D3_PAIRS_OFF + D3_ECON_OFF + 16 * D3_ECON_TAB_B) / 8);
         tab[0] = 0.0;
         for (int i = 1; i < D3_INV_TABLE; ++i) tab[i] = 1.0 / (double)i;
         for (int a = 0; a < D3_INV_TABLE; ++a) tab[D3_PAIRS_OFF / 8 + 2 * a] = tab[D3_PAIRS_OFF / 8 + 2 * a + 1] = 1.0 / (double)(a + 1);
-        for (int i = 0; i < ECON_NSETS; ++i)   // the polynomial of degree M at (M - 16) D3_ECON_TAB_B
+        for (int i = 0; i < ECON_NSETS; ++i)   // the polynomial of degree M at (M - ECON_MINDEG) D3_ECON_TAB_B
             for (int a = 0; a < ECON_DEG[i]; ++a)
                 for (int j = 0; j < 2; ++j)
-                    tab[(D3_PAIRS_OFF + D3_ECON_OFF + (ECON_DEG[i] - 16) * D3_ECON_TAB_B) / 8 + 2 * a + j] = ECON_TABS[i][a][j];
+                    tab[(D3_PAIRS_OFF + D3_ECON_OFF + (ECON_DEG[i] - ECON_MINDEG) * D3_ECON_TAB_B) / 8 + 2 * a + j] = ECON_TABS[i][a][j];
         int *pt = (int *)(tab.data() + D3_INV_TABLE);
         int np_ = 0;
         for (int ti = 0; ti < 4; ++ti)
@@ -379,7 +379,7 @@ hipError_t launch_d3_asm(const Deriv3Args &g, hipStream_t s, int blocks, bool ge
 }  // namespace
 
 // the tables of the economized derivative series on the current device, for the compiled kernels: degree M at
-// 64 (M - 16) doubles from the pointer, (omega_a, sigma_a); nullptr when the module cannot be loaded
+// 64 (M - ECON_MINDEG) doubles from the pointer, (omega_a, sigma_a); nullptr when the module cannot be loaded
 extern "C" const double *grape_econ_pairs(void) {
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) return nullptr;

@@ -312,7 +312,11 @@ int grape_reset_timings(grape_handle *h);
  * per generator class (Hermitian generators, 1 <= L <= 4, assembly route); the plan of an evaluation tests
  * (p8 + 2^-30 S8) dt^8 (1 + 1e-6) <= (1.36 * 2^s)^8 and p6 >= 0 on them and a cell that passes skips the spectral bound it
  * would otherwise compute from its own products -- the same inequality with a narrower margin, so the results are the same
- * bits.  0 on handles without tables, with GRAPE_EXPM_CERT=0, and when the plan skipped the route
+ * bits.  0 on handles without tables, with GRAPE_EXPM_CERT=0, and when the plan skipped the route,
+ * [20] the cells (counted per trajectory) of the last evaluation that qualified for the shortest economized derivative series
+ * (degree 15, spectral radius <= 1.11): verdict 0, no planned squarings, and certified by the plan from tr H^4, tr H^8 and
+ * tr H^12 (tables of grape_create: Hermitian generators, 1 <= L <= 2, assembly route; GRAPE_DERIV_SEG=0: no tables).  A batch of
+ * 16 cells still runs the largest degree of its cells (grape_get_work[4] says what ran).  0 on handles without these tables
  * (entries beyond n are not written). */
 int grape_get_work(grape_handle *h, double *out, int n);
 
@@ -321,6 +325,13 @@ int grape_get_work(grape_handle *h, double *out, int n);
  * of every class; exps (NULL: not wanted) [n8 + n6]: the exponents of e_1 .. e_L of the monomial a coefficient multiplies, four
  * bits each, e_1 lowest (e_l = pulse value times shape).  GRAPE_ERR_INVALID: h or dims NULL, an open handle, several devices. */
 int grape_get_cert_table(grape_handle *h, int *dims, double *coef, int *exps);
+
+/* The tables behind grape_get_work[20] (diagnostics, tests), as the plan of an evaluation reads them.  dims [4] = KC, n4, n8, n12:
+ * generator classes, coefficients of tr H^4, tr H^8 and tr H^12 (15, 45 and 91 at L = 2; all 0: this handle has no segment tables).
+ * coef (NULL: not wanted) [KC][n4 + n8 + n12]: t4 | t8 | t12 of every class -- t8 is the certificate's table above when the handle
+ * has it, the segment tables' own copy with GRAPE_EXPM_CERT=0; exps (NULL: not wanted) [n4 + n8 + n12]: exponents as above.
+ * GRAPE_ERR_INVALID: h or dims NULL, an open handle, several devices. */
+int grape_get_seg_table(grape_handle *h, int *dims, double *coef, int *exps);
 
 /* ABI v7.  Derivative of J with respect to the time steps dt_n = tlist[n+1] - tlist[n] (0-based n < N_T), for the duration
  * loop around GRAPE (INTEGRATION.md "Optimising the duration").  For piecewise-constant generators dU_n/d(dt_n) = -i H_n U_n:

@@ -32,11 +32,16 @@ import numpy as np
 
 mp.mp.dps = 60
 # (degree M, radius theta_M of the segment): the smallest degree whose derivative error 2 J_M(theta) stays below 2.5e-16.
+#   1.11  cells the three-moment certificate of the plan places there (t16_seg_certified, grape_kernels.hip.h): the
+#         largest two-decimal radius degree 15 covers
 #   1.36  the verdict of the four-product exponential kernel (T16_THETA)        1.6, 2.0  bounds of the blocked path
 #   2.72  a cell of the four-product kernel that was exponentiated as A / 2 (one planned squaring)
-SETS = [(16, "1.36"), (17, "1.6"), (19, "2.0"), (21, "2.72")]
-THETA = mp.mpf(SETS[0][1])
-M = SETS[0][0]
+# (ascending degrees: the kernels index their tables by M - ECON_MINDEG)
+SETS = [(15, "1.11"), (16, "1.36"), (17, "1.6"), (19, "2.0"), (21, "2.72")]
+T16_THETA = "1.36"                             # grape_t18_coeffs.h: the radius the verdict certifies
+assert [m for m, _ in SETS] == sorted({m for m, _ in SETS}) and [float(t) for _, t in SETS] == sorted(float(t) for _, t in SETS)
+VERDICT_SET = [t for _, t in SETS].index(T16_THETA)      # (a set added in front of it moves the index, not the meaning)
+M, THETA = SETS[VERDICT_SET][0], mp.mpf(T16_THETA)       # (defaults of the helpers below: the segment of the verdict)
 HERE = os.path.dirname(os.path.abspath(__file__))
 HEADER = os.path.join(HERE, "..", "grape.jl_amd", "csrc", "grape_econ_coeffs.h")
 
@@ -151,7 +156,10 @@ def main():
              "// degree, the smallest degree whose derivative stays within 2.5e-16 of exp's on its segment.",
              "#pragma once",
              f"#define ECON_NSETS {len(SETS)}",
+             f"#define ECON_MINDEG {min(m for m, _ in SETS)}",
              f"#define ECON_MAXDEG {max(m for m, _ in SETS)}",
+             f"#define ECON_SEG_THETA {SETS[0][1]}   // ECON_THETAS[0]: the segment cells are certified for from three trace moments",
+             f"#define ECON_VERDICT_SET {VERDICT_SET}   // ECON_THETAS[{VERDICT_SET}] = {T16_THETA}: the verdict of the four-product exponential kernel",
              f"static const int ECON_DEG[{len(SETS)}] = {{{', '.join(str(m) for m, _ in SETS)}}};",
              f"static const double ECON_THETAS[{len(SETS)}] = {{{', '.join(t for _, t in SETS)}}};",
              "// [set][a] = {omega_a, sigma_a}, a = 0 .. ECON_DEG[set] - 1   (Taylor: both 1 / (a + 1))",
