@@ -214,7 +214,8 @@ struct grape_handle {
     double lambda_user = 0.0;
     unsigned long long *d_stats = nullptr;
     double *h_pin = nullptr;  // pinned staging
-    DeviceBufs mem;           // owns every buffer above and below that this handle allocated (grape_devmem.h)
+    double *h_get = nullptr;  // pinned staging of the read-only getters (getter_fetch; allocated by the first one)
+    DeviceBufs mem;          // owns every buffer above and below that this handle allocated (grape_devmem.h)
     size_t h_pin_doubles = 0;
     Phase ph[kRing][kPhases]{};
     long n_fwd = 0, n_bwd = 0;  // evaluations recorded since the last grape_reset_timings
@@ -305,6 +306,7 @@ struct grape_handle {
     bool tg_unit = false;          // ... d_bw holds the unit backward states (factor z_k instead of rho_k)
     bool tg_xi_user = false;       // ... the running cost was the caller's (grape_backward_xi): no explicit weight term
     bool graph_tg_unit = false;    // tg_unit of the captured evaluation
+    int graph_walk_fuse = 0;       // last_walk_fuse of the captured evaluation (grape_get_work[17] after a replay)
     double2 *d_tq = nullptr;       // [K][N_T] per-trajectory terms of dJ/d(dt_n) (allocated on first use)
     double *d_dJdt = nullptr;      // [N_T]
     // grape_eval_batch (grape_batch.hip.h): many pulse vectors through this handle's problem.  The batched
@@ -401,6 +403,25 @@ struct LdsLimit {
     }
 };
 
+// A reset inside the captured evaluation (grape_handle::graph) is a kernel of this library, never a memset node: the runtime
+// replays a memset node with whatever a later copy or fill of the process has left in the buffer its fill kernel reads the
+// pattern from (flag word and statistics filled with the arguments of a getter's copy; cell list counter,
+// walk progress and only_if words start from that).  A kernel node carries its arguments by value.  Outside a capture the
+// runtime's fill stays (the pattern is written and read within one call).
+__global__ void fill_words_kernel(unsigned *p, unsigned v, size_t n) {
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) p[i] = v;
+}
+hipError_t stream_fill(void *p, int byte_value, size_t bytes, hipStream_t s) {
+    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+    if (bytes % 4 != 0 || ((size_t)p & 3) != 0 || hipStreamIsCapturing(s, &st) != hipSuccess || st != hipStreamCaptureStatusActive)
+        return hipMemsetAsync(p, byte_value, bytes, s);
+    const size_t n = bytes / 4;
+    if (n == 0) return hipSuccess;
+    const unsigned v = 0x01010101u * (unsigned)(byte_value & 0xFF);
+    hipLaunchKernelGGL(fill_words_kernel, dim3((unsigned)std::min<size_t>((n + 255) / 256, 1024)), dim3(256), 0, s, (unsigned *)p, v, n);
+    return hipGetLastError();
+}
+
 size_t expm_lds_bytes(int NT) {
     const int total = NT == 1 ? ExpmLds<1>::TOTAL : NT == 2 ? ExpmLds<2>::TOTAL : NT == 3 ? ExpmLds<3>::TOTAL : ExpmLds<4>::TOTAL;
     return sizeof(double) * (size_t)total;
@@ -418,7 +439,7 @@ hipError_t launch_expm(const ExpmArgs &a, bool herm, hipStream_t s, int persiste
         if (e == hipSuccess && NT >= 3) e = lim_herm.ensure((const void *)expm_pade_kernel<NT, false, NT >= 3>, dev, lds);
         if (e != hipSuccess) return e;
     }
-    hipError_t e = hipMemsetAsync(a.cellflag, 0, (size_t)a.K * a.N_T * sizeof(int), s);
+    hipError_t e = stream_fill(a.cellflag, 0, (size_t)a.K * a.N_T * sizeof(int), s);
     if (e != hipSuccess) return e;
     // fast pass: unpivoted block Gauss-Jordan, flags the cells it cannot solve safely; one workgroup per cell
     if (NT == 4 && persistent_blocks > 0) {   // one workgroup per CU walks its cells (see expm_persistent)
@@ -3422,7 +3443,7 @@ int grape_forward_device(grape_handle *h, const double *d_pulsevals, double *d_o
     // HIP's last-error is sticky per host thread: a failure elsewhere in the process (another handle's failed
     // allocation, a bad device ordinal) must not be reported by the launch checks of this evaluation
     (void)hipGetLastError();
-    HIPCHK(h, hipMemsetAsync(h->d_flags, 0, 8 * sizeof(int) + (size_t)GRAPE_STAT_SHARDS * GRAPE_STAT_SLOTS * sizeof(unsigned long long), s));   // flags | statistics
+    HIPCHK(h, stream_fill(h->d_flags, 0, 8 * sizeof(int) + (size_t)GRAPE_STAT_SHARDS * GRAPE_STAT_SLOTS * sizeof(unsigned long long), s));   // flags | statistics
     if (d_pulsevals != h->d_eps)
         HIPCHK(h, hipMemcpyAsync(h->d_eps, d_pulsevals, (size_t)h->L * h->N_T * 8, hipMemcpyDeviceToDevice, s));
     // ---- phase 0: expm of every cell ----
@@ -3493,7 +3514,7 @@ int grape_forward_device(grape_handle *h, const double *d_pulsevals, double *d_o
                 h->credit_pending = false;
                 if (h->asm18g) {   // general matrices: the assembly cell decides its squarings itself, nothing is handed over
                     walk_fuse = h->asm_walk & (1 | ((h->fuse && h->fuse_on && h->want_bw) ? 2 : 0));
-                    if (walk_fuse) HIPCHK(h, hipMemsetAsync(h->d_prog, 0, (size_t)2 * h->K * sizeof(int), s));
+                    if (walk_fuse) HIPCHK(h, stream_fill(h->d_prog, 0, (size_t)2 * h->K * sizeof(int), s));
                     const void *walk[6] = {h->d_wgtab, h->d_xinit, h->d_fw, h->d_bw, h->d_prog, h->d_splan};
                     if (h->asm18gp) {
                         hipLaunchKernelGGL(dte_kernel, dim3((unsigned)((h->N_T + 255) / 256)), dim3(256), 0, s, (const double *)h->d_eps,
@@ -3506,7 +3527,7 @@ int grape_forward_device(grape_handle *h, const double *d_pulsevals, double *d_o
                 }
                 else if (t16 && h->asm16p) {   // control operators per trajectory: the cell fetches them itself
                     walk_fuse = h->asm_walk & (1 | ((h->fuse && h->fuse_on && h->want_bw) ? 2 : 0));
-                    if (walk_fuse) HIPCHK(h, hipMemsetAsync(h->d_prog, 0, (size_t)2 * h->K * sizeof(int), s));
+                    if (walk_fuse) HIPCHK(h, stream_fill(h->d_prog, 0, (size_t)2 * h->K * sizeof(int), s));
                     hipLaunchKernelGGL(dte_kernel, dim3((unsigned)((h->N_T + 255) / 256)), dim3(256), 0, s, (const double *)h->d_eps,
                                        (const double *)h->d_shape, (const double *)h->d_dts, h->L, h->N_T, h->L <= 2 ? 2 : 4, h->d_dte);
                     HIPCHK(h, hipGetLastError());
@@ -3517,7 +3538,7 @@ int grape_forward_device(grape_handle *h, const double *d_pulsevals, double *d_o
                     // what the walks may carry along: Psi always (the forward sweep is the same whatever follows), conj(chi~)
                     // when this evaluation runs the backward sweep from the unit targets (concurrent sweeps)
                     walk_fuse = h->asm_walk & (1 | ((h->fuse && h->fuse_on && h->want_bw) ? 2 : 0));
-                    if (walk_fuse) HIPCHK(h, hipMemsetAsync(h->d_prog, 0, (size_t)2 * h->K * sizeof(int), s));
+                    if (walk_fuse) HIPCHK(h, stream_fill(h->d_prog, 0, (size_t)2 * h->K * sizeof(int), s));
                     const void *walk[6] = {h->d_wgtab, h->d_xinit, h->d_fw, h->d_bw, h->d_prog, h->d_splan};
                     e = (hipError_t)grape_t16_asm_launch(&ea, sizeof(ea), h->d_cellflag, (void *)s, h->asm_blocks, walk, walk_fuse, h->K);
                     h->credit_pending = true;
@@ -3758,7 +3779,7 @@ int backward_device_impl(grape_handle *h, const double *d_f, double *d_G, hipStr
     const int nblocks = h->K * ((h->N_T + cpb - 1) / cpb);
     phase_begin(h, 3, s);
     if (h->NP >= 48 && h->sub_theta > 0.0) {   // which batches of 16 cells need a sub-stepped derivative series?
-        HIPCHK(h, hipMemsetAsync(h->d_flags + 3, 0, sizeof(int), s));
+        HIPCHK(h, stream_fill(h->d_flags + 3, 0, sizeof(int), s));
         DerivFlagArgs fa{};
         fa.rb = h->d_rb; fa.eps = h->d_eps; fa.shape = h->d_shape; fa.dts = h->d_dts;
         fa.rb_k = h->K; fa.K = h->K; fa.L = h->L; fa.N_T = h->N_T; fa.hc_per_traj = h->p.hc_per_traj;
@@ -3835,7 +3856,7 @@ int backward_device_impl(grape_handle *h, const double *d_f, double *d_G, hipStr
                 d2.batch_econ = 1; d2.econ_pairs = h->d_econ_pairs;
             }
             if (sub) {
-                HIPCHK(h, hipMemsetAsync(h->d_flags + 3, 0, sizeof(int), s));
+                HIPCHK(h, stream_fill(h->d_flags + 3, 0, sizeof(int), s));
                 DerivFlagArgs fa{};
                 fa.rb = h->d_rb; fa.eps = h->d_eps; fa.shape = h->d_shape; fa.dts = h->d_dts;
                 fa.rb_k = h->K; fa.K = h->K; fa.L = h->L; fa.N_T = h->N_T; fa.hc_per_traj = h->p.hc_per_traj;
@@ -3901,6 +3922,42 @@ int digest_flags(grape_handle *h, const int *flags) {
     if (h->large && !h->series) h->sq_plan = std::max(2, flags[1] + 1);
     return status_from_flags(h, flags[0]);
 }
+
+// What the read-only getters of a closed single-device handle copy out: `rows` rows of `width` bytes, `spitch` bytes apart on
+// the device, packed at `dst`.  The copy runs on the handle's own stream -- the stream of the last evaluation, NON-BLOCKING, so
+// that the NULL stream of a blocking hipMemcpy is not ordered against it -- into pinned staging of the handle, with one wait
+// per piece, as the split-phase calls copy.  A device-pointer call on a stream of the caller's is not ordered
+// against the handle's stream either: then the device is waited for first.
+constexpr size_t kGetStageBytes = (size_t)4 << 20;
+int getter_fetch(grape_handle *h, void *dst, const void *src, size_t spitch, size_t width, size_t rows) {
+    HIPCHK(h, hipSetDevice(h->device));
+    if (h->foreign_stream) HIPCHK(h, hipDeviceSynchronize());
+    if (!h->h_get) HIPCHK(h, h->mem.alloc_pinned(&h->h_get, kGetStageBytes / sizeof(double)));
+    char *out = (char *)dst;
+    const char *in = (const char *)src;
+    if (width > kGetStageBytes) {   // (one contiguous block: the callers' rows are a state or a propagator, 64 KB at most)
+        if (rows != 1) { h->err = "getter_fetch: a row does not fit the staging buffer"; return GRAPE_ERR_INVALID; }
+        for (size_t off = 0; off < width; off += kGetStageBytes) {
+            const size_t n = std::min(kGetStageBytes, width - off);
+            HIPCHK(h, hipMemcpyAsync(h->h_get, in + off, n, hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(h, hipStreamSynchronize(h->stream));
+            memcpy(out + off, h->h_get, n);
+        }
+        return GRAPE_OK;
+    }
+    const size_t per = std::max<size_t>(1, kGetStageBytes / width);
+    for (size_t r0 = 0; r0 < rows; r0 += per) {
+        const size_t nr = std::min(per, rows - r0);
+        if (nr == 1 || spitch == width)
+            HIPCHK(h, hipMemcpyAsync(h->h_get, in + r0 * spitch, nr * width, hipMemcpyDeviceToHost, h->stream));
+        else
+            HIPCHK(h, hipMemcpy2DAsync(h->h_get, width, in + r0 * spitch, spitch, width, nr, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        memcpy(out + r0 * width, h->h_get, nr * width);
+    }
+    return GRAPE_OK;
+}
+int getter_fetch(grape_handle *h, void *dst, const void *src, size_t bytes) { return getter_fetch(h, dst, src, bytes, bytes, 1); }
 
 }  // namespace
 
@@ -4306,12 +4363,8 @@ int grape_get_sums(grape_handle *h, double sums[8]) try {
         }
         return GRAPE_OK;
     }
-    HIPCHK(h, hipSetDevice(h->device));
-    // (the handle's stream only: other handles of the process keep running -- unless the last device-pointer call ran on a
-    // stream of the caller's, which a blocking copy is not ordered against: then the device)
-    HIPCHK(h, h->foreign_stream ? hipDeviceSynchronize() : hipStreamSynchronize(h->stream));
-    HIPCHK(h, hipMemcpy(sums, h->d_out + 2 * (size_t)h->K, 8 * sizeof(double), hipMemcpyDeviceToHost));
-    return GRAPE_OK;
+    // (the handle's stream only: other handles of the process keep running; see getter_fetch)
+    return getter_fetch(h, sums, h->d_out + 2 * (size_t)h->K, 8 * sizeof(double));
 }
 GRAPE_BARRIER(h ? &h->err : &g_create_error)
 
@@ -4326,10 +4379,8 @@ int grape_get_final_states(grape_handle *h, double *psiT) try {
         }
         return GRAPE_OK;
     }
-    HIPCHK(h, hipSetDevice(h->device));
-    HIPCHK(h, h->foreign_stream ? hipDeviceSynchronize() : hipStreamSynchronize(h->stream));
-    HIPCHK(h, hipMemcpy2D(psiT, (size_t)h->N * 16, h->d_fw + (size_t)h->N_T * h->NP,
-                          (size_t)(h->N_T + 1) * h->NP * 16, (size_t)h->N * 16, h->K, hipMemcpyDeviceToHost));
+    const int rc = getter_fetch(h, psiT, h->d_fw + (size_t)h->N_T * h->NP, (size_t)(h->N_T + 1) * h->NP * 16, (size_t)h->N * 16, h->K);
+    if (rc) return rc;
     if (!h->bal.empty())   // Psi = D Psi~
         for (int k = 0; k < h->K; ++k)
             for (int i = 0; i < h->N; ++i) { psiT[2 * ((size_t)k * h->N + i)] *= h->bal[i]; psiT[2 * ((size_t)k * h->N + i) + 1] *= h->bal[i]; }
@@ -4382,6 +4433,7 @@ int grape_eval(grape_handle *h, const double *pulsevals, double *J, double *G, d
                         h->graph = gph; h->graph_fuse_on = h->fuse_on;
                         h->graph_bw_unit = h->bw_unit; h->graph_z_valid = h->z_valid; h->graph_credit = h->credit_pending;
                         h->graph_tg_unit = h->tg_unit;
+                        h->graph_walk_fuse = h->last_walk_fuse;
                     } else {
                         if (gph) hipGraphDestroy(gph);
                         h->graph_exec = nullptr;
@@ -4396,6 +4448,7 @@ int grape_eval(grape_handle *h, const double *pulsevals, double *J, double *G, d
                 h->foreign_stream = false; h->have_forward = true; h->bw_done = false;
                 h->bw_unit = h->graph_bw_unit; h->z_valid = h->graph_z_valid; h->credit_pending = h->graph_credit;
                 h->tg_state = 3; h->tg_unit = h->graph_tg_unit; h->tg_xi_user = false;
+                h->last_walk_fuse = h->graph_walk_fuse;   // (an evaluation without a gradient in between carries one end only)
                 h->hvs.came(grape_handle::HvpSplit::EVAL);
                 replayed = true;
             }
@@ -4462,10 +4515,7 @@ int grape_get_tau_grads(grape_handle *h, double *out) try {
         }
         return GRAPE_OK;
     }
-    HIPCHK(h, hipSetDevice(h->device));
-    HIPCHK(h, hipDeviceSynchronize());
-    HIPCHK(h, hipMemcpy(out, h->d_tg, (size_t)h->K * h->L * h->N_T * 16, hipMemcpyDeviceToHost));
-    return GRAPE_OK;
+    return getter_fetch(h, out, h->d_tg, (size_t)h->K * h->L * h->N_T * 16);
 }
 GRAPE_BARRIER(h ? &h->err : &g_create_error)
 
@@ -4488,15 +4538,14 @@ int grape_get_storage(grape_handle *h, int which, double *out) try {
                  "coefficient of chi is applied by grape_backward)";
         return GRAPE_ERR_INVALID;
     }
-    HIPCHK(h, hipSetDevice(h->device));
-    HIPCHK(h, hipDeviceSynchronize());
     const double2 *src = which == 0 ? h->d_fw : h->d_bw;
-    HIPCHK(h, hipMemcpy2D(out, (size_t)h->N * 16, src, (size_t)h->NP * 16, (size_t)h->N * 16,
-                          (size_t)h->K * (h->N_T + 1), hipMemcpyDeviceToHost));
+    int rc = getter_fetch(h, out, src, (size_t)h->NP * 16, (size_t)h->N * 16, (size_t)h->K * (h->N_T + 1));
+    if (rc) return rc;
     if (which == 1 && h->bw_unit) {
         // concurrent sweeps stored chi~_k(t_n); chi_k(t_n) = (c_k / |c_k|) chi~_k(t_n) with z_k = conj(c_k) ||target_k||
         std::vector<double> z(2 * (size_t)h->K);
-        HIPCHK(h, hipMemcpy(z.data(), h->d_z, z.size() * 8, hipMemcpyDeviceToHost));
+        rc = getter_fetch(h, z.data(), h->d_z, z.size() * 8);
+        if (rc) return rc;
         for (int k = 0; k < h->K; ++k) {
             const double a = std::hypot(z[2 * k], z[2 * k + 1]);
             const double pr = a > 0 ? z[2 * k] / a : 1.0, pi = a > 0 ? -z[2 * k + 1] / a : 0.0;
@@ -4546,11 +4595,10 @@ int grape_get_propagator(grape_handle *h, int k, int n, double *out) try {
                                : "prop_method = GRAPE_PROP_SERIES is matrix-free: no propagator is materialised";
         return GRAPE_ERR_INVALID;
     }
-    HIPCHK(h, hipSetDevice(h->device));
-    HIPCHK(h, hipDeviceSynchronize());
     const size_t pp = (size_t)h->NP * h->NP;
     std::vector<double> tmp(2 * pp);
-    HIPCHK(h, hipMemcpy(tmp.data(), h->d_U + ((size_t)h->cls[k] * h->N_T + n) * pp, pp * 16, hipMemcpyDeviceToHost));
+    const int rc = getter_fetch(h, tmp.data(), h->d_U + ((size_t)h->cls[k] * h->N_T + n) * pp, pp * 16);
+    if (rc) return rc;
     for (int j = 0; j < h->N; ++j)
         for (int i = 0; i < h->N; ++i) {
             const double f = h->bal.empty() ? 1.0 : h->bal[i] / h->bal[j];   // U = D U~ D^-1 (exact: powers of two)
@@ -4643,7 +4691,7 @@ int grape_get_work(grape_handle *h, double *out, int n) try {
         return 4;
     }
     HIPCHK(h, hipSetDevice(h->device));
-    HIPCHK(h, hipDeviceSynchronize());
+    if (h->foreign_stream) HIPCHK(h, hipDeviceSynchronize());
     if (h->credit_pending) {   // credited work of the assembly route's last evaluation: pulses, S_n and flags are still in place
         ExpmArgs ea{};
         ea.H0f = h->d_H0f; ea.Hcf = h->d_Hcf; ea.eps = h->d_eps; ea.shape = h->d_shape; ea.dts = h->d_dts;
@@ -4655,7 +4703,7 @@ int grape_get_work(grape_handle *h, double *out, int n) try {
         h->credit_pending = false;
     }
     unsigned long long sh[GRAPE_STAT_SHARDS * GRAPE_STAT_SLOTS], st[GRAPE_STAT_SLOTS] = {0};
-    HIPCHK(h, hipMemcpy(sh, h->d_stats, sizeof(sh), hipMemcpyDeviceToHost));
+    { const int rc_ = getter_fetch(h, sh, h->d_stats, sizeof(sh)); if (rc_) return rc_; }
     for (int q = 0; q < GRAPE_STAT_SHARDS; ++q)
         for (int i = 0; i < GRAPE_STAT_SLOTS; ++i) st[i] += sh[q * GRAPE_STAT_SLOTS + i];
     const double N3 = (double)h->N * h->N * h->N, N2 = (double)h->N * h->N;
@@ -4701,7 +4749,7 @@ int grape_get_work(grape_handle *h, double *out, int n) try {
         double carried = 0.0;
         if (h->last_walk_fuse && h->d_prog) {
             std::vector<int> prog((size_t)2 * h->K);
-            HIPCHK(h, hipMemcpy(prog.data(), h->d_prog, prog.size() * sizeof(int), hipMemcpyDeviceToHost));
+            { const int rc_ = getter_fetch(h, prog.data(), h->d_prog, prog.size() * sizeof(int)); if (rc_) return rc_; }
             for (int k = 0; k < h->K; ++k) {
                 if (h->last_walk_fuse & 1) carried += prog[(size_t)k];
                 if (h->last_walk_fuse & 2) carried += prog[(size_t)h->K + k];
@@ -4722,15 +4770,15 @@ int grape_get_work(grape_handle *h, double *out, int n) try {
             const size_t ncell = (size_t)h->KC * h->N_T;
             std::vector<int> plan(ncell);
             int fl[8];
-            HIPCHK(h, hipMemcpy(plan.data(), h->d_splan, ncell * sizeof(int), hipMemcpyDeviceToHost));
-            HIPCHK(h, hipMemcpy(fl, h->d_flags, sizeof(fl), hipMemcpyDeviceToHost));
+            { const int rc_ = getter_fetch(h, plan.data(), h->d_splan, ncell * sizeof(int)); if (rc_) return rc_; }
+            { const int rc_ = getter_fetch(h, fl, h->d_flags, sizeof(fl)); if (rc_) return rc_; }
             const bool tried = !(4L * fl[6] > (long)ncell);
             if (tried && h->d_cert)
                 for (int w : plan) certified += (w & T16_PLAN_CERT) ? 1.0 : 0.0;
             if (tried && want_seg) {
                 std::vector<int> sp(ncell), verdict(ncell);
-                HIPCHK(h, hipMemcpy(sp.data(), h->d_segplan, ncell * sizeof(int), hipMemcpyDeviceToHost));
-                HIPCHK(h, hipMemcpy(verdict.data(), h->d_cellflag, ncell * sizeof(int), hipMemcpyDeviceToHost));
+                { const int rc_ = getter_fetch(h, sp.data(), h->d_segplan, ncell * sizeof(int)); if (rc_) return rc_; }
+                { const int rc_ = getter_fetch(h, verdict.data(), h->d_cellflag, ncell * sizeof(int)); if (rc_) return rc_; }
                 for (int k = 0; k < h->K; ++k) {
                     const size_t c0 = (size_t)(h->cls.empty() ? k : h->cls[k]) * h->N_T;
                     for (int i = 0; i < h->N_T; ++i)

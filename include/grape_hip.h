@@ -305,8 +305,9 @@ int grape_reset_timings(grape_handle *h);
  * 2 deriv3s_asm (3 <= L <= 8, controls streamed through the LDS), 3 deriv3g_asm (general drift / controls), 4 deriv4_asm
  * (64 < N <= 256), [16] 1 if the products of the blocked polynomial route are the assembly kernel lg_gemm_asm,
  * [17] the steps of the two sweeps that the walks of the exponential kernel carried in the last evaluation (the sweep
- * launch did the remaining 2 K N_T - [17]), [18] the block length of the scanned sweeps of N <= 16 (round 6: the time axis is
- * cut into blocks whose propagators are formed first; 0: sequential sweeps; GRAPE_SCAN16=0 / 1 forces)
+ * launch did the remaining 2 K N_T - [17]), [18] the block length of the scanned sweeps of N <= 64 (round 6: the time axis is
+ * cut into blocks whose propagators are formed first; by default from 64 time steps on, with at most 96 / 64 / 48 / 24
+ * generator classes at NP = 16 / 32 / 48 / 64; 0: sequential sweeps; GRAPE_SCAN16=0 / 1 forces)
  * [19] the cells of the last evaluation whose spectrum was certified before the launch of the four-product assembly kernel:
  * tr H^8 and tr H^6 of H = H0_k + sum_l e_l C_l are polynomials in the pulse values whose coefficients grape_create tabulates
  * per generator class (Hermitian generators, 1 <= L <= 4, assembly route); the plan of an evaluation tests
