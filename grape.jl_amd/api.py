@@ -37,7 +37,8 @@ EXPORTS = ["grape_create", "grape_destroy", "grape_eval", "grape_forward", "grap
            "grape_hvp", "grape_get_hvp_info", "grape_open_time_gradient", "grape_open_hvp", "grape_get_open_hvp_info",
            "grape_open_eval_batch", "grape_get_open_batch_info", "grape_open_set_running_cost", "grape_open_backward_xi",
            "grape_hvp_forward", "grape_hvp_backward", "grape_hvp_backward_chi",
-           "grape_open_hvp_forward", "grape_open_hvp_backward", "grape_open_hvp_backward_chi"]
+           "grape_open_hvp_forward", "grape_open_hvp_backward", "grape_open_hvp_backward_chi",
+           "grape_expect", "grape_get_expect_info"]
 
 
 class GrapeHipError(RuntimeError):
@@ -105,7 +106,7 @@ def build_asm(verbose: bool = False, workdir: str | None = None) -> str:
 def _sources():
     srcs = [os.path.join(_CSRC, f) for f in ("grape_hip.hip", "grape_t18.hip", "grape_kernels.hip.h", "grape_large.hip.h",
                                              "grape_series.hip.h", "grape_cheby.hip.h", "grape_t18.hip.h", "grape_t18_coeffs.h",
-                                             "grape_deriv3.hip.h", "grape_timegrad.hip.h", "grape_batch.hip.h", "grape_lindblad.hip.h", "grape_lindblad_tg.hip.h", "grape_hvp.hip.h", "grape_hvp_split.hip.h", "grape_lindblad_hvp.hip.h", "grape_lindblad_hvp_split.hip.h", "grape_lindblad_batch.hip.h", "grape_lindblad_rc.hip.h", "grape_devmem.h", "grape_cert.hip.h", "grape_econ_coeffs.h", os.path.join("asm", "gen_t16.py"), os.path.join("asm", "gen_t16p.py"), os.path.join("asm", "gen_t18g.py"), os.path.join("asm", "gen_t18gp.py"), os.path.join("asm", "gen_d3.py"), os.path.join("asm", "gen_d3s.py"), os.path.join("asm", "gen_lg.py"), os.path.join("asm", "gen_d4.py"), os.path.join("asm", "gcn.py"))]
+                                             "grape_deriv3.hip.h", "grape_timegrad.hip.h", "grape_batch.hip.h", "grape_lindblad.hip.h", "grape_lindblad_tg.hip.h", "grape_hvp.hip.h", "grape_hvp_split.hip.h", "grape_lindblad_hvp.hip.h", "grape_lindblad_hvp_split.hip.h", "grape_lindblad_batch.hip.h", "grape_lindblad_rc.hip.h", "grape_devmem.h", "grape_cert.hip.h", "grape_expect.hip.h", "grape_econ_coeffs.h", os.path.join("asm", "gen_t16.py"), os.path.join("asm", "gen_t16p.py"), os.path.join("asm", "gen_t18g.py"), os.path.join("asm", "gen_t18gp.py"), os.path.join("asm", "gen_d3.py"), os.path.join("asm", "gen_d3s.py"), os.path.join("asm", "gen_lg.py"), os.path.join("asm", "gen_d4.py"), os.path.join("asm", "gcn.py"))]
     return srcs, os.path.join(_HERE, "..", "include", "grape_hip.h")
 
 
@@ -232,6 +233,8 @@ def load_library():
     lib.grape_get_open_batch_info.argtypes = [vp, vp, ip]
     lib.grape_open_set_running_cost.argtypes = [vp, vp, ip, C.c_double]
     lib.grape_open_backward_xi.argtypes = [vp, vp, vp, vp, C.c_double, vp]
+    lib.grape_expect.argtypes = [vp, ip, vp, ip, vp]
+    lib.grape_get_expect_info.argtypes = [vp, vp, ip]
     lib.grape_last_error.argtypes = [vp]
     lib.grape_last_error.restype = C.c_char_p
     lib.grape_abi_version.restype = ip
@@ -469,6 +472,28 @@ class GrapeHip:
         self._lib.grape_get_hvp_info(self._h, out.ctypes.data, 7)
         return dict(series_terms=int(out[0]), series_steps=int(out[1]), dirs_per_group=int(out[2]), bytes=int(out[3]), ms=float(out[4]),
                     terms_forward=int(out[5]), terms_backward=int(out[6]))
+
+    def expect(self, ops):
+        """Expectation values of operator observables on the stored forward states of the last evaluation, computed on the
+        device (grape_expect): ``ops`` [M, N, N] (one set for all trajectories) or [K, M, N, N], numpy ``[row, col]``, not
+        necessarily Hermitian, 1 <= M <= 16.  Returns [K, N_T+1, M] complex: ``<Psi_k(t_n)|O_m|Psi_k(t_n)>`` on a closed handle,
+        ``tr(O_m rho_k(t_n))`` on an open one; entry n = 0 is the initial state.  Needs a successful ``eval`` or ``forward`` on
+        the current time grid (include/grape_hip.h lists the refusals)."""
+        o = np.asarray(ops)
+        if o.ndim not in (3, 4) or o.shape[-2:] != (self.N, self.N) or (o.ndim == 4 and o.shape[0] != self.K):
+            raise ValueError(f"ops must be [M, N, N] or [K, M, N, N] with N = {self.N}, K = {self.K}, got {o.shape}")
+        M = o.shape[-3]
+        o = _c128(np.swapaxes(o, -1, -2))
+        out = np.empty((self.K, self.N_T + 1, M), dtype=np.complex128)
+        self._chk(self._lib.grape_expect(self._h, M, o.ctypes.data, int(o.ndim == 4), out.ctypes.data))
+        return out
+
+    def expect_info(self):
+        """What the last ``expect`` did (grape_get_expect_info): its M, bytes the feature holds on the device, milliseconds of
+        the call (host wall time, copies included), flop of the matrix instructions (0 on an open handle)."""
+        out = np.zeros(4)
+        self._lib.grape_get_expect_info(self._h, out.ctypes.data, 4)
+        return dict(M=int(out[0]), bytes=int(out[1]), ms=float(out[2]), mfma_flop=float(out[3]))
 
     def _hvp_dirs(self, V):
         v = np.ascontiguousarray(V, dtype=np.float64)

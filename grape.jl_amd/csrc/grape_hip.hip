@@ -24,6 +24,7 @@
 #include "grape_lindblad_rc.hip.h"
 #include "grape_devmem.h"
 #include "grape_cert.hip.h"
+#include "grape_expect.hip.h"
 
 #include <rccl/rccl.h>
 #include <dlfcn.h>
@@ -352,6 +353,20 @@ struct grape_handle {
     // generator.  Such a handle owns none of the buffers above: everything it holds hangs off this pointer, and the entry
     // points dispatch on it.
     OpenCtx *open = nullptr;
+    // grape_expect (grape_expect.hip.h): observables on the stored forward states.  The operators on the device and
+    // the result are buffers of its own -- allocated by the first call, grown on demand, freed by grape_destroy; nothing an
+    // evaluation, a getter or a derivative call uses is touched.  ex_state: whether the store of a closed single-device handle
+    // is that of one successful forward half on the current grid (an open handle asks OpenCtx::hv_state, a composite its shards).
+    struct ExpectStore {
+        enum { NONE = 0, READY, FAILED, TLIST, BATCH };
+        DeviceBufs mem;
+        double *d_ops = nullptr;
+        double2 *d_res = nullptr;
+        size_t ops_cap = 0, res_cap = 0;   // elements the two buffers hold
+        std::vector<double> stage;          // the operators in the device layout
+        double info[4] = {0., 0., 0., 0.};  // grape_get_expect_info
+    } ex;
+    int ex_state = ExpectStore::NONE;
 };
 
 namespace {
@@ -1610,7 +1625,7 @@ void open_destroy(grape_handle *h) {
     OpenCtx *o = h->open;
     hipSetDevice(h->device);
     if (h->stream) hipStreamSynchronize(h->stream);
-    o->hv.store.release(); o->hvs.mem.release(); o->ob.store.release(); o->mem.release();
+    o->hv.store.release(); o->hvs.mem.release(); o->ob.store.release(); h->ex.mem.release(); o->mem.release();
     for (hipEvent_t e : o->ev)
         if (e) hipEventDestroy(e);
     if (h->stream) hipStreamDestroy(h->stream);
@@ -2417,7 +2432,7 @@ void grape_destroy(grape_handle *h) {
     }
     hipSetDevice(h->device);
     if (h->stream) hipStreamSynchronize(h->stream);
-    h->batch.store.release(); h->hvp.store.release(); h->hvs.mem.release(); h->mem.release();
+    h->batch.store.release(); h->hvp.store.release(); h->hvs.mem.release(); h->ex.mem.release(); h->mem.release();
     for (auto &ring : h->ph)
         for (auto &p : ring) {
             if (p.e0) hipEventDestroy(p.e0);
@@ -3614,6 +3629,7 @@ int grape_forward_device(grape_handle *h, const double *d_pulsevals, double *d_o
 #endif
     h->last_walk_fuse = walk_fuse;
     h->tg_state = h->want_bw ? 2 : 1;
+    h->ex_state = grape_handle::ExpectStore::READY;
     h->hvs.came(grape_handle::HvpSplit::EVAL);
     // ---- phase 1: forward sweep + tau ----
     SweepArgs sa{};
@@ -4073,7 +4089,7 @@ int backward_enqueue(grape_handle *h, const double f_total[2], const double *chi
 }
 int backward_finish(grape_handle *h, double *G, bool accumulate) {
     const int rc = grape_check(h, h->stream);
-    if (rc) { h->tg_state = 0; return rc; }
+    if (rc) { h->tg_state = 0; h->ex_state = grape_handle::ExpectStore::FAILED; return rc; }
     if (!G) return GRAPE_OK;
     const size_t nl = (size_t)h->L * h->N_T;
     if (accumulate) for (size_t i = 0; i < nl; ++i) G[i] += h->h_pin[i];
@@ -4298,6 +4314,7 @@ int grape_forward(grape_handle *h, const double *pulsevals, double *tau) try {
     if (!h->shards.empty()) {
         int rc = multi_forward(h, pulsevals, tau);
         if (rc == GRAPE_ERR_AGAIN) rc = multi_forward(h, pulsevals, tau);   // launch plan adapted: once more
+        if (rc) for (grape_handle *c : h->shards) c->ex_state = grape_handle::ExpectStore::FAILED;   // (grape_expect asks the shards)
         return rc;
     }
     int rc = forward_enqueue(h, pulsevals);
@@ -4308,7 +4325,7 @@ int grape_forward(grape_handle *h, const double *pulsevals, double *tau) try {
         if (rc) return rc;
         rc = forward_finish(h, tau);
     }
-    if (rc) h->tg_state = 0;   // (the stored states of a failed sweep are nobody's input)
+    if (rc) { h->tg_state = 0; h->ex_state = grape_handle::ExpectStore::FAILED; }   // (the stored states of a failed sweep are nobody's input)
     return rc;
 }
 GRAPE_BARRIER(h ? &h->err : &g_create_error)
@@ -4448,6 +4465,7 @@ int grape_eval(grape_handle *h, const double *pulsevals, double *J, double *G, d
                 h->foreign_stream = false; h->have_forward = true; h->bw_done = false;
                 h->bw_unit = h->graph_bw_unit; h->z_valid = h->graph_z_valid; h->credit_pending = h->graph_credit;
                 h->tg_state = 3; h->tg_unit = h->graph_tg_unit; h->tg_xi_user = false;
+                h->ex_state = grape_handle::ExpectStore::READY;
                 h->last_walk_fuse = h->graph_walk_fuse;   // (an evaluation without a gradient in between carries one end only)
                 h->hvs.came(grape_handle::HvpSplit::EVAL);
                 replayed = true;
@@ -4469,7 +4487,7 @@ int grape_eval(grape_handle *h, const double *pulsevals, double *J, double *G, d
         }
         HIPCHK(h, hipStreamSynchronize(h->stream));
         rc = digest_flags(h, pinned_flags(h));
-        if (rc) { h->tg_state = 0; return rc; }
+        if (rc) { h->tg_state = 0; h->ex_state = grape_handle::ExpectStore::FAILED; return rc; }
         if (tau) memcpy(tau, h->h_pin + (size_t)h->L * h->N_T, (size_t)2 * h->K * 8);
         *J = functional_from_sums(h, forward_sums(h));
         memcpy(G, gpin, (size_t)h->L * h->N_T * 8);
@@ -5006,6 +5024,7 @@ int grape_set_tlist(grape_handle *h, const double *tlist) try {
         }
     if (h->open) return open_set_tlist(h, tlist);
     h->tg_state = 0;
+    h->ex_state = grape_handle::ExpectStore::TLIST;
     h->hvs.came(grape_handle::HvpSplit::TLIST);
     h->have_forward = false;
     if (!h->shards.empty()) {
@@ -5189,8 +5208,9 @@ int batch_group(grape_handle *h, const BatchStrides &st, int p0, int Pg, const d
 // the stored states no longer belong to "the last evaluation": grape_get_time_gradient refuses until the next ordinary one
 void batch_invalidate(grape_handle *h) {
     h->tg_state = 0;
+    h->ex_state = grape_handle::ExpectStore::BATCH;
     h->hvs.came(grape_handle::HvpSplit::BATCH);
-    for (grape_handle *c : h->shards) c->tg_state = 0;
+    for (grape_handle *c : h->shards) { c->tg_state = 0; c->ex_state = grape_handle::ExpectStore::BATCH; }
     if (h->open) {
         h->open->tg_state = OpenCtx::TG_BATCH; h->open->hv_state = OpenCtx::HV_BATCH;
         h->open->hvs.came(OpenCtx::HvpSplit::BATCH);
@@ -5376,6 +5396,153 @@ GRAPE_BARRIER(h ? &h->err : &g_create_error)
 int grape_get_hvp_info(grape_handle *h, double *out, int n) try {
     if (!h || !out) return GRAPE_ERR_INVALID;
     return copy_info(h->hvp.info, 7, out, n);
+}
+GRAPE_BARRIER(h ? &h->err : &g_create_error)
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------
+// grape_expect: operator observables on the stored forward states (grape_expect.hip.h)
+// ---------------------------------------------------------------------------------------
+namespace {
+
+#define EXPECT_REFUSE(text) do { h->err = "grape_expect: " text; return GRAPE_ERR_INVALID; } while (0)
+
+// why the store of this handle is not that of one successful forward half on the current grid (nullptr: it is)
+const char *expect_stale(const grape_handle *h) {
+    typedef grape_handle::ExpectStore X;
+    if (h->open) {
+        switch (h->open->hv_state) {
+        case OpenCtx::HV_READY:   // (the forward half stands; a backward half that failed behind it fails the evaluation)
+            return h->open->tg_state == OpenCtx::TG_FAILED ? "no valid forward state: the last evaluation failed" : nullptr;
+        case OpenCtx::HV_NONE: return "no valid forward state: no evaluation on this handle yet";
+        case OpenCtx::HV_NEW_GRID: return "no valid forward state: grape_set_tlist came after the last evaluation, the stored states belong to the previous grid";
+        case OpenCtx::HV_NEW_COST: return "no valid forward state: grape_open_set_running_cost came after the last evaluation";
+        case OpenCtx::HV_BATCH: return "no valid forward state: the last call was grape_eval_batch, the stored states are not those of one defined evaluation";
+        default: return "no valid forward state: the last evaluation failed";
+        }
+    }
+    if (!h->shards.empty()) {
+        for (const grape_handle *c : h->shards)
+            if (const char *why = expect_stale(c)) return why;
+        return nullptr;
+    }
+    switch (h->ex_state) {
+    case X::READY: return nullptr;
+    case X::NONE: return "no valid forward state: no evaluation on this handle yet";
+    case X::TLIST: return "no valid forward state: grape_set_tlist came after the last evaluation, the stored states belong to the previous grid";
+    case X::BATCH: return "no valid forward state: the last call was grape_eval_batch, the stored states are not those of one defined evaluation";
+    default: return "no valid forward state: the last evaluation failed";
+    }
+}
+
+// the two buffers of the call, through the handle's allocator; they only grow.  A failure names the size and leaves nothing
+int expect_reserve(grape_handle *h, size_t ops_n, size_t res_n) {
+    auto &x = h->ex;
+    if (ops_n <= x.ops_cap && res_n <= x.res_cap) return GRAPE_OK;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    ops_n = std::max(ops_n, x.ops_cap); res_n = std::max(res_n, x.res_cap);
+    x.mem.release(); x.ops_cap = x.res_cap = 0;
+    hipError_t e = x.mem.alloc(&x.d_ops, ops_n);
+    if (e == hipSuccess) e = x.mem.alloc(&x.d_res, res_n);
+    if (e != hipSuccess) {
+        x.mem.release();
+        (void)hipGetLastError();
+        h->err = "grape_expect: out of device memory for the operators and the result (" + std::to_string(ops_n * 8 + res_n * 16) +
+                 " bytes): " + hipGetErrorString(e);
+        return GRAPE_ERR_HIP;
+    }
+    x.ops_cap = ops_n; x.res_cap = res_n;
+    return GRAPE_OK;
+}
+
+int expect_single(grape_handle *h, int M, const double *ops, int ops_per_traj, double *out) {
+    const auto t0 = std::chrono::steady_clock::now();
+    auto &x = h->ex;
+    const size_t K = (size_t)h->K, pts = (size_t)h->N_T + 1, nn = (size_t)h->N * h->N, m2 = 2 * (size_t)h->NP * h->NP;
+    const size_t Ko = ops_per_traj ? K : 1, ops_n = Ko * M * m2, res_n = K * pts * M;
+    x.stage.resize(ops_n);
+    for (size_t q = 0; q < Ko * M; ++q) {
+        if (h->open) expect_pack_open(ops + 2 * q * nn, h->N, h->NP, x.stage.data() + q * m2);
+        else expect_pack_closed(ops + 2 * q * nn, h->N, h->NP, h->bal.empty() ? nullptr : h->bal.data(), x.stage.data() + q * m2);
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    if (h->foreign_stream) HIPCHK(h, hipDeviceSynchronize());   // (see grape_get_time_gradient)
+    (void)hipGetLastError();
+    const int rc = expect_reserve(h, ops_n, res_n);
+    if (rc) return rc;
+    hipStream_t s = h->stream;
+    HIPCHK(h, hipMemcpyAsync(x.d_ops, x.stage.data(), ops_n * 8, hipMemcpyHostToDevice, s));
+    double flop = 0.;
+    if (h->open) {
+        ExpectOpenArgs a{};
+        a.store = h->open->d_store; a.ops = x.d_ops; a.stride_k = ops_per_traj ? (size_t)M * m2 : 0; a.out = x.d_res;
+        a.N = h->N; a.N_T = h->N_T; a.M = M;
+        const dim3 grid((unsigned)(K * pts)), blk(EXPECT_NTH);
+        switch (h->NP) {
+        case 16: hipLaunchKernelGGL(expect_open_kernel<16>, grid, blk, 0, s, a); break;
+        case 32: hipLaunchKernelGGL(expect_open_kernel<32>, grid, blk, 0, s, a); break;
+        case 48: hipLaunchKernelGGL(expect_open_kernel<48>, grid, blk, 0, s, a); break;
+        default: hipLaunchKernelGGL(expect_open_kernel<64>, grid, blk, 0, s, a); break;
+        }
+    } else {
+        ExpectArgs a{};
+        a.fw = h->d_fw; a.ops = x.d_ops; a.stride_k = ops_per_traj ? (size_t)M * m2 : 0; a.out = x.d_res;
+        a.N = h->N; a.NP = h->NP; a.N_T = h->N_T; a.M = M;
+        static LdsLimit lim;
+        const size_t lds = expect_lds_bytes(h->NP);
+        HIPCHK(h, lim.ensure((const void *)expect_closed_kernel, h->device, lds));
+        const size_t nblk = (pts + 15) / 16;
+        hipLaunchKernelGGL(expect_closed_kernel, dim3((unsigned)nblk, (unsigned)K), dim3(EXPECT_NTH), lds, s, a);
+        // (every workgroup: M observables x NP / 16 row tiles x NP / 4 slices x 4 instructions of 2 . 16 . 16 . 4 flop)
+        flop = (double)K * (double)nblk * M * (h->NP / 16) * (h->NP / 4) * 4.0 * 2048.0;
+    }
+    HIPCHK(h, hipGetLastError());
+    if (h->open) {
+        HIPCHK(h, hipMemcpyAsync(out, x.d_res, res_n * 16, hipMemcpyDeviceToHost, s));
+        HIPCHK(h, hipStreamSynchronize(s));
+    } else {
+        const int rg = getter_fetch(h, out, x.d_res, res_n * 16);
+        if (rg) return rg;
+    }
+    x.info[0] = (double)M; x.info[1] = (double)x.mem.bytes(); x.info[3] = flop;
+    x.info[2] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return GRAPE_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int grape_expect(grape_handle *h, int M, const double *ops, int ops_per_traj, double *out) try {
+    if (!h) { g_create_error = "grape_expect: h == NULL"; return GRAPE_ERR_INVALID; }
+    if (!ops) EXPECT_REFUSE("ops == NULL");
+    if (!out) EXPECT_REFUSE("out == NULL");
+    if (M <= 0) EXPECT_REFUSE("M must be positive");
+    if (M > 16) EXPECT_REFUSE("M > 16: at most 16 observables per call");
+    if (ops_per_traj != 0 && ops_per_traj != 1) EXPECT_REFUSE("ops_per_traj must be 0 (one set of operators for all trajectories) or 1 (one per trajectory)");
+    if (const char *why = expect_stale(h)) { h->err = std::string("grape_expect: ") + why; return GRAPE_ERR_INVALID; }
+    if (!h->shards.empty()) {   // [k][n][m], operators [k][m]: the shards are contiguous blocks of k
+        const auto t0 = std::chrono::steady_clock::now();
+        double bytes = 0., flop = 0.;
+        for (size_t g = 0; g < h->shards.size(); ++g) {
+            grape_handle *c = h->shards[g];
+            const size_t lo = (size_t)h->shard_lo[g];
+            const int rc = expect_single(c, M, ops + (ops_per_traj ? 2 * lo * M * h->N * h->N : 0), ops_per_traj, out + 2 * lo * (h->N_T + 1) * M);
+            if (rc) return multi_fail(h, c, rc);
+            bytes += c->ex.info[1]; flop += c->ex.info[3];
+        }
+        h->ex.info[0] = (double)M; h->ex.info[1] = bytes; h->ex.info[3] = flop;
+        h->ex.info[2] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        return GRAPE_OK;
+    }
+    return expect_single(h, M, ops, ops_per_traj, out);
+}
+GRAPE_BARRIER(h ? &h->err : &g_create_error)
+
+int grape_get_expect_info(grape_handle *h, double *out, int n) try {
+    if (!h || !out) return GRAPE_ERR_INVALID;
+    return copy_info(h->ex.info, 4, out, n);
 }
 GRAPE_BARRIER(h ? &h->err : &g_create_error)
 

@@ -646,6 +646,38 @@ int grape_open_set_running_cost(grape_handle *h, const double *D, int d_per_traj
 int grape_open_backward_xi(grape_handle *h, const double f_total[2], const double *chi, const double *xi, double lambda_b,
                            double *G);
 
+/* Expectation values of operator observables on the stored forward states of the last evaluation, computed on the device
+ * (entry points only, the ABI version stays 7; csrc/grape_expect.hip.h).  The reference hands `observables` to a
+ * callback after every prop_step! of the forward sweep (src/optimize.jl:733-737); here the sweep has run and K (N_T+1) M numbers
+ * come back instead of the K (N_T+1) N states of grape_get_storage(0).
+ *   ops: [M][N*N] complex column-major, one set for all trajectories (ops_per_traj == 0), or [K][M][N*N] (== 1); 1 <= M <= 16.
+ *        The operators need not be Hermitian.
+ *   out: [K][N_T+1][M] complex; entry n belongs to t_n, n = 0 is the initial state.
+ *        closed handle: out[k][n][m] = <Psi_k(t_n)| O_m |Psi_k(t_n)>;  open handle (grape_create_open, N = d):
+ *        out[k][n][m] = tr(O_m rho_k(t_n)).  Values are in the caller's frame: a balanced handle stores D^-1 Psi and the upload
+ *        forms D O D (exact, powers of two), as Dpen is treated.
+ *   - It reads only the stored forward states, so it serves every handle that has them: all closed sizes and routes, with or
+ *     without Dpen or targets, split-phase shards (the local K trajectories), several devices behind one handle (per shard,
+ *     ops sliced like out when ops_per_traj == 1), open handles with or without a running cost.
+ *   - Valid after any successful call that ran the forward half on the current grid (grape_eval with or without G,
+ *     grape_forward, grape_forward_device; after a device-pointer call on a foreign stream it waits for the device).
+ *   - GRAPE_ERR_INVALID with a message that names the call and the reason, before the first HIP call, the handle unchanged and
+ *     usable: h == NULL (message: grape_last_error(NULL)); ops == NULL; out == NULL; M <= 0; M > 16; ops_per_traj not 0 or 1; no
+ *     evaluation yet; the last evaluation failed; grape_set_tlist, grape_open_set_running_cost or grape_eval_batch since
+ *     (grape_open_eval_batch does not invalidate the store).
+ *   - The operators on the device and the result are buffers of the call: allocated by the first call through the handle's
+ *     allocator, grown on demand, freed by grape_destroy.  A failed allocation is GRAPE_ERR_HIP with the size in the message and
+ *     nothing is left allocated.  Nothing an evaluation, a getter, the time gradient, a Hessian-vector product or a batch reads
+ *     or writes is touched: a grape_eval afterwards is bit for bit what it was.
+ *   - Two calls give the same bits; the value of one observable does not depend on M, on its position in ops or on the other
+ *     operators, bit for bit (no atomics, every reduction in a fixed order). */
+int grape_expect(grape_handle *h, int M, const double *ops, int ops_per_traj, double *out);
+
+/* What the last grape_expect of this handle did: [0] its M;  [1] bytes this feature holds on the device;  [2] milliseconds of the
+ * last call (host wall time, copies included);  [3] flop of the matrix instructions the kernel executed (0 on an open handle,
+ * whose kernel is element-wise).  Returns the number of entries written (at most n). */
+int grape_get_expect_info(grape_handle *h, double *out, int n);
+
 const char *grape_last_error(grape_handle *h); /* h may be NULL: error of the last failed create */
 int grape_abi_version(void);
 

@@ -451,6 +451,40 @@ function hvp_info(h::Handle)
 end
 
 """
+    expect!(out, h, ops)
+
+Expectation values of operator observables on the stored forward states of the last evaluation of `h`, computed on the device
+(grape_expect): what the reference hands to `cb(propagator, observables)` after every `prop_step!` of its forward sweep
+(src/optimize.jl:733-737), without moving the states to the host.  `ops` is `N × N × M` (one set of operators for all
+trajectories) or `N × N × M × K` (Julia's column-major layout is the ABI's: no copy), `1 ≤ M ≤ 16`, not necessarily Hermitian;
+`out` is `M × (N_T+1) × K` with `out[m, n, k] = ⟨Ψ_k(t_{n-1})|O_m|Ψ_k(t_{n-1})⟩` (`tr(O_m ρ_k)` on an open-system handle, `N = d`);
+`out[:, 1, k]` belongs to the initial state.  Valid after `fg!` (with or without gradient) or `grape_forward` on the current
+time grid; everything else is refused with a message (include/grape_hip.h).
+"""
+function expect!(out::Array{ComplexF64,3}, h::Handle, ops::Array{ComplexF64})
+    ndims(ops) in (3, 4) || throw(DimensionMismatch("ops must be N × N × M or N × N × M × K"))
+    size(ops, 1) == h.N && size(ops, 2) == h.N || throw(DimensionMismatch("ops must hold N × N = $(h.N) × $(h.N) matrices"))
+    ndims(ops) == 3 || size(ops, 4) == h.K || throw(DimensionMismatch("ops per trajectory need K = $(h.K) sets"))
+    M = size(ops, 3)
+    size(out) == (M, h.N_T + 1, h.K) || throw(DimensionMismatch("out must be M × (N_T+1) × K = $M × $(h.N_T + 1) × $(h.K)"))
+    check(h, GC.@preserve out ops ccall((:grape_expect, libgrape), Cint, (Ptr{Cvoid}, Cint, Ptr{ComplexF64}, Cint, Ptr{ComplexF64}),
+                                        h.ptr, M, ops, ndims(ops) == 4 ? 1 : 0, out))
+    return out
+end
+
+"""
+    expect_info(h)
+
+What the last `expect!` did (grape_get_expect_info): its `M`, `bytes` the feature holds on the device, milliseconds of the call
+(host wall time, copies included), `mfma_flop` of the matrix instructions (0 on an open-system handle).
+"""
+function expect_info(h::Handle)
+    out = zeros(Float64, 4)
+    GC.@preserve out ccall((:grape_get_expect_info, libgrape), Cint, (Ptr{Cvoid}, Ptr{Float64}, Cint), h.ptr, out, 4)
+    return (M = Int(out[1]), bytes = Int(out[2]), ms = out[3], mfma_flop = out[4])
+end
+
+"""
     hvp_forward!(h, V; dtau=nothing, dsums=nothing, dpsiT=nothing)
 
 First half of a split Hessian-vector product (grape_hvp_forward): the tangent forward sweep of the columns of the `L*N_T × nv`
