@@ -61,6 +61,7 @@ import os
 import re
 import struct
 import sys
+from types import SimpleNamespace
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from gcn import Prog, Reg, V, A, S, VCC, EXEC, Neg, Abs, kernel_text  # noqa: E402
@@ -635,7 +636,9 @@ class Gen:
 
         sk0 = 0
         if fused:
-            assert NS == 4 and not half_last and not bload
+            # (NS = 3 with half_last: a Hermitian square whose left operand is formed here -- gen_t16q.py; the stores of the
+            # fourth row tile ride behind the matrix instructions of slot 2, no fragments are requested for it)
+            assert not bload and (NS == 4 or (NS == 3 and half_last))
 
             def rdk(pl, so, r):      # k-block 0, slot by slot: the twelve fragment registers hold [plane][k-step] of ONE slot
                 p.tag = "fragment"
@@ -650,7 +653,7 @@ class Gen:
             for r in range(4):
                 for pl in range(3):
                     rdk(pl, 0, r)
-            for so in range(4):
+            for so in range(NS):
                 gaps = [[] for _ in range(12)]       # what rides behind matrix instruction j = 3 r + pl of this slot
                 if so < 3:
                     fused["valu"](so + 1)
@@ -660,7 +663,7 @@ class Gen:
                     last = {pl: (4 * pl + 1 if pend else 0) for pl in range(3)}
                     # fragment (pl, r) of the next slot: behind the two stores of its plane and behind the matrix
                     # instruction that was the last reader of its register
-                    for r in range(4):
+                    for r in range(4 if so + 1 < NS else 0):
                         for pl in range(3):
                             gaps[max(last[pl], 3 * r + pl)].append(lambda pl=pl, r=r: rdk(pl, so + 1, r))
                 j = 0
@@ -753,6 +756,20 @@ class Gen:
             p.dpp_mov(tmp.sub(1), x.sub(1), ctrl, row_mask=rm)
             p.valu(op, x, x, tmp)
 
+    # ---- hooks of the variant whose second product is a Hermitian square on cells the plan marks (gen_t16q.py) ----
+    def second_product_fork(self, cx):
+        pass
+
+    def second_product_square(self, cx, L_join):
+        pass
+
+    def cell_coeffs(self, q):
+        """thunk that loads c3..c15 of this cell's coefficient set behind the first k-block of the second product, or None"""
+        return None
+
+    def load_c16(self, k16):
+        self.smov64(k16, self.c["C16"])
+
     # -----------------------------------------------------------------------------------------------------------------
     def cell(self):
         p, c = self.p, self.s_c
@@ -828,6 +845,8 @@ class Gen:
             p.ds_write(64, self.v_EW1, A2im[1].d(r), EXH + 128 * r)
         p.s_waitcnt(lgkm=0)
         p.s_barrier()                                   # (also: everybody is done reading A)
+        cx = SimpleNamespace(Qt=Qt, A2re=A2re, A2im=A2im, A2sm=A2sm)
+        self.second_product_fork(cx)
         # scalars of the NEXT cell (its operator bases, dt): requested here, needed by the last product
         self.advance()
         self.cell_bases_issue(self.s_nkc, self.s_nn, self.s_ncell)
@@ -866,7 +885,8 @@ class Gen:
                                 lambda r=r, a2r=a2r, a2i=a2i: p.valu("v_add_f64", A2sm[sl].d(r), a2r, a2i)])
             self.interleave(streams)
 
-        self.product(Qt, [A2re, A2im, A2sm], fused={"valu": valu2, "stores": lambda sl: self.plane_stores(sl, tt[0], tt[1], Qt[sl][1])})
+        self.product(Qt, [A2re, A2im, A2sm], fused={"valu": valu2, "stores": lambda sl: self.plane_stores(sl, tt[0], tt[1], Qt[sl][1]),
+                                                    "post": self.cell_coeffs(False)})
         for t in tt + A2sm:
             vp.free(t)
         self.cell_bases_finish(self.s_nkc)
@@ -1008,6 +1028,7 @@ class Gen:
         p.s_waitcnt(lgkm=0)
         p.s_barrier()                                   # everybody is done reading the planes
         p.salu("s_and_b32", self.s_prop, self.s_prop, 1)                 # the verdict is "ok": bit 1 stays clear
+        self.second_product_square(cx, L_vdone)
         p.label(L_vdone)
         # ================= y1 = (y0 + c3 A2 + c4 A)(y0 + c5 A2) + c6 y0 + c7 A2 ======================================
         # planes <- y0 + c3 A2 + c4 A; right operand y0 + c5 A2; start values c6 y0 + c7 A2; A2 parked in the accumulation half
@@ -1066,7 +1087,7 @@ class Gen:
         # right operand y1 + c10 y0 + c11 A in place of y0 + c5 A2; start values in place of y1
         self.stamp(8)
         k16 = S(58, 2)
-        self.smov64(k16, self.c["C16"])
+        self.load_c16(k16)
         tt = [vp.alloc() for _ in range(4)]
 
         def valu4(sl):

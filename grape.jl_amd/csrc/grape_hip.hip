@@ -155,6 +155,21 @@ struct grape_handle {
     int *d_seg_exp = nullptr;           // [seg_n8 | n6 of the plan | seg_n4 + seg_n12] exponents, laid out like CertPlan::exps
     int seg_n8 = 0, seg_n4 = 0, seg_n12 = 0, seg8_stride = 0, seg_exp_off = 0;
     int *d_segplan = nullptr;           // [KC * N_T] 1: the plan of the last evaluation certified the cell for ECON_SEG_THETA
+    // The tables have three users -- the certificate, the segment certificate and the Hermitian-square cell (asm16q below) -- and
+    // are built once when any of them wants them: d_t86 = t8 | t6, d_t412 = t4 | t12, d_texp the exponent words of all four.
+    // d_cert / d_seg / d_*_exp above alias them and are set only when their OWN switch is on: they are what the getters and the
+    // plan's cert_use / seg_use go by.  (d_seg8 is where the segment test reads t8 -- d_t86 or a table of its own -- and is set
+    // whenever t4 | t12 are built, also for this route alone; the getter goes by d_seg.)
+    double *d_t86 = nullptr, *d_t412 = nullptr;
+    int *d_texp = nullptr;
+    int t_n8 = 0, t_n6 = 0, t_n4 = 0, t_n12 = 0;
+    // expm_t16q_asm (asm/gen_t16q.py): cells the plan certifies for the segment 1.11 run their second product as a Hermitian
+    // square with the coefficient set T16Q_* (625 instead of 697 matrix instructions per wave).  Shared controls, 1 <= L <= 2;
+    // GRAPE_EXPM_T16Q=0 off, 1 on for every eligible handle, unset: on when every workgroup walks at least
+    // T16Q_MIN_WALK cells.  Independent of GRAPE_EXPM_CERT, GRAPE_DERIV_SEG and GRAPE_DERIV_ECON.
+    bool asm16q = false;
+    bool t16q_twin = false;      // ... the same route with GRAPE_EXPM_ASM=0: expm_t18_kernel<4, true, true, T16> reads bit 9 of the plan words and
+                                 // takes the same path (624 matrix instructions per wave), under the same switch and the same rule
     // the four-product route as hand-allocated assembly (asm/gen_t16.py; GRAPE_EXPM_ASM=0: the C++ kernel): four tiles
     // per side, Hermitian generators, controls shared by the trajectories
     bool asm16 = false;
@@ -482,7 +497,7 @@ extern "C" int grape_t16p_asm_launch(const void *args, size_t args_size, int *ve
 extern "C" int grape_t18g_asm_launch(const void *args, size_t args_size, int *verdict, void *stream, int blocks,
                                      const void *const *walk, int fuse, int K, const double *dte);
 extern "C" int grape_t16_asm_launch(const void *args, size_t args_size, int *verdict, void *stream, int blocks,
-                                    const void *const *walk, int fuse, int K);
+                                    const void *const *walk, int fuse, int K, int q);
 extern "C" int grape_t18_batch_launch(int herm, const void *args, size_t args_size, const void *strides, size_t strides_size,
                                       int sets, void *stream, int blocks);
 extern "C" void grape_t16_walks(int KC, int N_T, int nblk, int *tab);
@@ -3202,6 +3217,11 @@ int grape_create(grape_handle **out, const grape_problem *p) try {
         // one workgroup per CU (512 registers, 139 KB of LDS), never more workgroups than cells
         const long ncell = (long)h->KC * N_T;
         h->asm_blocks = (int)std::max<long>(1, std::min<long>(h->num_cus, ncell));
+        {   // the Hermitian-square cell: by rule, not for every handle (a short walk gains nothing: DESIGN 4.1)
+            const char *envt = getenv("GRAPE_EXPM_T16Q");
+            const bool eligible = h->asm16 && !h->asm16p && !p->hc_per_traj && L >= 1 && L <= 2;
+            h->asm16q = eligible && (envt ? atoi(envt) != 0 : ncell >= (long)T16Q_MIN_WALK * h->asm_blocks);
+        }
         std::vector<int> tab((size_t)4 * h->asm_blocks);
         grape_t16_walks(h->KC, N_T, h->asm_blocks, tab.data());
         CCHK(h->mem.alloc(&h->d_wgtab, tab.size()));
@@ -3232,6 +3252,17 @@ int grape_create(grape_handle **out, const grape_problem *p) try {
             CCHK(hipMemcpy(h->d_xinit, xi.data(), xi.size() * 8, hipMemcpyHostToDevice));
             CCHK(h->mem.alloc(&h->d_prog, (size_t)2 * K));
             CCHK(hipMemset(h->d_prog, 0, (size_t)2 * K * sizeof(int)));
+        }
+    }
+    if (!h->asm16 && !h->asm18g && h->t16 && h->t18 && h->herm && !h->large && !h->series && h->NT == 4 && !p->hc_per_traj && L >= 1 && L <= 2 &&
+        (long)K * N_T < (1L << 28)) {
+        // the compiled twin of the Hermitian-square route: the rule counts the workgroups the assembly launch would have
+        const char *envt = getenv("GRAPE_EXPM_T16Q");
+        const long ncell = (long)h->KC * N_T, blocks = std::max<long>(1, std::min<long>(h->num_cus, ncell));
+        h->t16q_twin = envt ? atoi(envt) != 0 : ncell >= (long)T16Q_MIN_WALK * blocks;
+        if (h->t16q_twin) {
+            CCHK(h->mem.alloc(&h->d_splan, (size_t)ncell));
+            CCHK(hipMemset(h->d_splan, 0, (size_t)ncell * sizeof(int)));
         }
     }
     // (N <= 16 stays with five products: one tile per side is latency-bound -- the kernel gains nothing from the shorter
@@ -3306,24 +3337,34 @@ int grape_create(grape_handle **out, const grape_problem *p) try {
         static_assert(T16_PLAN_LMAX == GRAPE_CERT_LMAX, "power table of t16_plan_kernel");
         const bool want_cert = h->asm16 && L >= 1 && L <= GRAPE_CERT_LMAX && !(envc && atoi(envc) == 0);
         const bool want_seg = h->asm16 && h->deriv_econ && L >= 1 && L <= 2 && !(envg && atoi(envg) == 0);
-        if (want_cert || want_seg) {
-            const CertPlan pl(L, want_seg);
+        const bool want_q = h->asm16q || h->t16q_twin;
+        // (what is BUILT: t8 | t6 for the certificate or the Hermitian-square cell, t4 | t12 for the segment certificate or that
+        // cell; who may READ them is a matter of each user's own switch)
+        const bool build_cert = want_cert || want_q, build_seg = want_seg || want_q;
+        if (build_cert || build_seg) {
+            const CertPlan pl(L, build_seg);
             const int nt = pl.n8 + pl.n6, ns = pl.n4 + pl.n12;
+            CCHK(h->mem.alloc(&h->d_texp, pl.exps.size()));
+            CCHK(hipMemcpy(h->d_texp, pl.exps.data(), pl.exps.size() * sizeof(int), hipMemcpyHostToDevice));
+            h->t_n8 = pl.n8; h->t_n6 = pl.n6;
+            if (build_cert) CCHK(h->mem.alloc(&h->d_t86, (size_t)KCn * nt));
+            if (build_seg) {
+                h->t_n4 = pl.n4; h->t_n12 = pl.n12;
+                CCHK(h->mem.alloc(&h->d_t412, (size_t)KCn * ns));
+            }
             if (want_cert) {
                 h->cert_n8 = pl.n8; h->cert_n6 = pl.n6;
-                CCHK(h->mem.alloc(&h->d_cert, (size_t)KCn * nt));
-                CCHK(h->mem.alloc(&h->d_cert_exp, (size_t)nt));
-                CCHK(hipMemcpy(h->d_cert_exp, pl.exps.data(), (size_t)nt * sizeof(int), hipMemcpyHostToDevice));
+                h->d_cert = h->d_t86; h->d_cert_exp = h->d_texp;
             }
             if (want_seg) {
                 h->seg_n8 = pl.n8; h->seg_n4 = pl.n4; h->seg_n12 = pl.n12; h->seg_exp_off = nt;
-                CCHK(h->mem.alloc(&h->d_seg, (size_t)KCn * ns));
-                CCHK(h->mem.alloc(&h->d_seg_exp, pl.exps.size()));
-                CCHK(hipMemcpy(h->d_seg_exp, pl.exps.data(), pl.exps.size() * sizeof(int), hipMemcpyHostToDevice));
-                if (want_cert) { h->d_seg8 = h->d_cert; h->seg8_stride = nt; }
-                else { CCHK(h->mem.alloc(&h->d_seg8, (size_t)KCn * pl.n8)); h->seg8_stride = pl.n8; }
+                h->d_seg = h->d_t412; h->d_seg_exp = h->d_texp;
                 CCHK(h->mem.alloc(&h->d_segplan, (size_t)KCn * N_T));
                 CCHK(hipMemset(h->d_segplan, 0, (size_t)KCn * N_T * sizeof(int)));
+            }
+            if (build_seg) {   // t8 of the segment test: the table of t8 | t6 when the handle has it, else one of its own
+                if (build_cert) { h->d_seg8 = h->d_t86; h->seg8_stride = nt; }
+                else { CCHK(h->mem.alloc(&h->d_seg8, (size_t)KCn * pl.n8)); h->seg8_stride = pl.n8; }
             }
             DeviceBufs tmp;   // (scratch of the build: released when it is done)
             int *d_job[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -3345,17 +3386,17 @@ int grape_create(grape_handle **out, const grape_problem *p) try {
                 hipLaunchKernelGGL(cert_mm_kernel, dim3((unsigned)(pl.n3 + pl.n4), nc), dim3(256), 0, 0, d_scr, pl.nmat, N, pl.M + pl.n2, (const int *)d_job[2],
                                    (const int *)d_job[3]);
                 // t8 | t6 into the certificate's table, or t8 alone into the segment tables' own; the same sums either way
-                if (want_cert)
+                if (build_cert)
                     hipLaunchKernelGGL(cert_trace_kernel, dim3((unsigned)nt, nc), dim3(256), 0, 0, (const double2 *)d_scr, pl.nmat, N, (const int *)d_job[4],
-                                       (const int *)d_job[5], nt, h->d_cert + (size_t)kc0 * nt);
+                                       (const int *)d_job[5], nt, h->d_t86 + (size_t)kc0 * nt);
                 else
                     hipLaunchKernelGGL(cert_trace_kernel, dim3((unsigned)pl.n8, nc), dim3(256), 0, 0, (const double2 *)d_scr, pl.nmat, N, (const int *)d_job[4],
                                        (const int *)d_job[5], pl.n8, h->d_seg8 + (size_t)kc0 * pl.n8);
-                if (want_seg) {
+                if (build_seg) {
                     hipLaunchKernelGGL(cert_mm_kernel, dim3((unsigned)pl.n6, nc), dim3(256), 0, 0, d_scr, pl.nmat, N, pl.M + pl.n2 + pl.n3 + pl.n4,
                                        (const int *)d_job[6], (const int *)d_job[7]);
                     hipLaunchKernelGGL(cert_trace_kernel, dim3((unsigned)ns, nc), dim3(256), 0, 0, (const double2 *)d_scr, pl.nmat, N,
-                                       (const int *)d_job[4] + nt, (const int *)d_job[5], ns, h->d_seg + (size_t)kc0 * ns);
+                                       (const int *)d_job[4] + nt, (const int *)d_job[5], ns, h->d_t412 + (size_t)kc0 * ns);
                 }
                 CCHK(hipGetLastError());
             }
@@ -3506,13 +3547,15 @@ int grape_forward_device(grape_handle *h, const double *d_pulsevals, double *d_o
                     T16PlanArgs pa{};
                     pa.gram = h->d_gram; pa.eps = h->d_eps; pa.shape = h->d_shape; pa.dts = h->d_dts; pa.flags = h->d_flags;
                     pa.KC = h->KC; pa.L = h->L; pa.N_T = h->N_T; pa.N = h->N;
-                    pa.splan = (h->asm16 && (h->asm_sq || h->d_cert)) ? h->d_splan : nullptr;
-                    pa.sq_on = h->asm_sq ? 1 : 0;
-                    pa.cert = h->d_cert; pa.cert_exp = h->d_cert_exp; pa.n8 = h->cert_n8; pa.n6 = h->cert_n6;
+                    pa.splan = ((h->asm16 && (h->asm_sq || h->d_cert || h->asm16q)) || h->t16q_twin) ? h->d_splan : nullptr;
+                    pa.sq_on = (h->asm16 && h->asm_sq) ? 1 : 0;   // (the compiled kernel squares nothing)
+                    // (the tables the handle has; cert_use / seg_use / q_use: whose decisions this plan writes)
+                    pa.cert = h->d_t86; pa.cert_exp = h->d_t86 ? h->d_texp : nullptr; pa.n8 = h->t_n8; pa.n6 = h->t_n6;
                     pa.verdict = h->d_cellflag;
-                    pa.seg = h->d_seg; pa.seg8 = h->d_seg8; pa.seg8_stride = h->seg8_stride; pa.seg8_exp = h->d_seg_exp;
-                    pa.seg_exp = h->d_seg_exp ? h->d_seg_exp + h->seg_exp_off : nullptr;
-                    pa.s8 = h->seg_n8; pa.n4 = h->seg_n4; pa.n12 = h->seg_n12; pa.segplan = h->d_segplan;
+                    pa.seg = h->d_t412; pa.seg8 = h->d_seg8; pa.seg8_stride = h->seg8_stride; pa.seg8_exp = h->d_t412 ? h->d_texp : nullptr;
+                    pa.seg_exp = h->d_t412 ? h->d_texp + h->t_n8 + h->t_n6 : nullptr;
+                    pa.s8 = h->d_t412 ? h->t_n8 : 0; pa.n4 = h->t_n4; pa.n12 = h->t_n12; pa.segplan = h->d_segplan;
+                    pa.cert_use = h->d_cert ? 1 : 0; pa.seg_use = h->d_seg ? 1 : 0; pa.q_use = (h->asm16q || h->t16q_twin) ? 1 : 0;
                     const unsigned plan_blocks = (unsigned)(h->KC * ((h->N_T + T16_PLAN_TPB - 1) / T16_PLAN_TPB));
                     const size_t plan_lds = t16_plan_lds(pa);
                     switch (plan_lds ? h->L : 0) {   // (tables: 1 <= L <= T16_PLAN_LMAX)
@@ -3555,11 +3598,13 @@ int grape_forward_device(grape_handle *h, const double *d_pulsevals, double *d_o
                     walk_fuse = h->asm_walk & (1 | ((h->fuse && h->fuse_on && h->want_bw) ? 2 : 0));
                     if (walk_fuse) HIPCHK(h, stream_fill(h->d_prog, 0, (size_t)2 * h->K * sizeof(int), s));
                     const void *walk[6] = {h->d_wgtab, h->d_xinit, h->d_fw, h->d_bw, h->d_prog, h->d_splan};
-                    e = (hipError_t)grape_t16_asm_launch(&ea, sizeof(ea), h->d_cellflag, (void *)s, h->asm_blocks, walk, walk_fuse, h->K);
+                    e = (hipError_t)grape_t16_asm_launch(&ea, sizeof(ea), h->d_cellflag, (void *)s, h->asm_blocks, walk, walk_fuse, h->K, h->asm16q ? 1 : 0);
                     h->credit_pending = true;
                 }
-                else
+                else {
+                    ea.splan = h->t16q_twin ? h->d_splan : nullptr;
                     e = (hipError_t)grape_t18_launch(h->NT, h->herm ? 1 : 0, t16 ? 1 : 0, &ea, sizeof(ea), (void *)s, blocks16);
+                }
                 if (t16 && e == hipSuccess) {   // the cells it listed, by the degree-18 variant (none: the launch ends at once)
                     ea.listed = 1;
                     e = (hipError_t)grape_t18_launch(h->NT, 1, 0, &ea, sizeof(ea), (void *)s, t18_blocks);
@@ -4697,10 +4742,10 @@ int grape_get_work(grape_handle *h, double *out, int n) try {
     if (!h || !out || n < 4) return GRAPE_ERR_INVALID;
     if (h->open) return open_work(h, out, n);
     if (!h->shards.empty()) {   // every entry is a count: the shards add up
-        const int m = n < 21 ? n : 21;
+        const int m = n < 22 ? n : 22;
         std::fill(out, out + m, 0.0);
         for (grape_handle *c : h->shards) {
-            double cw[21] = {0.};
+            double cw[22] = {0.};
             const int rc = grape_get_work(c, cw, m);
             if (rc < 0) return multi_fail(h, c, rc);
             for (int i = 0; i < m; ++i) out[i] = (i == 15 || i == 16 || i == 18) ? cw[i] : out[i] + cw[i];   // ([15], [16]: kernel ids, the same in every shard)
@@ -4782,9 +4827,10 @@ int grape_get_work(grape_handle *h, double *out, int n) try {
     // for ECON_SEG_THETA by the plan (deriv_econ_kernel's rule, counted from the same arrays).  One copy of the plan words
     // and the flags serves both.
     if (n > 19) {
-        double certified = 0.0, seg = 0.0;
+        double certified = 0.0, seg = 0.0, qcells = 0.0;
         const bool want_seg = n > 20 && h->d_segplan && h->deriv_econ;
-        if ((h->d_cert || want_seg) && h->d_splan && !h->series) {
+        const bool want_q = n > 21 && (h->asm16q || h->t16q_twin);
+        if ((h->d_cert || want_seg || want_q) && h->d_splan && !h->series) {
             const size_t ncell = (size_t)h->KC * h->N_T;
             std::vector<int> plan(ncell);
             int fl[8];
@@ -4793,6 +4839,8 @@ int grape_get_work(grape_handle *h, double *out, int n) try {
             const bool tried = !(4L * fl[6] > (long)ncell);
             if (tried && h->d_cert)
                 for (int w : plan) certified += (w & T16_PLAN_CERT) ? 1.0 : 0.0;
+            if (tried && want_q)
+                for (int w : plan) qcells += (w & T16_PLAN_Q) ? 1.0 : 0.0;
             if (tried && want_seg) {
                 std::vector<int> sp(ncell), verdict(ncell);
                 { const int rc_ = getter_fetch(h, sp.data(), h->d_segplan, ncell * sizeof(int)); if (rc_) return rc_; }
@@ -4806,6 +4854,8 @@ int grape_get_work(grape_handle *h, double *out, int n) try {
         }
         out[19] = certified;
         if (n > 20) out[20] = seg;
+        // cells of the last evaluation whose second product ran as a Hermitian square (expm_t16q_asm; bits of the same plan words)
+        if (n > 21) out[21] = qcells;
     }
     return 4;
 }

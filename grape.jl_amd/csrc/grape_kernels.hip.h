@@ -75,6 +75,9 @@ struct ExpmArgs {
     // polynomial kernel, more than two controls shared by all trajectories: S_n = sum_l eps_ln shape_ln H_l, formed once per
     // evaluation by ctrl_sum_kernel ([N_T][2][NP*NP], planar like Hcf) -- the cell then fetches H0_k and S_n, whatever L
     const double *Sf;
+    // compiled four-product kernel at four tiles per side: nullptr, or the plan words of the evaluation when the Hermitian-square
+    // route is on (bit 9, T16_PLAN_Q: the cell's second product is y0 = c1 A2 A2 with the T16Q_* coefficients)
+    const int *splan;
 #ifdef GRAPE_DIAG
     int ablate;  // diagnostic builds only (tools/ablate.sh): bit0 skip invert16, bit1 skip solve
     unsigned long long *stamps;  // [nblocks][16] s_memtime at phase boundaries (diagnostic builds only)
@@ -124,10 +127,25 @@ struct T16PlanArgs {
     const int *seg8_exp;  // [s8]
     int seg8_stride, s8, n4, n12;
     int *segplan;         // [KC * N_T]: 1 for a cell with no planned squarings whose spectral radius is certified <= ECON_THETAS[0]
+    // Who reads the tables.  `cert` and `seg` say which tables the handle HAS (grape_create builds them when any of three users
+    // wants them); the certified bit and the verdict it implies are written only with cert_use, segplan only with seg_use,
+    // bit 9 only with q_use -- each user's output is the same bits whatever the other two switches say.
+    int cert_use, seg_use;
+    // Hermitian-square cell (asm/gen_t16q.py, coefficient set T16Q_*, good for spectra inside T16Q_THETA = ECON_SEG_THETA):
+    // q_use marks with bit 9 the cells that (a) have no planned squarings, (b) pass the certificate's inequality for
+    // T16_THETA at s = 0 -- so the in-cell verdict of the other path would have been 0 and the hand-over list is the same
+    // with and without the route -- and (c) are certified for the segment by t16_seg_certified; verdict[cell] = 0 is
+    // written for them (the marked cell computes no bound).  Needs both sets of tables and splan.
+    int q_use;
 };
-// splan[cell]: bits 0..7 the planned squarings, bit 8 the cell's spectrum was certified before the launch
+// splan[cell]: bits 0..7 the planned squarings, bit 8 the cell's spectrum was certified before the launch, bit 9 the cell's
+// second product is the Hermitian square
 #define T16_PLAN_SQ_MASK 0xFF
 #define T16_PLAN_CERT 0x100
+#define T16_PLAN_Q 0x200
+// cells per workgroup of the launch from which a handle takes expm_t16q_asm when GRAPE_EXPM_T16Q is unset (grape_create)
+#define T16Q_MIN_WALK 8
+static_assert(T16Q_THETA == ECON_SEG_THETA, "the segment the plan certifies is the one the T16Q_* set was made for");
 #define T16_PLAN_TPB 128    // cells per workgroup
 #define T16_PLAN_LMAX 4     // controls the trace tables are built for (GRAPE_CERT_LMAX)
 #define T16_PLAN_PMAX 12    // largest power of a pulse value in a monomial (tr H^12)
@@ -267,22 +285,24 @@ __global__ void __launch_bounds__(T16_PLAN_TPB) t16_plan_kernel(T16PlanArgs a) {
                 double x = 1.0;
                 for (int j = 0; j <= T16_PLAN_PMAX; ++j, x *= e[1 + l]) pw[l][j][tid] = x;
             }
-        double p8 = 0., S8 = 0.;
-        const bool have8 = a.splan && a.cert;
+        double p8 = 0., S8 = 0., p6 = 0.;
+        const bool q_use = tables && a.q_use && a.splan && a.cert && a.seg;
+        const bool have8 = a.splan && a.cert && (a.cert_use || q_use);
+        int word = sq;
         if (a.splan) {
             // the certificate of the cell as it will be exponentiated (A / 2^sq); the estimate above keeps its two roles, the
             // squaring plan and the "more than a quarter out of range" rule
             bool cert = false;
-            if (tables && a.cert) {
-                double p6, S6;
+            if (tables && have8) {
+                double S6;
                 t16_trace_poly<LT>(tt, tx, a.n8, pw, p8, S8);
                 t16_trace_poly<LT>(tt + a.n8, tx + a.n8, a.n6, pw, p6, S6);
-                cert = t16_certified(p8, S8, p6, dt, sq);
+                cert = a.cert_use && t16_certified(p8, S8, p6, dt, sq);
             }
             if (cert) a.verdict[cell] = 0;
-            a.splan[cell] = sq | (cert ? T16_PLAN_CERT : 0);
+            word |= cert ? T16_PLAN_CERT : 0;
         }
-        if (tables && a.seg) {
+        if (tables && a.seg && (a.seg_use || q_use)) {
             bool seg = false;
             if (sq == 0) {
                 const double *t = tt + nc + n8own;
@@ -293,8 +313,13 @@ __global__ void __launch_bounds__(T16_PLAN_TPB) t16_plan_kernel(T16PlanArgs a) {
                 t16_trace_poly<LT>(t + a.n4, x + a.n4, a.n12, pw, p12, S12);
                 seg = t16_seg_certified(p4, S4, p8, S8, p12, S12, dt);
             }
-            a.segplan[cell] = seg ? 1 : 0;
+            if (a.seg_use) a.segplan[cell] = seg ? 1 : 0;
+            if (q_use && seg && t16_certified(p8, S8, p6, dt, 0)) {
+                a.verdict[cell] = 0;
+                word |= T16_PLAN_Q;
+            }
         }
+        if (a.splan) a.splan[cell] = word;
     }
     const unsigned long long m = __ballot(out);
     if ((threadIdx.x & 63) == 0 && m) atomicAdd(&a.flags[6], (int)__popcll(m));

@@ -692,7 +692,7 @@ struct T16Count {
 
 // SYM as in expm_t18_cell: the tile symmetry of the Hermitian square (NT >= 3); without it all NT row tiles of A2 come
 // from the matrix instructions (NT <= 2, where no wave computes an off-diagonal tile it could mirror).
-template <int NT, bool SYM, class HookFirst, class HookLast>
+template <int NT, bool SYM, bool Q = false, class HookFirst, class HookLast>
 __device__ __forceinline__ bool expm_t16_cell(double *smem, const int wave, const int lane_in, Strip3M<NT> &U, HookFirst hook_first,
                                               HookLast hook_last) {
     // (per-lane addresses are recomputed per stage from a pinned copy of the lane index: shared between the stages they
@@ -702,6 +702,13 @@ __device__ __forceinline__ bool expm_t16_cell(double *smem, const int wave, cons
     constexpr int LD = LY::LD, NS = SYM ? NT - 1 : NT;
     constexpr bool HALF = SYM && NT == 4;
     static_assert(!SYM || NT >= 3, "tile symmetry needs at least three tiles per side");
+    // Q: the second product is the Hermitian square y0 = c1 A2 A2 with the coefficient set T16Q_* (c2 = 0; asm/gen_t16q.py is
+    // the same path in the assembly kernel): the cells the plan marked with bit 9 of their plan word, no bound, verdict "ok"
+    static_assert(!Q || (SYM && NT == 4), "the Hermitian-square path is a four-tile path");
+#define T16_K(i) constexpr double K##i = Q ? T16Q_C##i : T16_C##i
+    T16_K(1); T16_K(2); T16_K(3); T16_K(4); T16_K(5); T16_K(6); T16_K(7); T16_K(8); T16_K(9); T16_K(10); T16_K(11); T16_K(12); T16_K(13);
+    T16_K(14); T16_K(15); T16_K(16);
+#undef T16_K
     double *R = smem, *e1 = smem + LY::E1, *e2 = smem + LY::E2, *red = smem + LY::RED;
     const T18NoHook nohook;
     Strip3M<NT> As, A2, Y0;
@@ -725,43 +732,66 @@ __device__ __forceinline__ bool expm_t16_cell(double *smem, const int wave, cons
     }
     Acc3<NT> q;
     { T16_FRESH_LANE(l2); lane = l2; }
-    // ---- y0 = (c1 A2 + c2 A) A2: the combination goes to the planes, A2 -- alive to the end anyway -- is the right operand ----
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-        U.re[t] = T16_C1 * A2.re[t] + T16_C2 * As.re[t];
-        U.im[t] = T16_C1 * A2.im[t] + T16_C2 * As.im[t];
-        A2.sm[t] = A2.re[t] + A2.im[t];
-    }
-    t18_store_slots<LD, NT, NT>(R, U, wave, lane);
-    __syncthreads();
-    acc3_zero(q);
-    t18_gemm<LD, NT, NT, false>(q, R, A2, wave, lane, nohook);
-    t18_combine<NT, NT>(q, Y0);
-    // ---- spectral bound ----
-    {
-        double f = 0., g = 0.;
-#pragma unroll
-        for (int t = 0; t < NT; ++t)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                f = fma(Y0.re[t][r], Y0.re[t][r], f); f = fma(Y0.im[t][r], Y0.im[t][r], f);
-                g = fma(A2.re[t][r], Y0.re[t][r], g); g = fma(A2.im[t][r], Y0.im[t][r], g);
-            }
-        f = wave_sum(f);
-        g = wave_sum(g);
-        const double n2w = t18_colsum_max<NT>(A2);
-        if (lane == 0) { red[wave] = f; red[NT + wave] = g; red[2 * NT + wave] = n2w; }
-    }
-    __syncthreads();                                                          // (also: everybody is done reading the planes)
     bool ok;
-    {
-        double F = red[0], G = red[NT], n2 = red[2 * NT];
+    if constexpr (Q) {
+        // ---- y0 = c1 A2 A2: A2 goes to the planes and is its own right operand; upper tiles, mirrored ones by exchange ----
+        (void)K2;
 #pragma unroll
-        for (int w = 1; w < NT; ++w) { F += red[w]; G += red[NT + w]; n2 = fmax(n2, red[2 * NT + w]); }
-        const double m6 = -G / T16_C1;                                        // sum lam^6
-        const double m8 = (F - (T16_C2 * T16_C2) * m6) / (T16_C1 * T16_C1);   // sum lam^8 (cancellation: 55 ulp of F, far inside the 1e-9)
-        constexpr double th2 = T16_THETA * T16_THETA, th8 = th2 * th2 * th2 * th2;
-        ok = (n2 * (1.0 + 1e-9) <= th2) || (m6 >= 0. && m8 * (1.0 + 1e-9) <= th8);   // (NaN: neither)
+        for (int t = 0; t < NT; ++t) A2.sm[t] = A2.re[t] + A2.im[t];
+        t18_store_slots<LD, NT, NT>(R, A2, wave, lane);
+        __syncthreads();
+        {
+            Acc3<NS> qh;
+            acc3_zero(qh);
+            t18_gemm<LD, NS, NT, HALF>(qh, R, A2, wave, lane, nohook);
+            t18_combine<NS, NT>(qh, Y0);
+        }
+#pragma unroll
+        for (int t = 0; t < NS; ++t) { Y0.re[t] = K1 * Y0.re[t]; Y0.im[t] = K1 * Y0.im[t]; }
+        rot_exch_write<NT, 2>(e1, Y0.re[2], Y0.im[2], wave, lane, 1.0);
+        rot_exch_write<NT>(e2, Y0.re[1], Y0.im[1], wave, lane, 1.0);
+        __syncthreads();                                                      // (also: everybody is done reading the planes)
+        t18_exch_add<NT, 2>(e1, Y0, wave, lane);
+        t18_exch_read_last<NT>(e2, Y0, wave, lane);
+        ok = true;
+    } else {
+        // ---- y0 = (c1 A2 + c2 A) A2: the combination goes to the planes, A2 -- alive to the end anyway -- is the right operand ----
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+            U.re[t] = K1 * A2.re[t] + K2 * As.re[t];
+            U.im[t] = K1 * A2.im[t] + K2 * As.im[t];
+            A2.sm[t] = A2.re[t] + A2.im[t];
+        }
+        t18_store_slots<LD, NT, NT>(R, U, wave, lane);
+        __syncthreads();
+        acc3_zero(q);
+        t18_gemm<LD, NT, NT, false>(q, R, A2, wave, lane, nohook);
+        t18_combine<NT, NT>(q, Y0);
+        // ---- spectral bound ----
+        {
+            double f = 0., g = 0.;
+#pragma unroll
+            for (int t = 0; t < NT; ++t)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    f = fma(Y0.re[t][r], Y0.re[t][r], f); f = fma(Y0.im[t][r], Y0.im[t][r], f);
+                    g = fma(A2.re[t][r], Y0.re[t][r], g); g = fma(A2.im[t][r], Y0.im[t][r], g);
+                }
+            f = wave_sum(f);
+            g = wave_sum(g);
+            const double n2w = t18_colsum_max<NT>(A2);
+            if (lane == 0) { red[wave] = f; red[NT + wave] = g; red[2 * NT + wave] = n2w; }
+        }
+        __syncthreads();                                                          // (also: everybody is done reading the planes)
+        {
+            double F = red[0], G = red[NT], n2 = red[2 * NT];
+#pragma unroll
+            for (int w = 1; w < NT; ++w) { F += red[w]; G += red[NT + w]; n2 = fmax(n2, red[2 * NT + w]); }
+            const double m6 = -G / K1;                                        // sum lam^6
+            const double m8 = (F - (K2 * K2) * m6) / (K1 * K1);   // sum lam^8 (cancellation: 55 ulp of F, far inside the 1e-9)
+            constexpr double th2 = T16_THETA * T16_THETA, th8 = th2 * th2 * th2 * th2;
+            ok = (n2 * (1.0 + 1e-9) <= th2) || (m6 >= 0. && m8 * (1.0 + 1e-9) <= th8);   // (NaN: neither)
+        }
     }
     ok = __builtin_amdgcn_readfirstlane((int)ok) != 0;
     { T16_FRESH_LANE(l3); lane = l3; }
@@ -770,12 +800,12 @@ __device__ __forceinline__ bool expm_t16_cell(double *smem, const int wave, cons
     // operand alive the product runs 32 doubles per lane above what the register file holds beside A, A2 and the accumulators)
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
-        U.re[t] = Y0.re[t] + T16_C3 * A2.re[t] + T16_C4 * As.re[t];
-        U.im[t] = Y0.im[t] + T16_C3 * A2.im[t] + T16_C4 * As.im[t];
-        const d4 vr = T16_C6 * Y0.re[t] + T16_C7 * A2.re[t], vi = T16_C6 * Y0.im[t] + T16_C7 * A2.im[t];
+        U.re[t] = Y0.re[t] + K3 * A2.re[t] + K4 * As.re[t];
+        U.im[t] = Y0.im[t] + K3 * A2.im[t] + K4 * As.im[t];
+        const d4 vr = K6 * Y0.re[t] + K7 * A2.re[t], vi = K6 * Y0.im[t] + K7 * A2.im[t];
         q.p1[t] = vr; q.p2[t] = (d4){0., 0., 0., 0.}; q.p3[t] = vr + vi;       // re = p1 - p2, im = p3 - p1 - p2
-        Y0.re[t] += T16_C5 * A2.re[t];
-        Y0.im[t] += T16_C5 * A2.im[t];
+        Y0.re[t] += K5 * A2.re[t];
+        Y0.im[t] += K5 * A2.im[t];
         Y0.sm[t] = Y0.re[t] + Y0.im[t];
     }
     t18_store_slots<LD, NT, NT>(R, U, wave, lane);                            // planes = y0 + c3 A2 + c4 A
@@ -792,24 +822,24 @@ __device__ __forceinline__ bool expm_t16_cell(double *smem, const int wave, cons
         double *x = R + (lane >> 4) * LD + 16 * wave + (lane & 15);
 #pragma unroll
         for (int t = 0; t < NT; ++t) {
-            const d4 y0r = Y0.re[t] - T16_C5 * A2.re[t], y0i = Y0.im[t] - T16_C5 * A2.im[t];
-            const d4 xr = Y1.re[t] + T16_C8 * A2.re[t] + T16_C9 * As.re[t], xi = Y1.im[t] + T16_C8 * A2.im[t] + T16_C9 * As.im[t];
+            const d4 y0r = Y0.re[t] - K5 * A2.re[t], y0i = Y0.im[t] - K5 * A2.im[t];
+            const d4 xr = Y1.re[t] + K8 * A2.re[t] + K9 * As.re[t], xi = Y1.im[t] + K8 * A2.im[t] + K9 * As.im[t];
             const int tb = (wave + t) % NT;
 #pragma unroll
             for (int r = 0; r < 4; ++r) {                                     // planes = y1 + c8 A2 + c9 A, tile by tile
                 const int o = (16 * tb + 4 * r) * LD;
                 x[o] = xr[r]; x[PL + o] = xi[r]; x[2 * PL + o] = xr[r] + xi[r];
             }
-            d4 vr = T16_C12 * Y1.re[t] + T16_C13 * y0r + T16_C14 * A2.re[t] + T16_C15 * As.re[t];
-            const d4 vi = T16_C12 * Y1.im[t] + T16_C13 * y0i + T16_C14 * A2.im[t] + T16_C15 * As.im[t];
+            d4 vr = K12 * Y1.re[t] + K13 * y0r + K14 * A2.re[t] + K15 * As.re[t];
+            const d4 vi = K12 * Y1.im[t] + K13 * y0i + K14 * A2.im[t] + K15 * As.im[t];
             if (t == 0) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r)
-                    if (4 * r + rgd == cdiag) vr[r] += T16_C16;
+                    if (4 * r + rgd == cdiag) vr[r] += K16;
             }
             q.p1[t] = vr; q.p2[t] = (d4){0., 0., 0., 0.}; q.p3[t] = vr + vi;
-            Y0.re[t] = Y1.re[t] + T16_C10 * y0r + T16_C11 * As.re[t];         // right operand in place
-            Y0.im[t] = Y1.im[t] + T16_C10 * y0i + T16_C11 * As.im[t];
+            Y0.re[t] = Y1.re[t] + K10 * y0r + K11 * As.re[t];         // right operand in place
+            Y0.im[t] = Y1.im[t] + K10 * y0i + K11 * As.im[t];
             Y0.sm[t] = Y0.re[t] + Y0.im[t];
         }
     }
@@ -879,7 +909,7 @@ __device__ __forceinline__ void expm_t18_body(const ExpmArgs &a) {
     const int end = listed ? min(__builtin_amdgcn_readfirstlane(a.flags[4]), ncell) : hi;
     const int idx0 = listed ? (int)blockIdx.x : lo + ((int)blockIdx.x >> 3);
     auto cell_at = [&](int i) -> int { return listed ? __builtin_amdgcn_readfirstlane(a.cell_list[i]) : i; };
-    int st_s = 0, st_max = 0, st_ord[5] = {0, 0, 0, 0, 0}, st_sq = 0, st_cells = 0, st_t16 = 0;
+    int st_s = 0, st_max = 0, st_ord[5] = {0, 0, 0, 0, 0}, st_sq = 0, st_cells = 0, st_t16 = 0, st_q = 0;
     bool any_bad = false;
     // Software pipeline over the cells of this workgroup: the result of cell c is stored between the matrix instructions
     // of the first product of cell c+1, the operator tiles of cell c+1 are requested in front of the last product of
@@ -932,7 +962,13 @@ __device__ __forceinline__ void expm_t18_body(const ExpmArgs &a) {
             auto fetch_next = [&](int sk, int r) { if (sk == 1 && r == 0) fa.issue(); };   // (fenced by scheduling barriers on both sides)
             if constexpr (T16) {
                 s = 0; bad = false;
-                const bool ok16 = expm_t16_cell<NT, true>(smem, wave, lane, U, store_prev, fetch_next);
+                bool ok16;
+                if constexpr (NT == 4) {   // cells the plan marked for the Hermitian-square path (a.splan: only with that route on)
+                    const bool q = a.splan != nullptr && (__builtin_amdgcn_readfirstlane(a.splan[cell]) & T16_PLAN_Q) != 0;
+                    if (q) { ok16 = expm_t16_cell<NT, true, true>(smem, wave, lane, U, store_prev, fetch_next); st_q += 1; }
+                    else ok16 = expm_t16_cell<NT, true>(smem, wave, lane, U, store_prev, fetch_next);
+                } else
+                    ok16 = expm_t16_cell<NT, true>(smem, wave, lane, U, store_prev, fetch_next);
                 if (tid == 0 && a.cellflag) a.cellflag[cell] = ok16 ? 0 : 1;   // the verdict (round 6: deriv_econ_kernel reads it)
                 if (ok16) st_t16 += 1;
                 else if (tid == 0) a.cell_list[atomicAdd(&a.flags[4], 1)] = cell;   // to be redone by the five-product launch
@@ -992,6 +1028,7 @@ __device__ __forceinline__ void expm_t18_body(const ExpmArgs &a) {
         // executed, the cells handed over are counted by the launch that redoes them)
         unsigned long long mi = (unsigned long long)st_cells * (T16 ? (SYM ? T16Count<NT>::CELL : T16Count<NT>::CELL_NOSYM) : SYM ? T18Count<NT>::CELL : T18Count<NT>::CELL_GENERAL)
                                 + (unsigned long long)st_sq * T18Count<NT>::GP;
+        mi -= (unsigned long long)st_q * (T18Count<NT>::GP - T18Count<NT>::SQH);   // (the second product of a marked cell is a Hermitian square: 624)
         if constexpr (T16) {
             stat_add(a.stats, 15, (unsigned long long)st_t16);
             atomicAdd(&a.flags[5], st_cells);

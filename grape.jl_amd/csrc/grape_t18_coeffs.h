@@ -81,3 +81,30 @@
 #define T16_C14 0.32660098775353450156
 #define T16_C15 0.9999999999999999025
 #define T16_C16 0.99999999999999991128
+//   * T16Q_C* : the same scheme with c2 = 0 (tools/t16_coeffs.py q): the second product is y0 = c1 A2 A2, the square of a
+//              Hermitian matrix, and runs on the half-tile pipeline of A A.  b15 = 0 is structural (y1 has no x^7 term); the
+//              coefficients 0..14 are those of the degree-14 Chebyshev truncation of exp on the segment minus the absorbable
+//              part of b16 x^16 (b16 = c1^4 = 1.479 / 16!).  |p(-i lam) - exp(-i lam)| <= 2.193e-16 for |lam| <= 1.11
+//              (2 J15(1.11) = 2.19e-16: the missing T15 term, the bound the degree-15 derivative series accepts).
+//              The system of 15 equations has four real branches up to its sign symmetry; this is the one with the smallest
+//              coefficients among the two that round like T16_C* (docs/LAB_NOTEBOOK.md).  Measured in double precision
+//              against an 80-bit reference, random Hermitian N = 64, three matrices per radius (q_rounding of the tool): max
+//              element error 0.8e-16 / 2.0e-16 / 2.0e-16 at rho = 0.5 / 1.0 / 1.11 (T16_C*: 0.9e-16 / 1.6e-16 / 1.6e-16),
+//              2-norm 2.5e-16 / 3.5e-16 / 3.7e-16 (T16_C*: 1.5e-16 / 2.2e-16 / 2.4e-16).
+#define T16Q_THETA 1.11
+#define T16Q_C1 0.00051563001890111433182
+#define T16Q_C2 0.0
+#define T16Q_C3 0.0023030158800575477112
+#define T16Q_C4 0.57294486810438500817
+#define T16Q_C5 0.039952426348918349803
+#define T16Q_C6 9.9345037093649872503
+#define T16Q_C7 0.12383410213207938471
+#define T16Q_C8 -0.036677532080650709165
+#define T16Q_C9 -0.38874283651186037534
+#define T16Q_C10 -8.4588053279285115744
+#define T16Q_C11 0.2598977251233012689
+#define T16Q_C12 8.3944945060272534018
+#define T16Q_C13 -19.297513921073804518
+#define T16Q_C14 -0.43849131113914585078
+#define T16Q_C15 0.99999999999999703594
+#define T16Q_C16 1.0000000000000000038

@@ -317,7 +317,13 @@ int grape_reset_timings(grape_handle *h);
  * [20] the cells (counted per trajectory) of the last evaluation that qualified for the shortest economized derivative series
  * (degree 15, spectral radius <= 1.11): verdict 0, no planned squarings, and certified by the plan from tr H^4, tr H^8 and
  * tr H^12 (tables of grape_create: Hermitian generators, 1 <= L <= 2, assembly route; GRAPE_DERIV_SEG=0: no tables).  A batch of
- * 16 cells still runs the largest degree of its cells (grape_get_work[4] says what ran).  0 on handles without these tables
+ * 16 cells still runs the largest degree of its cells (grape_get_work[4] says what ran).  0 on handles without these tables,
+ * [21] the cells of the last evaluation whose second product ran as a Hermitian square (csrc/asm/gen_t16q.py, coefficient set
+ * T16Q_* with c2 = 0: 625 instead of 697 matrix instructions per wave): cells with no planned squarings that the plan certified
+ * both for the range of the four products (the inequality of [19] at s = 0) and for the segment 1.11 (the three moments of
+ * [20]); Hermitian generators, shared controls, 1 <= L <= 2, assembly route.  GRAPE_EXPM_T16Q=0: never, 1: every such handle,
+ * unset: handles whose launch gives every workgroup a walk of at least 8 cells.  Independent of GRAPE_EXPM_CERT,
+ * GRAPE_DERIV_SEG and GRAPE_DERIV_ECON.  0 on other handles and when the plan skipped the route
  * (entries beyond n are not written). */
 int grape_get_work(grape_handle *h, double *out, int n);
 
