@@ -74,7 +74,7 @@ def build_asm(verbose: bool = False, workdir: str | None = None) -> str:
     intermediates are written to ``workdir`` (default: csrc/asm, the layout tools/ expect); returns the object's path."""
     asm_dir = os.path.join(_CSRC, "asm")
     work = workdir or asm_dir
-    kernels = (("gen_t16.py", "expm_t16_asm"), ("gen_t16q.py", "expm_t16q_asm"), ("gen_t16p.py", "expm_t16p_asm"), ("gen_t16p.py", "expm_t16p4_asm"), ("gen_t18g.py", "expm_t18g_asm"), ("gen_t18gp.py", "expm_t18gp_asm"), ("gen_d3.py", "deriv3_asm"), ("gen_d3s.py", "deriv3s_asm"), ("gen_d3s.py", "deriv3g_asm"),
+    kernels = (("gen_t16.py", "expm_t16_asm"), ("gen_t16q.py", "expm_t16q_asm"), ("gen_t16r.py", "expm_t16r_asm"), ("gen_t16p.py", "expm_t16p_asm"), ("gen_t16p.py", "expm_t16p4_asm"), ("gen_t18g.py", "expm_t18g_asm"), ("gen_t18gp.py", "expm_t18gp_asm"), ("gen_d3.py", "deriv3_asm"), ("gen_d3s.py", "deriv3s_asm"), ("gen_d3s.py", "deriv3g_asm"),
                ("gen_lg.py", "lg_gemm_asm"), ("gen_d4.py", "deriv4_asm_128"), ("gen_d4.py", "deriv4_asm_256"))
     co_path, emb_s, emb_o = os.path.join(work, "grape_asm.co"), os.path.join(work, "asm_embed.S"), os.path.join(work, "asm_embed.o")
     llvm = "/opt/rocm/lib/llvm/bin"
@@ -106,7 +106,7 @@ def build_asm(verbose: bool = False, workdir: str | None = None) -> str:
 def _sources():
     srcs = [os.path.join(_CSRC, f) for f in ("grape_hip.hip", "grape_t18.hip", "grape_kernels.hip.h", "grape_large.hip.h",
                                              "grape_series.hip.h", "grape_cheby.hip.h", "grape_t18.hip.h", "grape_t18_coeffs.h",
-                                             "grape_deriv3.hip.h", "grape_timegrad.hip.h", "grape_batch.hip.h", "grape_lindblad.hip.h", "grape_lindblad_tg.hip.h", "grape_hvp.hip.h", "grape_hvp_split.hip.h", "grape_lindblad_hvp.hip.h", "grape_lindblad_hvp_split.hip.h", "grape_lindblad_batch.hip.h", "grape_lindblad_rc.hip.h", "grape_devmem.h", "grape_cert.hip.h", "grape_expect.hip.h", "grape_econ_coeffs.h", os.path.join("asm", "gen_t16.py"), os.path.join("asm", "gen_t16q.py"), os.path.join("asm", "gen_t16p.py"), os.path.join("asm", "gen_t18g.py"), os.path.join("asm", "gen_t18gp.py"), os.path.join("asm", "gen_d3.py"), os.path.join("asm", "gen_d3s.py"), os.path.join("asm", "gen_lg.py"), os.path.join("asm", "gen_d4.py"), os.path.join("asm", "gcn.py"))]
+                                             "grape_deriv3.hip.h", "grape_timegrad.hip.h", "grape_batch.hip.h", "grape_lindblad.hip.h", "grape_lindblad_tg.hip.h", "grape_hvp.hip.h", "grape_hvp_split.hip.h", "grape_lindblad_hvp.hip.h", "grape_lindblad_hvp_split.hip.h", "grape_lindblad_batch.hip.h", "grape_lindblad_rc.hip.h", "grape_devmem.h", "grape_cert.hip.h", "grape_expect.hip.h", "grape_econ_coeffs.h", os.path.join("asm", "gen_t16.py"), os.path.join("asm", "gen_t16q.py"), os.path.join("asm", "gen_t16r.py"), os.path.join("asm", "gen_t16p.py"), os.path.join("asm", "gen_t18g.py"), os.path.join("asm", "gen_t18gp.py"), os.path.join("asm", "gen_d3.py"), os.path.join("asm", "gen_d3s.py"), os.path.join("asm", "gen_lg.py"), os.path.join("asm", "gen_d4.py"), os.path.join("asm", "gcn.py"))]
     return srcs, os.path.join(_HERE, "..", "include", "grape_hip.h")
 
 
@@ -600,13 +600,14 @@ class GrapeHip:
         self._chk(self._lib.grape_reset_timings(self._h))
 
     def work(self):
-        w = np.zeros(22)
-        self._lib.grape_get_work(self._h, w.ctypes.data, 22)
+        w = np.zeros(23)
+        self._lib.grape_get_work(self._h, w.ctypes.data, 23)
         return dict(cells=w[0], squarings=w[1], flop_expm=w[2], flop_deriv=w[3], deriv_orders=w[4],
                     pivoted_cells=w[5], expm_cells=w[6], series_terms=w[7], series_steps=w[8],
                     t18_mfma_flop=w[9], t18_squarings=w[10], t18_cells=w[11], matrix_free_fallback=w[12], t16_cells=w[13],
                     asm_kernel=w[14], asm_deriv_kernel=w[15], asm_blocked_products=w[16],
-                    walk_steps=w[17], scan_block=w[18], t16_certified=w[19], seg_certified=w[20], t16q_cells=w[21])
+                    walk_steps=w[17], scan_block=w[18], t16_certified=w[19], seg_certified=w[20], t16q_cells=w[21],
+                    t16r_kernel=w[22])
 
     def cert_table(self):
         """trace tables of the generator classes (grape_get_cert_table): (t8 [KC][n8], t6 [KC][n6], exponents [n8 + n6][L]);

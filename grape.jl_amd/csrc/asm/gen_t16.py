@@ -442,6 +442,7 @@ class Gen:
         self.vp.free(t)
 
     # ---- the operator tiles of the next cell (hooks of the variant with control operators per trajectory, gen_t16p.py) ----
+    lead_ride = False       # True: see product()
     early_free = False      # True: A and the parked A2 are released behind the first k-block of the last product (pf_late)
 
     def pf_alloc(self):
@@ -603,7 +604,7 @@ class Gen:
             self.vp.free(t)
 
     # ---- strips ----
-    def product(self, Q, B, half_last=False, init=None, hook=None, bload=None, fused=None):
+    def product(self, Q, B, half_last=False, init=None, hook=None, bload=None, fused=None, tail=None):
         """Q[so] = (p1, p2, p3) += X B over the rotated k order; X in the planes, B = (re, im, sm) tile lists by slot.
         init: set of (so, j) accumulators that hold a start value (the others start from the literal 0).
         bload(pl, sk, r): the right operand of k-step (sk, r) comes from the planes too (A2 = A A) and is requested with the
@@ -615,7 +616,11 @@ class Gen:
         slot: valu(0), stores of row tile 0, valu(1), then the twelve matrix instructions of output slot 0 with the stores
         of row tile 1 and the fragment requests of slot 1 in their shadow, valu(2), slot 1 with the stores of row tile 2,
         ...  Only the first row tile's stores are exposed.  The barrier that makes the other waves' columns visible
-        stands behind k-block 0: the skew of the waves hides under its 48 matrix instructions."""
+        stands behind k-block 0: the skew of the waves hides under its 48 matrix instructions.
+        tail = {mid(), split(), split_at} (Hermitian squares only; gen_t16r.py): the last k-block runs slot 1 first, then
+        mid(), then slot 0's twelve matrix instructions with split() in front of number split_at.  Both emit what must stand
+        in the open and return thunks (LDS instructions) that ride behind the matrix instructions that follow.
+        fused["ride0"] = [(j, thunk)]: more LDS instructions behind matrix instruction j of slot 0 of k-block 0."""
         p = self.p
         NS = len(Q)
         started = set(init or ())
@@ -666,6 +671,9 @@ class Gen:
                     for r in range(4 if so + 1 < NS else 0):
                         for pl in range(3):
                             gaps[max(last[pl], 3 * r + pl)].append(lambda pl=pl, r=r: rdk(pl, so + 1, r))
+                if so == 0 and fused.get("ride0"):       # [(j, thunk)]: more LDS instructions for the shadows of slot 0 (gen_t16r.py)
+                    for j, f in fused["ride0"]:
+                        gaps[j].append(f)
                 j = 0
                 for r in range(4):
                     for pl in range(3):
@@ -677,12 +685,26 @@ class Gen:
                 fused["post"]()
             p.s_barrier()
             sk0 = 1
+        # (lead_ride, gen_t16r.py: only plane 0's fragments of the first k-step are requested in the open; those of the planes 1
+        # and 2 ride one by one behind the matrix instructions of the plane before)
+        pending = {}
         for pl in range(3):
-            for so in range(nslots(sk0)):
-                rd(pl, so, sk0, 0)
+            th = [lambda pl=pl, so=so: rd(pl, so, sk0, 0) for so in range(nslots(sk0))]
             if bload:
-                bload(pl, sk0, 0)
-        for sk in range(sk0, 4):
+                th.append(lambda pl=pl: bload(pl, sk0, 0))
+            if self.lead_ride and pl > 0:
+                pending[pl] = th
+            else:
+                for f in th:
+                    f()
+        if tail:
+            assert NS == 3 and half_last and sk0 < 3
+
+            def rdt(pl, so, r):      # last k-block, slot by slot: the twelve fragment registers hold [plane][k-step] of ONE slot
+                p.tag = "fragment"
+                p.ds_read(64, self.aop[pl][r], self.v_AA[so][3], self.KSTEP * r * LDB + pl * PLB)
+                p.tag = ""
+        for sk in range(sk0, 3 if tail else 4):
             for r in range(4):
                 ns = nslots(sk)
                 more = not (sk == 3 and r == 3)
@@ -693,10 +715,59 @@ class Gen:
                         mma(so, pl, self.aop[pl][so], B[pl][sk].d(r))
                         if hook and pl == 0 and so == 0:
                             hook(sk, r)        # (behind the first matrix instruction of the k-step: its issue slots are free)
+                        if pending.get(pl + 1):
+                            pending[pl + 1].pop(0)()
+                    while pending.get(pl + 1):
+                        pending[pl + 1].pop(0)()
+                    if tail and nsk == 3:
+                        # (the fragment registers of the slots 2 and 3 are idle from k-block 2 on: all four k-steps of slot 1)
+                        for r3 in range(4):
+                            rdt(pl, 1, r3)
+                            if bload:
+                                bload(pl, 3, r3)
+                        continue
                     for so in range(nsn):
                         rd(pl, so, nsk, nr)
                     if bload and more:
                         bload(pl, nsk, nr)
+        if tail:
+            # the last k-block slot by slot, slot 1 first: the slots whose tiles other waves need (1 and the half slot 2) are
+            # complete twelve matrix instructions before the product is, and what tail["mid"] sends rides under slot 0's
+            # (per accumulator the k-steps keep their order: the sums are the same to the bit)
+            for r in range(4):
+                for pl in range(3):
+                    mma(1, pl, self.aop[pl][r], B[pl][3].d(r))
+                    if hook and pl == 0:
+                        hook(3, r)
+                    rdt(pl, 0, r)
+            # (mid() and split() return thunks -- their LDS instructions -- that ride one by one behind slot 0's matrix
+            # instructions: outside such a shadow an LDS instruction costs the wave ~28 cycles of issue)
+            cut = tail.get("split_at", 12) if "split" in tail else 12
+
+            def spread(thunks, first, n):
+                gaps = [[] for _ in range(12)]
+                thunks = list(thunks or [])
+                if n <= 0:
+                    for f in thunks:
+                        f()
+                    return gaps
+                per = -(-len(thunks) // n)
+                for q, f in enumerate(thunks):
+                    gaps[first + q // per].append(f)
+                return gaps
+
+            gaps = spread(tail["mid"](), 0, cut)
+            j = 0
+            for r in range(4):
+                for pl in range(3):
+                    if j == cut and "split" in tail:
+                        gaps = spread(tail["split"](), cut, 12 - cut)
+                    mma(0, pl, self.aop[pl][r], B[pl][3].d(r))
+                    for f in gaps[j]:
+                        f()
+                    j += 1
+            if "split" in tail and cut == 12:
+                spread(tail["split"](), 12, 0)
 
     def plane_stores(self, sl, xr, xi, xs):
         """the six 16-byte stores of row tile (w + sl) & 3 of this wave's column strip (xr, xi, xs: tiles), as thunks"""
@@ -770,6 +841,44 @@ class Gen:
     def load_c16(self, k16):
         self.smov64(k16, self.c["C16"])
 
+    # ---- A2 = A A with its exchange (hook of the variant that sends the tiles before the product is complete, gen_t16r.py) ----
+    def a2_streams(self, Qt, A2re, A2im, slots):
+        p = self.p
+        streams = []
+        for sl in slots:
+            for r in range(4):
+                p1, p2, p3 = (Qt[sl][j].d(r) for j in range(3))
+                re_, im_ = A2re[sl].d(r), A2im[sl].d(r)
+                streams.append([lambda re_=re_, p1=p1, p2=p2: p.valu("v_add_f64", re_, p1, Neg(p2)),
+                                lambda im_=im_, p3=p3, p1=p1: p.valu("v_add_f64", im_, p3, Neg(p1)),
+                                lambda im_=im_, p2=p2: p.valu("v_add_f64", im_, im_, Neg(p2))])
+        for g in range(0, len(streams), 4):
+            self.interleave(streams[g:g + 4])
+
+    def exchange_writes(self, re1, im1, re2, im2):
+        """half sum of slot 2 -> wave w + 2, slot-1 tile -> wave w + 1 (its mirrored slot 3); plain values, the reader
+        conjugates"""
+        p = self.p
+        for r in range(4):
+            p.ds_write(64, self.v_EW2, re2.d(r), 128 * r)
+            p.ds_write(64, self.v_EW2, im2.d(r), EXH + 128 * r)
+            p.ds_write(64, self.v_EW1, re1.d(r), 128 * r)
+            p.ds_write(64, self.v_EW1, im1.d(r), EXH + 128 * r)
+
+    def first_square(self, Qt, B_As, hook_store, bload_A, Uprev):
+        p, vp, ap = self.p, self.vp, self.ap
+        self.product(Qt[:3], B_As, half_last=True, hook=hook_store, bload=bload_A)
+        ap.free(self.As_sm)
+        vp.free(Uprev)
+        self.stamp(1)
+        # ---- A2: slots 0..2 from the partial products; A2 lives in the vector half (right operand of the second product) ----
+        A2re, A2im, A2sm = [vp.alloc() for _ in range(4)], [vp.alloc() for _ in range(4)], [vp.alloc() for _ in range(4)]
+        self.a2_streams(Qt, A2re, A2im, range(3))
+        self.exchange_writes(A2re[1], A2im[1], A2re[2], A2im[2])
+        p.s_waitcnt(lgkm=0)
+        p.s_barrier()                                   # (also: everybody is done reading A)
+        return A2re, A2im, A2sm
+
     # -----------------------------------------------------------------------------------------------------------------
     def cell(self):
         p, c = self.p, self.s_c
@@ -803,10 +912,7 @@ class Gen:
                 p.tag = ""
 
         B_As = [[S_.sub(8 * sl, 8) for sl in range(4)] for S_ in As]
-        self.product(Qt[:3], B_As, half_last=True, hook=hook_store, bload=bload_A)
-        ap.free(self.As_sm)
-        vp.free(Uprev)
-        self.stamp(1)
+        A2re, A2im, A2sm = self.first_square(Qt, B_As, hook_store, bload_A, Uprev)
         As_re, As_im = self.As_re, self.As_im
 
         def A_(sl, r):          # A in the accumulation half
@@ -824,27 +930,6 @@ class Gen:
             for g in range(0, len(streams), 4):
                 self.interleave(streams[g:g + 4])
 
-        # ---- A2: slots 0..2 from the partial products; A2 lives in the vector half (right operand of the second product) ----
-        A2re, A2im, A2sm = [vp.alloc() for _ in range(4)], [vp.alloc() for _ in range(4)], [vp.alloc() for _ in range(4)]
-        streams = []
-        for sl in range(3):
-            for r in range(4):
-                p1, p2, p3 = (Qt[sl][j].d(r) for j in range(3))
-                re_, im_ = A2re[sl].d(r), A2im[sl].d(r)
-                streams.append([lambda re_=re_, p1=p1, p2=p2: p.valu("v_add_f64", re_, p1, Neg(p2)),
-                                lambda im_=im_, p3=p3, p1=p1: p.valu("v_add_f64", im_, p3, Neg(p1)),
-                                lambda im_=im_, p2=p2: p.valu("v_add_f64", im_, im_, Neg(p2))])
-        for g in range(0, len(streams), 4):
-            self.interleave(streams[g:g + 4])
-        # exchange: half sum of slot 2 -> wave w + 2, slot-1 tile -> wave w + 1 (its mirrored slot 3); plain values, the
-        # reader conjugates
-        for r in range(4):
-            p.ds_write(64, self.v_EW2, A2re[2].d(r), 128 * r)
-            p.ds_write(64, self.v_EW2, A2im[2].d(r), EXH + 128 * r)
-            p.ds_write(64, self.v_EW1, A2re[1].d(r), 128 * r)
-            p.ds_write(64, self.v_EW1, A2im[1].d(r), EXH + 128 * r)
-        p.s_waitcnt(lgkm=0)
-        p.s_barrier()                                   # (also: everybody is done reading A)
         cx = SimpleNamespace(Qt=Qt, A2re=A2re, A2im=A2im, A2sm=A2sm)
         self.second_product_fork(cx)
         # scalars of the NEXT cell (its operator bases, dt): requested here, needed by the last product

@@ -78,6 +78,12 @@ class GenQ(g16.Gen):
         p.salu("s_and_b32", self.s_tmp[0], self.s_scur, Q_BIT)
         p.s_branch("s_cbranch_scc1", cx.L_q)
 
+    def bound_stand_in(self, A2re):
+        # (the matrix instruction the counter books for the bound of the other path: operands whatever, result dropped)
+        drop = self.vp.alloc()
+        self.p.mfma(drop, A2re[0].d(0), A2re[0].d(0), 0)
+        self.vp.free(drop)
+
     def second_product_square(self, cx, L_join):
         p, vp = self.p, self.vp
         Qt, A2re, A2im, A2sm = cx.Qt, cx.A2re, cx.A2im, cx.A2sm
@@ -148,10 +154,7 @@ class GenQ(g16.Gen):
             p.ds_read(128, txi.sub(4 * h, 4), self.v_ER, EXH + 16 * h)
             p.ds_read(128, Qt[3][0].sub(4 * h, 4), self.v_ER, (E2 - E1) + 16 * h)
             p.ds_read(128, Qt[3][2].sub(4 * h, 4), self.v_ER, (E2 - E1) + EXH + 16 * h)
-        # (the matrix instruction the counter books for the bound of the other path: operands whatever, result dropped)
-        drop = vp.alloc()
-        p.mfma(drop, A2re[0].d(0), A2re[0].d(0), 0)
-        vp.free(drop)
+        self.bound_stand_in(A2re)
         for r in range(4):
             p.valu("v_add_f64", Qt[2][0].d(r), Qt[2][0].d(r), txr.d(r))
             p.valu("v_add_f64", Qt[2][2].d(r), Qt[2][2].d(r), Neg(txi.d(r)))

@@ -168,6 +168,11 @@ struct grape_handle {
     // GRAPE_EXPM_T16Q=0 off, 1 on for every eligible handle, unset: on when every workgroup walks at least
     // T16Q_MIN_WALK cells.  Independent of GRAPE_EXPM_CERT, GRAPE_DERIV_SEG and GRAPE_DERIV_ECON.
     bool asm16q = false;
+    // ... and its launch is expm_t16r_asm (asm/gen_t16r.py): the same arithmetic to the bit, the tile exchanges of the two Hermitian
+    // squares sent under the last matrix instructions of the square, 624 matrix instructions per marked cell and wave.
+    // GRAPE_EXPM_T16R=0 off, 1 on wherever asm16q is, unset: on when asm16q is on by its own rule and not by GRAPE_EXPM_T16Q=1
+    // (the handles the suite forces onto expm_t16q_asm keep that kernel and its count)
+    bool asm16r = false;
     bool t16q_twin = false;      // ... the same route with GRAPE_EXPM_ASM=0: expm_t18_kernel<4, true, true, T16> reads bit 9 of the plan words and
                                  // takes the same path (624 matrix instructions per wave), under the same switch and the same rule
     // the four-product route as hand-allocated assembly (asm/gen_t16.py; GRAPE_EXPM_ASM=0: the C++ kernel): four tiles
@@ -3221,6 +3226,8 @@ int grape_create(grape_handle **out, const grape_problem *p) try {
             const char *envt = getenv("GRAPE_EXPM_T16Q");
             const bool eligible = h->asm16 && !h->asm16p && !p->hc_per_traj && L >= 1 && L <= 2;
             h->asm16q = eligible && (envt ? atoi(envt) != 0 : ncell >= (long)T16Q_MIN_WALK * h->asm_blocks);
+            const char *envr = getenv("GRAPE_EXPM_T16R");
+            h->asm16r = h->asm16q && (envr ? atoi(envr) != 0 : !envt);
         }
         std::vector<int> tab((size_t)4 * h->asm_blocks);
         grape_t16_walks(h->KC, N_T, h->asm_blocks, tab.data());
@@ -3598,7 +3605,7 @@ int grape_forward_device(grape_handle *h, const double *d_pulsevals, double *d_o
                     walk_fuse = h->asm_walk & (1 | ((h->fuse && h->fuse_on && h->want_bw) ? 2 : 0));
                     if (walk_fuse) HIPCHK(h, stream_fill(h->d_prog, 0, (size_t)2 * h->K * sizeof(int), s));
                     const void *walk[6] = {h->d_wgtab, h->d_xinit, h->d_fw, h->d_bw, h->d_prog, h->d_splan};
-                    e = (hipError_t)grape_t16_asm_launch(&ea, sizeof(ea), h->d_cellflag, (void *)s, h->asm_blocks, walk, walk_fuse, h->K, h->asm16q ? 1 : 0);
+                    e = (hipError_t)grape_t16_asm_launch(&ea, sizeof(ea), h->d_cellflag, (void *)s, h->asm_blocks, walk, walk_fuse, h->K, h->asm16r ? 2 : h->asm16q ? 1 : 0);
                     h->credit_pending = true;
                 }
                 else {
@@ -4742,13 +4749,13 @@ int grape_get_work(grape_handle *h, double *out, int n) try {
     if (!h || !out || n < 4) return GRAPE_ERR_INVALID;
     if (h->open) return open_work(h, out, n);
     if (!h->shards.empty()) {   // every entry is a count: the shards add up
-        const int m = n < 22 ? n : 22;
+        const int m = n < 23 ? n : 23;
         std::fill(out, out + m, 0.0);
         for (grape_handle *c : h->shards) {
-            double cw[22] = {0.};
+            double cw[23] = {0.};
             const int rc = grape_get_work(c, cw, m);
             if (rc < 0) return multi_fail(h, c, rc);
-            for (int i = 0; i < m; ++i) out[i] = (i == 15 || i == 16 || i == 18) ? cw[i] : out[i] + cw[i];   // ([15], [16]: kernel ids, the same in every shard)
+            for (int i = 0; i < m; ++i) out[i] = (i == 15 || i == 16 || i == 18 || i == 22) ? cw[i] : out[i] + cw[i];   // ([15], [16]: kernel ids, the same in every shard)
         }
         if (m > 14 && out[14] > 0.0) out[14] = h->shards[0]->asm16p ? 3.0 : h->shards[0]->asm18gp ? 4.0 : h->shards[0]->asm18g ? 2.0 : 1.0;   // (an id, not a count)
         return 4;
@@ -4856,6 +4863,8 @@ int grape_get_work(grape_handle *h, double *out, int n) try {
         if (n > 20) out[20] = seg;
         // cells of the last evaluation whose second product ran as a Hermitian square (expm_t16q_asm; bits of the same plan words)
         if (n > 21) out[21] = qcells;
+        // ... and 1 when the kernel that ran them was expm_t16r_asm (an id, like [14])
+        if (n > 22) out[22] = (h->asm16r && qcells > 0.0) ? 1.0 : 0.0;
     }
     return 4;
 }

@@ -152,7 +152,7 @@ __device__ __forceinline__ double t16_post_norm1(const ExpmArgs &a, const int ce
 }
 
 // behind the assembly kernel, every evaluation: the cells beyond the bound go to the hand-over list; executed work
-__global__ void __launch_bounds__(256) t16_post_kernel(ExpmArgs a, const int *verdict, const int *prog, int nprog, const int *splan) {
+__global__ void __launch_bounds__(256) t16_post_kernel(ExpmArgs a, const int *verdict, const int *prog, int nprog, const int *splan, int q_stand_in) {
     const int tid = threadIdx.x, lane = tid & 63, ncell = a.K * a.N_T;
     if (t16_skipped(a.flags, ncell)) return;   // the route was not tried: the five-product launch books all cells
     if (prog && blockIdx.x == 0) {   // two matrix instructions per wave for every step a walk carried its state over (round 5)
@@ -173,13 +173,14 @@ __global__ void __launch_bounds__(256) t16_post_kernel(ExpmArgs a, const int *ve
         if (lane == 0 && sq) stat_add(a.stats, 12, sq * 4ull * 192ull);
         if (lane == 0 && sq_ok) stat_add(a.stats, 13, sq_ok);   // squarings of cells this route finished
     }
-    // (cells whose second product was the Hermitian square, gen_t16q.py: 120 instead of 192 there)
+    // (cells whose second product was the Hermitian square, gen_t16q.py: 120 instead of 192 there; q_stand_in: the marked path
+    // issues the one instruction of the other path's bound all the same -- expm_t16q_asm does, expm_t16r_asm does not)
     const unsigned long long m_q = __ballot(valid && (splan[cell] & T16_PLAN_Q));
     if (lane == 0 && m_valid) {
         // executed matrix instructions of the assembly kernel: four waves x (120 + 3 * 192 + 1 for the column sums) per cell
         // (a cell certified before the launch still issues that one instruction: gen_t16.py, "certified")
         stat_add(a.stats, 12, (unsigned long long)__popcll(m_valid) * 4ull * (unsigned long long)(T16Count<4>::CELL + 1)
-                                  - (unsigned long long)__popcll(m_q) * 4ull * (unsigned long long)(T18Count<4>::GP - T18Count<4>::SQH));
+                                  - (unsigned long long)__popcll(m_q) * 4ull * (unsigned long long)(T18Count<4>::GP - T18Count<4>::SQH + (q_stand_in ? 0 : 1)));
         if (m_ok) {
             stat_add(a.stats, 14, (unsigned long long)__popcll(m_ok));
             stat_add(a.stats, 15, (unsigned long long)__popcll(m_ok));
@@ -241,13 +242,14 @@ constexpr int D3_PAIRS_OFF = 32768, D3_ECON_OFF = 32768, D3_ECON_TAB_B = 512;   
 struct AsmModule {
     hipModule_t mod = nullptr;
     hipFunction_t fn = nullptr, fn_d3 = nullptr, fn_d3s = nullptr, fn_lg = nullptr, fn_d3g = nullptr, fn_d4[2] = {nullptr, nullptr};
-    hipFunction_t fn_t18g = nullptr, fn_t16p = nullptr, fn_t16p4 = nullptr, fn_t18gp = nullptr, fn_t16q = nullptr;
+    hipFunction_t fn_t18g = nullptr, fn_t16p = nullptr, fn_t16p4 = nullptr, fn_t18gp = nullptr, fn_t16q = nullptr, fn_t16r = nullptr;
     double *inv = nullptr;      // 1 / m, m < D3_INV_TABLE
 };
 hipError_t asm_function(int dev, hipFunction_t *fn, hipFunction_t *fn_d3 = nullptr, const double **inv = nullptr,
                         hipFunction_t *fn_d3s = nullptr, hipFunction_t *fn_lg = nullptr, hipFunction_t *fn_d3g = nullptr,
                         hipFunction_t *fn_d4 = nullptr, int d4_index = 0, hipFunction_t *fn_t18g = nullptr,
-                        hipFunction_t *fn_t16p = nullptr, int t16p_slots = 2, hipFunction_t *fn_t16q = nullptr) {
+                        hipFunction_t *fn_t16p = nullptr, int t16p_slots = 2, hipFunction_t *fn_t16q = nullptr,
+                        hipFunction_t *fn_t16r = nullptr) {
     static AsmModule mods[64];
     static std::mutex mtx;
     std::lock_guard<std::mutex> lock(mtx);
@@ -297,6 +299,8 @@ hipError_t asm_function(int dev, hipFunction_t *fn, hipFunction_t *fn_d3 = nullp
         if (e != hipSuccess) return e;
         e = hipModuleGetFunction(&m.fn_t16q, m.mod, "expm_t16q_asm");
         if (e != hipSuccess) return e;
+        e = hipModuleGetFunction(&m.fn_t16r, m.mod, "expm_t16r_asm");
+        if (e != hipSuccess) return e;
         // 1 / m for the series orders (the kernels read them with scalar loads; gfx9 has no scalar floating point); behind
         // them the piece table of the streamed kernel (gen_d3s.py piece_table: source offset of piece 4 tile + 2 plane + half)
         // round 6: at D3_PAIRS_OFF bytes the scalars (omega_a, sigma_a) of pass 2, a < D3_INV_TABLE, of the Taylor series (both
@@ -332,6 +336,7 @@ hipError_t asm_function(int dev, hipFunction_t *fn, hipFunction_t *fn_d3 = nullp
     if (fn_t18g) *fn_t18g = m.fn_t18g;
     if (fn_t16p) *fn_t16p = t16p_slots == 4 ? m.fn_t16p4 : t16p_slots == 0 ? m.fn_t18gp : m.fn_t16p;   // (0: the general-matrix variant)
     if (fn_t16q) *fn_t16q = m.fn_t16q;
+    if (fn_t16r) *fn_t16r = m.fn_t16r;
     if (inv) *inv = m.inv;
     return hipSuccess;
 }
@@ -479,7 +484,8 @@ extern "C" void grape_t16_walks(int KC, int N_T, int nblk, int *tab) {
 
 // args: ExpmArgs with Sf set (summed controls of every time step) and cell_list / flags / stats as for the C++ kernel;
 // walk: {wgtab, xinit, fw, bw, prog, splan} device pointers, fuse / K as in T16AsmArgs
-// q != 0: expm_t16q_asm (same argument block; the plan of this evaluation marked its cells with bit 9 of the plan words)
+// q != 0: expm_t16q_asm (same argument block; the plan of this evaluation marked its cells with bit 9 of the plan words);
+// q == 2: expm_t16r_asm, the same cells with the exchanges of the Hermitian squares sent early (asm/gen_t16r.py)
 extern "C" int grape_t16_asm_launch(const void *args, size_t args_size, int *verdict, void *stream, int blocks,
                                     const void *const *walk, int fuse, int K, int q) {
     if (args_size != sizeof(ExpmArgs)) return (int)hipErrorInvalidValue;
@@ -492,10 +498,10 @@ extern "C" int grape_t16_asm_launch(const void *args, size_t args_size, int *ver
     int dev = 0;
     hipError_t e = hipGetDevice(&dev);
     if (e != hipSuccess) return (int)e;
-    hipFunction_t fn, fn_q;
-    e = asm_function(dev, &fn, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, 2, &fn_q);
+    hipFunction_t fn, fn_q, fn_r;
+    e = asm_function(dev, &fn, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, 2, &fn_q, &fn_r);
     if (e != hipSuccess) return (int)e;
-    if (q) fn = fn_q;
+    if (q) fn = q == 2 ? fn_r : fn_q;
     T16AsmArgs k{};
     k.H0f = a.H0f; k.Sf = a.Sf; k.dts = a.dts; k.U = a.U; k.verdict = verdict; k.rep = a.rep;
     k.KC = a.K; k.N_T = a.N_T; k.nblk = blocks; k.flags = a.flags;
@@ -508,7 +514,7 @@ extern "C" int grape_t16_asm_launch(const void *args, size_t args_size, int *ver
     e = hipModuleLaunchKernel(fn, (unsigned)blocks, 1, 1, 256, 1, 1, 0, s, nullptr, cfg);
     if (e != hipSuccess) return (int)e;
     hipLaunchKernelGGL(t16_post_kernel, dim3((unsigned)((ncell + 255) / 256)), dim3(256), 0, s, a, (const int *)verdict,
-                       fuse ? (const int *)walk[4] : (const int *)nullptr, 2 * K, (const int *)walk[5]);
+                       fuse ? (const int *)walk[4] : (const int *)nullptr, 2 * K, (const int *)walk[5], q == 2 ? 0 : 1);
     return (int)hipGetLastError();
 }
 
@@ -543,7 +549,7 @@ extern "C" int grape_t16p_asm_launch(const void *args, size_t args_size, int *ve
     e = hipModuleLaunchKernel(fn, (unsigned)blocks, 1, 1, 256, 1, 1, 0, s, nullptr, cfg);
     if (e != hipSuccess) return (int)e;
     hipLaunchKernelGGL(t16_post_kernel, dim3((unsigned)((ncell + 255) / 256)), dim3(256), 0, s, a, (const int *)verdict,
-                       fuse ? (const int *)walk[4] : (const int *)nullptr, 2 * K, (const int *)walk[5]);
+                       fuse ? (const int *)walk[4] : (const int *)nullptr, 2 * K, (const int *)walk[5], 1);
     return (int)hipGetLastError();
 }
 

@@ -323,7 +323,12 @@ int grape_reset_timings(grape_handle *h);
  * both for the range of the four products (the inequality of [19] at s = 0) and for the segment 1.11 (the three moments of
  * [20]); Hermitian generators, shared controls, 1 <= L <= 2, assembly route.  GRAPE_EXPM_T16Q=0: never, 1: every such handle,
  * unset: handles whose launch gives every workgroup a walk of at least 8 cells.  Independent of GRAPE_EXPM_CERT,
- * GRAPE_DERIV_SEG and GRAPE_DERIV_ECON.  0 on other handles and when the plan skipped the route
+ * GRAPE_DERIV_SEG and GRAPE_DERIV_ECON.  0 on other handles and when the plan skipped the route,
+ * [22] 1 when the kernel that ran the cells of [21] was expm_t16r_asm (csrc/asm/gen_t16r.py): the arithmetic of expm_t16q_asm
+ * operation for operation -- the same bits -- with the tile exchanges of the two Hermitian squares sent under the last matrix
+ * instructions of the square, and 624 matrix instructions per marked cell and wave ([9] books them).  GRAPE_EXPM_T16R=0: never,
+ * 1: wherever [21] counts cells of the assembly route, unset: where that route is on by its own rule and not by
+ * GRAPE_EXPM_T16Q=1.  [14] stays 1
  * (entries beyond n are not written). */
 int grape_get_work(grape_handle *h, double *out, int n);
 
