@@ -18,6 +18,7 @@
 #include "grape_lindblad_tg.hip.h"
 #include "grape_hvp.hip.h"
 #include "grape_hvp_split.hip.h"
+#include "grape_hessian.hip.h"
 #include "grape_lindblad_hvp.hip.h"
 #include "grape_lindblad_hvp_split.hip.h"
 #include "grape_lindblad_batch.hip.h"
@@ -354,6 +355,16 @@ struct grape_handle {
         unsigned long long *d_hvstats = nullptr;   // [4 cap K] statistics of the workgroups, then the flag word
         double info[7] = {0., 0., 0., 0., 0., 0., 0.};   // grape_get_hvp_info
     } hvp;
+    // grape_hessian (grape_hessian.hip.h): the Hessian as a matrix.  Storage of its own -- the seeds, the
+    // overlaps, the accumulator and the result, and per trajectory of a pass a strip and the step matrices of its fan --
+    // allocated by the first call and freed by grape_destroy; nothing an evaluation, a getter or grape_hvp uses is touched.
+    struct HessStore {
+        GroupStore store;          // units: trajectories per pass; env: GRAPE_HESS_TRAJ at grape_create
+        double2 *d_a = nullptr, *d_b = nullptr, *d_T = nullptr, *d_Sd = nullptr;
+        double *d_strip = nullptr, *d_acc = nullptr, *d_H = nullptr, *d_wsf = nullptr, *d_wsfan = nullptr;
+        unsigned long long *d_stats = nullptr;   // statistics of the workgroups of a launch, then the flag word
+        double info[8] = {0., 0., 0., 0., 0., 0., 0., 0.};   // grape_get_hessian_info
+    } hess;
     // grape_hvp_forward / grape_hvp_backward / grape_hvp_backward_chi (grape_hvp_split.hip.h): the two halves
     // share the tangent storage above; what only they need lives here, allocated by the first split call, so that a handle
     // which never makes one holds -- and reports -- what it held before.
@@ -2452,7 +2463,7 @@ void grape_destroy(grape_handle *h) {
     }
     hipSetDevice(h->device);
     if (h->stream) hipStreamSynchronize(h->stream);
-    h->batch.store.release(); h->hvp.store.release(); h->hvs.mem.release(); h->ex.mem.release(); h->mem.release();
+    h->batch.store.release(); h->hvp.store.release(); h->hess.store.release(); h->hvs.mem.release(); h->ex.mem.release(); h->mem.release();
     for (auto &ring : h->ph)
         for (auto &p : ring) {
             if (p.e0) hipEventDestroy(p.e0);
@@ -3481,6 +3492,7 @@ int grape_create(grape_handle **out, const grape_problem *p) try {
         if (const char *envb = getenv("GRAPE_BATCH")) h->batch_env = atoi(envb) != 0 ? 1 : 0;
         if (const char *envs = getenv("GRAPE_BATCH_SETS")) h->batch.store.env = std::max(0, atoi(envs));
         if (const char *envh = getenv("GRAPE_HVP_DIRS")) h->hvp.store.env = std::max(0, atoi(envh));
+        if (const char *envt = getenv("GRAPE_HESS_TRAJ")) h->hess.store.env = std::max(0, atoi(envt));
     }
     CCHK(h->mem.alloc_pinned(&h->h_pin, h->h_pin_doubles));
     // Everything above went through the NULL stream (hipMemset of device memory returns before the fill has run; a copy from
@@ -5455,6 +5467,184 @@ GRAPE_BARRIER(h ? &h->err : &g_create_error)
 int grape_get_hvp_info(grape_handle *h, double *out, int n) try {
     if (!h || !out) return GRAPE_ERR_INVALID;
     return copy_info(h->hvp.info, 7, out, n);
+}
+GRAPE_BARRIER(h ? &h->err : &g_create_error)
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------
+// grape_hessian: the exact Hessian of J as a matrix on the stored forward states (grape_hessian.hip.h)
+// ---------------------------------------------------------------------------------------
+namespace {
+
+// workgroups of the forward seeds along the intervals: about four workgroups per compute unit over all trajectories
+int hess_seed_rows(const grape_handle *h) { return std::max(1, std::min(h->N_T, (1024 + h->K - 1) / h->K)); }
+
+// bytes every call holds whatever the pass size | bytes per trajectory of a pass (strip, step matrices and statistics of its fan)
+size_t hess_bytes_fixed(const grape_handle *h) {
+    const size_t K = (size_t)h->K, N_T = (size_t)h->N_T, L = (size_t)h->L, P = L * N_T, pp = (size_t)h->NP * h->NP;
+    const size_t seeds = K * (size_t)hess_seed_rows(h);
+    return 2 * K * N_T * L * h->NP * 16 + K * P * 16 + K * N_T * HESS_PAIRS * 16 + 2 * P * P * 8 + seeds * 4 * pp * 8 + (2 * seeds + 1) * 8;
+}
+size_t hess_bytes_per_trajectory(const grape_handle *h) {
+    const size_t P = (size_t)h->L * h->N_T, pp = (size_t)h->NP * h->NP, nblk = (P + 15) / 16;
+    return P * P * 8 + nblk * 4 * pp * 8 + nblk * 16;
+}
+
+// trajectories per pass and the storage for that many: the budget rule of grape_devmem.h on what the fixed part leaves of 8 GB
+int hess_reserve(grape_handle *h, int *traj) {
+    auto &v = h->hess;
+    const size_t K = (size_t)h->K, N_T = (size_t)h->N_T, L = (size_t)h->L, P = L * N_T, pp = (size_t)h->NP * h->NP, nblk = (P + 15) / 16;
+    const size_t seeds = K * (size_t)hess_seed_rows(h), fixed = hess_bytes_fixed(h), per = hess_bytes_per_trajectory(h);
+    hipError_t e = v.store.plan(h->K, per, std::max(0.0, 8.0 * 1073741824.0 - (double)fixed), traj);
+    if (e != hipSuccess) { h->err = std::string("hipMemGetInfo(&free_b, &total_b): ") + hipGetErrorString(e); return GRAPE_ERR_HIP; }
+    const GroupStore::Grow r = v.store.grow(*traj, h->stream, [&](GroupStore::Requests &get) {
+        const size_t n = (size_t)*traj;
+        get(&v.d_a, K * N_T * L * h->NP); get(&v.d_b, K * N_T * L * h->NP); get(&v.d_T, K * P); get(&v.d_Sd, K * N_T * HESS_PAIRS);
+        get(&v.d_acc, P * P); get(&v.d_H, P * P); get(&v.d_wsf, seeds * 4 * pp);
+        get(&v.d_strip, n * P * P); get(&v.d_wsfan, n * nblk * 4 * pp); get(&v.d_stats, 2 * std::max(seeds, n * nblk) + 1);
+    }, &e);
+    if (r == GroupStore::Grow::sync_failed) { h->err = std::string("hipStreamSynchronize(h->stream): ") + hipGetErrorString(e); return GRAPE_ERR_HIP; }
+    if (r == GroupStore::Grow::alloc_failed) {
+        h->err = "grape_hessian: out of device memory for the seeds, the accumulator and the result (" + std::to_string(fixed >> 20) +
+                 " MB) and the strips of " + std::to_string(*traj) + " trajectories per pass (" + std::to_string(per * (size_t)*traj >> 20) +
+                 " MB); GRAPE_HESS_TRAJ=<n> makes the passes smaller";
+        (void)hipGetLastError();
+        return GRAPE_ERR_HIP;
+    }
+    return GRAPE_OK;
+}
+
+template <int NP>
+void hess_launch_seeds(const HessArgs &a, int rows, hipStream_t s) {
+    hipLaunchKernelGGL(hess_forward_seeds_kernel<NP>, dim3((unsigned)a.s.K, (unsigned)rows), dim3(4 * NP), 0, s, a);
+}
+template <int NP>
+void hess_launch_backward(const HessArgs &a, hipStream_t s) {
+    hipLaunchKernelGGL(hess_backward_seeds_kernel<NP>, dim3((unsigned)a.s.K), dim3(4 * NP), 0, s, a);
+}
+template <int NP>
+void hess_launch_fan(const HessArgs &a, int nblk, int ntraj, hipStream_t s) {
+    hipLaunchKernelGGL(hess_fan_kernel<NP>, dim3((unsigned)nblk, (unsigned)ntraj), dim3(4 * NP), 0, s, a);
+}
+#define HESS_DISPATCH(fn, ...)                                   \
+    switch (h->NP) {                                             \
+        case 16: fn<16>(__VA_ARGS__); break;                     \
+        case 32: fn<32>(__VA_ARGS__); break;                     \
+        case 48: fn<48>(__VA_ARGS__); break;                     \
+        default: fn<64>(__VA_ARGS__); break;                     \
+    }
+
+// why this handle cannot give the Hessian (nullptr: it can); every test precedes the first HIP call
+const char *hess_refusal(const grape_handle *h) {
+    if (h->open) return "open-system handles are out of scope (DESIGN.md 25): grape_open_hvp with unit directions is the route";
+    if (!h->shards.empty() || h->p.ndev > 1) return "several devices behind one handle (ndev > 1) are out of scope";
+    if (h->N > 64) return "N > 64 is out of scope (the kernels work on at most four 16-wide tiles)";
+    if (h->L > HESS_MAX_L)
+        return "L > 4 is out of scope (the backward seeds are one 16-column tile: 1 + L + L (L + 1) / 2 columns): grape_hvp with "
+               "unit directions is the route";
+    if ((long long)h->L * h->N_T > 8192) return "L * N_T > 8192 is out of scope (the matrix and a strip per trajectory are (L * N_T)^2 doubles each)";
+    if (h->K != h->K_total) return "a split-phase shard (K < K_total) is out of scope: the boundary term couples all trajectories";
+    if (h->no_target) return "this handle has no target states (grape_problem.target == NULL): the functional would be the caller's";
+    if (h->have_gb || (h->p.Dpen && h->p.lambda_b != 0.0)) return "the built-in running cost (Dpen, lambda_b != 0) is out of scope";
+    if (h->tg_xi_user) return "the last backward half took a caller's xi (grape_backward_xi): running costs are out of scope";
+    if (h->tg_state < 1)
+        return "no valid forward state on this time grid (no evaluation yet, the last one failed, grape_set_tlist came since, "
+               "or the last call was grape_eval_batch)";
+    return nullptr;
+}
+
+// the statistics of `nwg` workgroups and the flag word of the launch before, summed on the host
+int hess_collect(grape_handle *h, size_t nwg, std::vector<unsigned long long> &st, double *terms, double *steps, bool *taylor) {
+    hipStream_t s = h->stream;
+    st.assign(2 * nwg + 1, 0ull);
+    HIPCHK(h, hipMemcpyAsync(st.data(), h->hess.d_stats, (2 * nwg + 1) * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipStreamSynchronize(s));
+    for (size_t q = 0; q < nwg; ++q) { *terms += (double)st[2 * q]; *steps += (double)st[2 * q + 1]; }
+    if ((int)(st[2 * nwg] & 0xffffffffull) & 16) *taylor = true;
+    return GRAPE_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int grape_hessian(grape_handle *h, double *H) try {
+    if (!h) { g_create_error = "grape_hessian: h == NULL"; return GRAPE_ERR_INVALID; }
+    if (!H) { h->err = "grape_hessian: H must not be NULL"; return GRAPE_ERR_INVALID; }
+    if (const char *why = hess_refusal(h)) { h->err = std::string("grape_hessian: ") + why; return GRAPE_ERR_INVALID; }
+    const auto t0 = std::chrono::steady_clock::now();
+    HIPCHK(h, hipSetDevice(h->device));
+    if (h->foreign_stream) HIPCHK(h, hipDeviceSynchronize());   // (see grape_get_time_gradient)
+    (void)hipGetLastError();
+    int ntraj = 0;
+    int rc = hess_reserve(h, &ntraj);
+    if (rc) return rc;
+    auto &v = h->hess;
+    const size_t K = (size_t)h->K, P = (size_t)h->L * h->N_T, nblk = (P + 15) / 16;
+    const int rows = hess_seed_rows(h);
+    hipStream_t s = h->stream;
+    HessArgs a{};
+    a.s.H0f = h->d_H0f; a.s.Hcf = h->d_Hcf; a.s.eps = h->d_eps; a.s.shape = h->d_shape; a.s.dts = h->d_dts; a.s.rb = h->d_rb;
+    a.s.fw = h->d_fw; a.s.target = h->d_target; a.s.weights = h->d_weights;
+    a.s.tau = (const double2 *)h->d_out; a.s.f = h->d_out + 2 * K;
+    a.s.tol = h->series_tol; a.s.theta = h->series_theta;
+    a.s.K = h->K; a.s.K_total = h->K_total; a.s.L = h->L; a.s.N = h->N; a.s.N_T = h->N_T; a.s.functional = h->p.functional;
+    a.s.hc_per_traj = h->p.hc_per_traj;
+    a.av = v.d_a; a.bv = v.d_b; a.T = v.d_T; a.Sd = v.d_Sd; a.strip = v.d_strip; a.acc = v.d_acc; a.H = v.d_H;
+    a.stats = v.d_stats;
+    std::vector<unsigned long long> st;
+    double terms_f = 0., terms_b = 0., terms_fan = 0., steps = 0.;
+    bool taylor = false;
+    // the flag word sits behind the statistics of the launch
+    auto begin = [&](size_t nwg) {
+        a.s.flags = (int *)(v.d_stats + 2 * nwg);
+        return hipMemsetAsync(v.d_stats, 0, (2 * nwg + 1) * 8, s);
+    };
+    {   // forward seeds
+        const size_t nwg = K * (size_t)rows;
+        HIPCHK(h, begin(nwg));
+        a.ws = v.d_wsf;
+        HESS_DISPATCH(hess_launch_seeds, a, rows, s)
+        HIPCHK(h, hipGetLastError());
+        if ((rc = hess_collect(h, nwg, st, &terms_f, &steps, &taylor))) return rc;
+    }
+    if (!taylor) {   // backward seeds (the step matrices of K workgroups fit those of the forward seeds)
+        HIPCHK(h, begin(K));
+        HESS_DISPATCH(hess_launch_backward, a, s)
+        HIPCHK(h, hipGetLastError());
+        if ((rc = hess_collect(h, K, st, &terms_b, &steps, &taylor))) return rc;
+    }
+    if (!taylor) HIPCHK(h, hipMemsetAsync(v.d_acc, 0, P * P * 8, s));
+    const unsigned eblocks = (unsigned)((P * P + 255) / 256);
+    for (int k0 = 0; k0 < h->K && !taylor; k0 += ntraj) {   // the fan, pass by pass
+        const int ng = std::min(ntraj, h->K - k0);
+        const size_t nwg = (size_t)ng * nblk;
+        HIPCHK(h, begin(nwg));
+        a.ws = v.d_wsfan; a.k0 = k0;
+        HESS_DISPATCH(hess_launch_fan, a, (int)nblk, ng, s)
+        hipLaunchKernelGGL(hess_accumulate_kernel, dim3(eblocks), dim3(256), 0, s, a, ng);
+        HIPCHK(h, hipGetLastError());
+        if ((rc = hess_collect(h, nwg, st, &terms_fan, &steps, &taylor))) return rc;
+    }
+    if (taylor) {
+        h->err = "grape_hessian: a series did not converge within 200 terms";
+        return GRAPE_ERR_TAYLOR;
+    }
+    hipLaunchKernelGGL(hess_finish_kernel, dim3(eblocks), dim3(256), 0, s, a);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipMemcpyAsync(H, v.d_H, P * P * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipStreamSynchronize(s));
+    v.info[0] = terms_f + terms_b + terms_fan; v.info[1] = steps; v.info[2] = (double)ntraj; v.info[3] = (double)v.store.mem.bytes();
+    v.info[4] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    v.info[5] = terms_f; v.info[6] = terms_b; v.info[7] = terms_fan;
+    return GRAPE_OK;
+}
+GRAPE_BARRIER(h ? &h->err : &g_create_error)
+
+int grape_get_hessian_info(grape_handle *h, double *out, int n) try {
+    if (!h || !out) return GRAPE_ERR_INVALID;
+    return copy_info(h->hess.info, 8, out, n);
 }
 GRAPE_BARRIER(h ? &h->err : &g_create_error)
 

@@ -688,6 +688,30 @@ def _make_hessp(wrk, bounds, state):
     return hessp
 
 
+def _make_hess(wrk, bounds, state):
+    """``hess(x)`` for scipy's ``trust-exact``: the backend's exact Hessian matrix at the pulses of its last evaluation
+    (grape_hessian).  The same rule as ``_make_hessp`` where x is not the point evaluated last, and the same refusals."""
+    backend = wrk.backend
+    if not callable(getattr(type(backend), "hessian", None)):
+        raise ValueError("method=trust-exact needs a backend with the exact Hessian matrix (`hessian`): the built-in "
+                         f"functionals on the plain HIP handle, not {type(backend).__name__}")
+    if wrk.kwargs.get("J_a") is not None:
+        raise ValueError("method=trust-exact cannot be combined with a pulse running cost J_a (its Hessian is not known)")
+    if bounds is not None:
+        raise ValueError("method=trust-exact cannot be combined with pulse bounds")
+    state["hess_calls"] = 0
+
+    def hess(x):
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        if state.get("x_eval") is None or not np.array_equal(x, state["x_eval"]):
+            backend.eval(x, gradient=False)
+            state["x_eval"] = x.copy()
+        state["hess_calls"] += 1
+        return np.asarray(backend.hessian(), dtype=np.float64).reshape(x.size, x.size)
+
+    return hess
+
+
 def optimize(trajectories, tlist, backend=None, **kwargs):
     """``GRAPE.optimize(trajectories, tlist; kwargs...)`` -- src/optimize.jl:73-144."""
     from scipy.optimize import minimize
@@ -751,17 +775,20 @@ def optimize(trajectories, tlist, backend=None, **kwargs):
                           np.where(np.isfinite(wrk.upper_bounds), wrk.upper_bounds, None)))
     # method="trust-ncg" / "newton-cg": second-order solvers of scipy.optimize.minimize on the exact Hessian-vector products of
     # the backend (grape_hvp; the reference names a true Hessian as future work, paper/paper.md:42).  Default: L-BFGS-B, the
-    # reference's optimizer.
+    # reference's optimizer.  method="trust-exact": scipy's nearly exact trust-region solver on the Hessian matrix itself
+    # (grape_hessian).
     solver = str(kwargs.get("method", "L-BFGS-B"))
-    second_order = {"trust-ncg": "trust-ncg", "newton-cg": "Newton-CG"}.get(solver.lower())
+    second_order = {"trust-ncg": "trust-ncg", "newton-cg": "Newton-CG", "trust-exact": "trust-exact"}.get(solver.lower())
     if second_order is None and solver.upper().replace("_", "-") not in ("L-BFGS-B", "LBFGSB", "GRAPE"):
-        raise ValueError(f"method={solver!r} not in (L-BFGS-B, trust-ncg, newton-cg)")
-    hessp = None
-    if second_order:
+        raise ValueError(f"method={solver!r} not in (L-BFGS-B, trust-ncg, newton-cg, trust-exact)")
+    hessp = hess = None
+    if second_order == "trust-exact":
+        hess = _make_hess(wrk, bounds, state)
+    elif second_order:
         hessp = _make_hessp(wrk, bounds, state)
     try:
         if second_order:
-            res = minimize(fg, wrk.pulsevals.copy(), jac=True, hessp=hessp, method=second_order, callback=new_x,
+            res = minimize(fg, wrk.pulsevals.copy(), jac=True, hess=hess, hessp=hessp, method=second_order, callback=new_x,
                            options=dict(maxiter=wrk.result.iter_stop + 1, **kwargs.get("solver_options", {})))
         else:
             res = minimize(fg, wrk.pulsevals.copy(), jac=True, method="L-BFGS-B", bounds=bounds, callback=new_x,

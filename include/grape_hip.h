@@ -462,6 +462,47 @@ int grape_hvp(grape_handle *h, int nv, const double *V, double *HV);
  * Returns the number of entries written (at most n). */
 int grape_get_hvp_info(grape_handle *h, double *out, int n);
 
+/* The exact Hessian of J as a matrix, in one call (entry points only: the ABI version stays 7; csrc/grape_hessian.hip.h,
+ * DESIGN.md 25).  What Newton-Raphson / RFO GRAPE with a regularised Hessian (Goodwin & Kuprov 2016), scipy's trust-exact
+ * and any look at the curvature of a converged pulse need (saddle points, conditioning, error bars):
+ *   H[p][q] = d^2 J / d eps_p d eps_q,  p, q < P = L*N_T, indexed as G (p = l*N_T + n), at the pulses of the last evaluation;
+ *   H: [P][P] doubles, the full symmetric matrix (both triangles, bitwise symmetric).
+ * J is the handle's built-in functional (J_T_sm / ss / re with weights, K == K_total).  Exact to rounding like grape_hvp:
+ * H[:, q] is what grape_hvp returns for the unit direction e_q -- but a unit direction spends two full sweeps on a tangent
+ * that is zero before its interval and merely propagated after it.  Here the first derivatives of every interval are
+ * formed once (forward from the stored Psi_k(t_n), backward from the bare targets), carried forwards sixteen columns to a
+ * matrix tile from the interval where they are born, and overlapped at every grid point; the diagonal blocks come from
+ * the second-order series of the backward chain, the coupling of the trajectories through f from a closed boundary term.
+ *   - Valid when grape_hvp is valid: after any successful evaluation that ran the forward half on the current time grid.
+ *     It reads only the stored forward states, tau, f, the device copy of the pulses and the static data of the handle
+ *     (balanced frame): the result does not depend on which exponential / derivative route ran.
+ *   - The storage is the handle's, allocated by the first call and freed by grape_destroy: 2 K N_T L NP 16 bytes of first
+ *     derivatives, two P x P matrices, and 8 P^2 bytes plus step matrices per trajectory of a pass.  The trajectories are
+ *     taken in passes under the memory budget of grape_hvp (8 GB, half of the free memory; GRAPE_HESS_TRAJ=<n>, read by
+ *     grape_create, sets the pass size); the passes are summed one trajectory after the other in ascending k, so the
+ *     result does not depend on the budget or on the passes, bit for bit.  Two calls give the same bits.
+ *   - The call runs on the handle's stream outside the captured graph and touches neither the scan set-up, the launch
+ *     plans nor the storage of grape_hvp and its halves: a grape_eval after it returns bit for bit what it returned
+ *     before; grape_get_time_gradient, grape_hvp, grape_expect and a pending grape_hvp_backward still answer.
+ *   - Series as grape_hvp: m = ceil(beta_n dt_n / theta) sub-steps, a series stops when every column has
+ *     ||term|| <= prop_tolerance ||sum||, after at most 200 terms -- beyond that GRAPE_ERR_TAYLOR, the handle stays usable.
+ *   - GRAPE_ERR_INVALID with a message that begins "grape_hessian:" and names the reason, before anything touches the
+ *     device, the handle stays usable: h == NULL (message through grape_last_error(NULL)), H == NULL; an open-system
+ *     handle; ndev > 1; N > 64; L > 4 (grape_hvp with unit directions is the route); L*N_T > 8192; a split-phase shard
+ *     (K < K_total); a handle without targets; the built-in running cost (Dpen, lambda_b != 0) or a last backward half that
+ *     took a caller's xi; no valid forward state (no evaluation yet, the last one failed, grape_set_tlist came since, or
+ *     the last call was grape_eval_batch).  A caller's chi and mixed derivatives with respect to the time steps are out of
+ *     scope.
+ *   - GRAPE_ERR_HIP with the sizes in the message when the storage cannot be allocated (even for one trajectory per pass);
+ *     nothing stays allocated then. */
+int grape_hessian(grape_handle *h, double *H);
+
+/* What the last grape_hessian of this handle did: [0] series terms and [1] (sub-)steps summed over all workgroups of the
+ * call;  [2] trajectories per pass;  [3] bytes of Hessian storage the handle holds;  [4] milliseconds of the last call (host
+ * wall time, copies included);  [5] / [6] / [7] the series terms of the forward seeds / the backward seeds / the fan
+ * ([0] = [5] + [6] + [7]).  Returns the number of entries written (at most n). */
+int grape_get_hessian_info(grape_handle *h, double *out, int n);
+
 /* grape_hvp in two halves, cut at its one cross-trajectory dependency (entry points only, the ABI version stays 7;
  * csrc/grape_hvp_split.hip.h).  What grape_hvp refuses -- a trajectory shard (K < K_total) and a caller's
  * functional, handles without targets included -- goes through these, as the gradient goes through grape_forward +

@@ -451,6 +451,35 @@ function hvp_info(h::Handle)
 end
 
 """
+    hessian!(H, h)
+
+The exact Hessian of `J` at the pulses of the last evaluation of `h` as a matrix (grape_hessian): `H` is `L*N_T × L*N_T`, indexed
+as the gradient, both triangles filled and bitwise symmetric; column `q` is what `hvp!` returns for the unit direction `e_q`.
+What Newton-Raphson / RFO with a regularised Hessian or `Optim.NewtonTrustRegion` (`h!(H, x)`: call `fg!` at `x` first) take.
+Valid where `hvp!` is valid, for `L ≤ 4` and `L*N_T ≤ 8192`; everything else is refused with a message (include/grape_hip.h).
+"""
+function hessian!(H::Matrix{Float64}, h::Handle)
+    isempty(h.fixed) || error("GrapeHIP.hessian!: handles with pseudo-controls are not supported (the matrix has no entries for them)")
+    size(H) == (h.L * h.N_T, h.L * h.N_T) || throw(DimensionMismatch("H must be L*N_T × L*N_T = $(h.L * h.N_T) × $(h.L * h.N_T)"))
+    check(h, GC.@preserve H ccall((:grape_hessian, libgrape), Cint, (Ptr{Cvoid}, Ptr{Float64}), h.ptr, H))
+    return H
+end
+
+"""
+    hessian_info(h)
+
+What the last `hessian!` did (grape_get_hessian_info): series `terms` and (sub-)`steps` summed over all workgroups, trajectories
+per pass, `bytes` of storage held by the handle, milliseconds of the call, and the series terms of the forward seeds, the
+backward seeds and the fan.
+"""
+function hessian_info(h::Handle)
+    out = zeros(Float64, 8)
+    GC.@preserve out ccall((:grape_get_hessian_info, libgrape), Cint, (Ptr{Cvoid}, Ptr{Float64}, Cint), h.ptr, out, 8)
+    return (terms = Int(out[1]), steps = Int(out[2]), traj_per_pass = Int(out[3]), bytes = Int(out[4]), ms = out[5],
+            terms_forward_seeds = Int(out[6]), terms_backward_seeds = Int(out[7]), terms_fan = Int(out[8]))
+end
+
+"""
     expect!(out, h, ops)
 
 Expectation values of operator observables on the stored forward states of the last evaluation of `h`, computed on the device
