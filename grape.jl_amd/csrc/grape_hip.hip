@@ -5478,6 +5478,7 @@ GRAPE_BARRIER(h ? &h->err : &g_create_error)
 namespace {
 
 // workgroups of the forward seeds along the intervals: about four workgroups per compute unit over all trajectories
+// (restated as seed_rows in tests/test_gpu_hessian.py, whose LONG_CASES are chosen by it: the two move together)
 int hess_seed_rows(const grape_handle *h) { return std::max(1, std::min(h->N_T, (1024 + h->K - 1) / h->K)); }
 
 // bytes every call holds whatever the pass size | bytes per trajectory of a pass (strip, step matrices and statistics of its fan)

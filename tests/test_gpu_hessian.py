@@ -4,7 +4,15 @@ Bar: the project's gradient tolerance applied to the entries of H against tests/
 tests/test_hessian_reference.py),
     ||dH||_inf <= 1e-10 * max(||H||_inf, 1e-3)   over all entries,
 and every case asserts on the reference alone min|tau_k| >= 0.1, ||G||_inf >= 1e-3, ||H||_inf >= 1e-3, so that the bound is
-relative and never its floor.  The shapes are the smallest at which each mechanism can go wrong (the table of CASES).
+relative and never its floor.  The shapes are the smallest at which each mechanism can go wrong: the table of CASES for
+the kernels' arithmetic (paddings, column blocks that straddle intervals, a full backward tile, cut intervals), where every
+forward-seed workgroup takes one interval, and the table of LONG_CASES for the launch plan beyond that regime:
+  * the stride of the forward seeds: hess_seed_rows (csrc/grape_hip.hip, restated here as ``seed_rows``) deals
+    min(N_T, ceil(1024 / K)) workgroups per trajectory, so with K N_T > 1024 a workgroup takes n = g, g + rows, ... -- a second
+    trip for some workgroups only (N_T 300, K 4), for every one (N_T 2048, K 1), and all intervals in one workgroup (K 1030);
+  * the block count: 38 and 128 column blocks of the fan instead of at most three, columns carried across up to 2047
+    intervals, and 1407 and 16384 workgroups of the accumulate and finish kernels instead of at most five;
+  * the NULL operands: handles created without weights and without shape (``plain``), under sm and ss.
 "Bit for bit" is ``np.array_equal``.
 """
 import numpy as np
@@ -18,8 +26,9 @@ from grape_jl_amd import synth
 pytestmark = pytest.mark.gpu
 
 
-def make_case(N, L, N_T, K, seed, herm=True, per_traj=False, skew=0, dt=1.0, amp=3.0, uniform=False):
-    """weights, shape and a non-uniform grid throughout (``uniform``: every interval is dt long)"""
+def make_case(N, L, N_T, K, seed, herm=True, per_traj=False, skew=0, dt=1.0, amp=3.0, uniform=False, plain=False):
+    """weights, shape and a non-uniform grid throughout (``uniform``: every interval is dt long; ``plain``: neither weights
+    nor shape, the handle gets NULL for both)"""
     pr = synth.make_problem(N, L, N_T, K, seed=seed, hermitian=herm, dt=dt)
     pr["pulsevals"] = amp * pr["pulsevals"]
     if per_traj:
@@ -40,6 +49,9 @@ def make_case(N, L, N_T, K, seed, herm=True, per_traj=False, skew=0, dt=1.0, amp
         pr["tlist"] = np.concatenate([[0.0], np.cumsum(dt * (0.5 + u[:N_T]))])
     pr["shape"] = 0.5 + 0.5 * u[N_T:N_T + L * N_T].reshape(L, N_T)
     pr["weights"] = 0.5 + u[N_T + L * N_T:]
+    if plain:
+        pr["shape"] = None
+        pr["weights"] = None
     hr.order_one_targets(pr)
     return pr
 
@@ -63,13 +75,37 @@ CASES = {
     "N48-L1-NT18-K1-ss-long-intervals": dict(N=48, L=1, N_T=18, K=1, f=1, dt=4.0, uniform=True),
     "N64-L2-NT9-K1-sm": dict(N=64, L=2, N_T=9, K=1, f=0),
 }
+
+
+def seed_rows(K, N_T):
+    """workgroups of the forward seeds per trajectory: hess_seed_rows of csrc/grape_hip.hip restated.  Below N_T, workgroup
+    g takes the intervals n = g, g + rows, ..."""
+    return max(1, min(N_T, (1024 + K - 1) // K))
+
+
+# beyond one interval per forward-seed workgroup, three column blocks and five element workgroups; NULL weights and shape
+LONG_CASES = {
+    # rows = 256 < 300: the workgroups g < 44 take two intervals, the rest one; 38 column blocks; 1407 element workgroups
+    "N3-L2-NT300-K4-sm-strided-seeds": dict(N=3, L=2, N_T=300, K=4, f=0),
+    # rows = 26 < 30 with many trajectories: the boundary term of ss over 40 of them
+    "N5-L1-NT30-K40-ss-strided-seeds": dict(N=5, L=1, N_T=30, K=40, f=1),
+    # rows = 1: one workgroup per trajectory loops over all intervals; grid.x = 1030; the boundary term of sm over 1030
+    "N2-L1-NT3-K1030-sm-one-seed-row": dict(N=2, L=1, N_T=3, K=1030, f=0),
+    # rows = 1024: every workgroup takes exactly two intervals; 128 column blocks; carries across 2047 intervals; 16384
+    # element workgroups
+    "N2-L1-NT2048-K1-re-two-intervals-per-seed": dict(N=2, L=1, N_T=2048, K=1, f=2, dt=0.25),
+    # NULL weights and shape: the coefficient and the boundary term of sm, then ss with a full backward tile
+    "N20-L3-NT12-K2-sm-plain": dict(N=20, L=3, N_T=12, K=2, f=0, plain=True, uniform=True),
+    "N17-L4-NT6-K2-ss-plain": dict(N=17, L=4, N_T=6, K=2, f=1, plain=True, uniform=True, amp=1.5),
+}
+STRIDED = list(LONG_CASES)[:4]
 _cache = {}
 
 
 def case(name):
     """(problem, functional, reference): computed once and shared, never modified"""
     if name not in _cache:
-        c = dict(CASES[name])
+        c = dict(CASES[name] if name in CASES else LONG_CASES[name])
         f = c.pop("f")
         pr = make_case(seed=2000 + sum(map(ord, name)), **c)
         _cache[name] = (pr, f, hs.evaluate(pr, pr["pulsevals"], f))
@@ -81,6 +117,17 @@ def uncut_steps(L, N_T, K):
     the fan from the interval after the birth of its first column to the last but one"""
     fan = sum(max(0, N_T - 1 - ((16 * b) // L + 1)) for b in range((L * N_T + 15) // 16))
     return K * (2 * N_T + fan)
+
+
+def probe_columns(L, N_T, K):
+    """the columns of H (p = l N_T + n) where the launch plan changes, from the shape alone.  The fan and the seeds count
+    interval-major, q = n L + l: the first and the last column, both sides of the first column-block boundary (q = 15, 16),
+    the first and last control on both sides of the seed stride (n = rows - 1, rows), one column of the interior (q = P / 3).
+    At most nine."""
+    P, rows = L * N_T, seed_rows(K, N_T)
+    qs = [0, P - 1, 15, 16] + [n * L + l for n in (rows - 1, rows) for l in (0, L - 1)] + [P // 3]
+    qs = list(dict.fromkeys(q for q in qs if 0 <= q < P))
+    return np.array([(q % L) * N_T + q // L for q in qs])
 
 
 @pytest.mark.parametrize("name", list(CASES))
@@ -110,6 +157,82 @@ def test_hessian_against_the_reference(name):
     assert info["series_terms"] == info["terms_forward_seeds"] + info["terms_backward_seeds"] + info["terms_fan"]
     assert min(info["terms_forward_seeds"], info["terms_backward_seeds"], info["terms_fan"]) > 0
     assert info["traj_per_pass"] == pr["K"] and info["bytes"] > 0 and info["ms"] > 0
+
+
+@pytest.mark.parametrize("name", list(LONG_CASES))
+def test_hessian_beyond_one_interval_per_seed_workgroup(name):
+    """LONG_CASES against the reference (proved at these lengths in tests/test_hessian_reference.py), and against grape_hvp
+    on the columns where the launch plan changes.  Worst dH / tol on the device: docs/LAB_NOTEBOOK.md"""
+    pr, f, want = case(name)
+    L, N_T, K = pr["L"], pr["N_T"], pr["K"]
+    P, rows = L * N_T, seed_rows(K, N_T)
+    if name in STRIDED:
+        assert rows < N_T, (rows, N_T)           # from the inputs alone: the case reaches the strided loop
+    else:
+        assert pr["weights"] is None and pr["shape"] is None
+    hs.assert_order_one(want)
+    cols = probe_columns(L, N_T, K)
+    assert 1 <= len(cols) <= 16 and len(set(cols)) == len(cols)
+    E = np.zeros((len(cols), P))
+    E[np.arange(len(cols)), cols] = 1.0
+    with handle(pr, f) as h:
+        J, G, tau = h.eval(pr["pulsevals"])
+        H = h.hessian()
+        info = h.hessian_info()
+        Hv = h.hvp(E)
+    print(name, dict(dJ=abs(J - want["J"]), dG=float(np.abs(G - want["G"]).max()), tol_G=hr.tol_hv(want["G"])))
+    assert abs(J - want["J"]) <= 1e-12 and np.abs(G - want["G"]).max() <= hr.tol_hv(want["G"])
+    assert H.shape == (P, P)
+    dev = hs.assert_hessian_agrees(H, want["H"], name)
+    print(name, "worst dH / tol = %.3g" % (dev / hs.tol_hessian(want["H"])))
+    assert np.array_equal(H, H.T)
+    # on the device: column p is grape_hvp of the unit direction e_p
+    hs.assert_hessian_agrees(H[cols], Hv, name + " against grape_hvp(unit directions %s)" % cols.tolist())
+    print(info)
+    steps = uncut_steps(L, N_T, K)
+    assert info["series_steps"] >= steps, (info, steps)
+    assert info["series_terms"] == info["terms_forward_seeds"] + info["terms_backward_seeds"] + info["terms_fan"]
+    assert min(info["terms_forward_seeds"], info["terms_backward_seeds"], info["terms_fan"]) > 0
+    assert info["traj_per_pass"] == K
+
+
+def test_passes_on_a_strided_shape_give_the_same_bits(monkeypatch):
+    """K = 4 with strided seeds: passes of 3 + 1 trajectories and four passes of one against the default single pass"""
+    pr, f, _ = case("N3-L2-NT300-K4-sm-strided-seeds")
+    assert seed_rows(pr["K"], pr["N_T"]) < pr["N_T"]
+    got = {}
+    for traj, reported in ((None, 4), ("3", 3), ("1", 1)):
+        if traj:
+            monkeypatch.setenv("GRAPE_HESS_TRAJ", traj)
+        with handle(pr, f) as h:
+            h.eval(pr["pulsevals"])
+            got[traj] = h.hessian()
+            assert h.hessian_info()["traj_per_pass"] == reported
+            assert np.array_equal(h.hessian(), got[traj])
+    assert np.array_equal(got["3"], got[None]) and np.array_equal(got["1"], got[None])
+
+
+@pytest.mark.parametrize("name", ["N3-L1-NT20-K2-sm", "N64-L2-NT9-K1-sm"])
+def test_hessian_from_the_stored_states_of_the_default_route(monkeypatch, name):
+    """without the session's GRAPE_DERIV3=1 pin (tests/test_gpu_default_routes.py) a small problem stores the forward states of
+    the scan sweeps and the workgroup-per-batch derivative kernels; the Hessian is taken after the captured graph has replayed"""
+    pr, f, want = case(name)
+    monkeypatch.setenv("GRAPE_DERIV3", "1")
+    with handle(pr, f) as h:
+        h.eval(pr["pulsevals"])
+        pinned, pinned_kernel = h.hessian(), int(h.work()["asm_deriv_kernel"])
+    monkeypatch.delenv("GRAPE_DERIV3")
+    with handle(pr, f) as h:
+        for _ in range(4):            # (beyond the second evaluation the captured graph replays)
+            J, G, tau = h.eval(pr["pulsevals"])
+        H, kernel = h.hessian(), int(h.work()["asm_deriv_kernel"])
+    if pr["N"] >= 49:                 # (grape_get_work names the derivative kernel from N = 49 on: the two handles took two routes)
+        assert (pinned_kernel, kernel) == (1, 0), (pinned_kernel, kernel)
+    assert abs(J - want["J"]) <= 1e-12 and np.abs(G - want["G"]).max() <= hr.tol_hv(want["G"])
+    hs.assert_hessian_agrees(H, want["H"], name + " default route")
+    hs.assert_hessian_agrees(H, pinned, name + " default route against the pinned route")
+    print(name, "bit for bit with the pinned route:", np.array_equal(H, pinned))
+    assert np.array_equal(H, H.T)
 
 
 def test_two_calls_and_forced_passes_give_the_same_bits(monkeypatch):

@@ -37,7 +37,8 @@ def make_case(N, L, K, seed, herm=True, per_traj=False, shape=False, weights=Fal
     if nonuniform:
         pr["tlist"] = np.concatenate([[0.0], np.cumsum(dt * (0.5 + u[:N_T]))])
     pr["shape"] = 0.5 + 0.5 * u[N_T:N_T + L * N_T].reshape(L, N_T) if shape else None
-    pr["weights"] = 0.5 + u[N_T + L * N_T:] if weights else np.ones(K)
+    # True: drawn; False: ones; None: no weights at all, the handle gets NULL
+    pr["weights"] = None if weights is None else 0.5 + u[N_T + L * N_T:] if weights else np.ones(K)
     hr.order_one_targets(pr)
     return pr
 
@@ -52,6 +53,8 @@ CASES = {
     "N3-L1-sm": dict(N=3, L=1, K=2, f=0),
     "N16-L8-ss": dict(N=16, L=8, K=2, f=1, amp=1.0),
     "N16-L2-re": dict(N=16, L=2, K=2, f=2),
+    # weights == NULL in grape_problem: the other arm of every `weights ? weights[k] : 1.0` (sm: coefficient and its derivative)
+    "N16-L2-sm-no-weights": dict(N=16, L=2, K=2, f=0, weights=None),
     "N17-L3-re-K3-weights-shape-nonuniform": dict(N=17, L=3, K=3, f=2, weights=True, shape=True, nonuniform=True),
     "N32-L2-ss-pertraj": dict(N=32, L=2, K=2, f=1, per_traj=True),
     "N32-L1-sm": dict(N=32, L=1, K=2, f=0),

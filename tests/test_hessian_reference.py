@@ -4,7 +4,8 @@ and by the shared comparison refusing deliberately wrong references.  No GPU, no
 
 Both references are double-precision restatements of the same derivative with different formulas (explicit Psi', chi' there;
 seeds, fan and a closed boundary term here).  Their largest deviation over the five shapes below was measured as 2.2e-16 for
-||H||_inf between 0.27 and 0.84; the bound is 1e-12 ||H||_inf."""
+||H||_inf between 0.27 and 0.84; the bound is 1e-12 ||H||_inf.  At the lengths of the device test's long cases (300 and 2048
+intervals, seven to nine columns each) it was 1.0e-15 at ||H||_inf = 0.81 and 2.2e-16 at 0.085, under the same bound."""
 import numpy as np
 import pytest
 
@@ -65,6 +66,39 @@ def test_reference_is_symmetric(cases, name):
     _, _, want = cases[name]
     H = want["H"]
     assert np.abs(H - H.T).max() <= 1e-14 * np.abs(H).max()
+
+
+# the two longest cases of the device test's second table, under its names and seeds (tests/test_gpu_hessian.py imports
+# without a GPU): 300 and 2048 intervals, where the comparison above stops at 20
+LONG = ["N3-L2-NT300-K4-sm-strided-seeds", "N2-L1-NT2048-K1-re-two-intervals-per-seed"]
+
+
+@pytest.mark.parametrize("name", LONG)
+def test_reference_at_the_lengths_of_the_long_device_cases(name):
+    """columns of H against the hvp reference with the matching unit directions, where the device's launch plan changes
+    (first and last column, q = 15 and 16, both sides of n = rows, one mid column), and the symmetry of the whole matrix"""
+    import test_gpu_hessian as dev
+    assert name in dev.LONG_CASES
+    pr, f, want = dev.case(name)
+    hs.assert_order_one(want)
+    L, N_T, K = pr["L"], pr["N_T"], pr["K"]
+    P, rows = L * N_T, dev.seed_rows(K, N_T)
+    assert rows < N_T
+    cols = dev.probe_columns(L, N_T, K)
+    n_of = cols % N_T
+    assert {0, P - 1} <= set(cols.tolist()) and {rows - 1, rows} <= set(n_of.tolist()) and 7 <= len(cols) <= 9
+    E = np.zeros((len(cols), P))
+    E[np.arange(len(cols)), cols] = 1.0
+    other = hr.evaluate(pr, pr["pulsevals"], E, f)
+    H = want["H"]
+    scale = np.abs(H).max()
+    dev_cols = np.abs(H[:, cols].T - other["Hv"]).max()
+    print(name, dict(columns=cols.tolist(), dH=dev_cols, H_max=scale, asym=np.abs(H - H.T).max()))
+    assert abs(want["J"] - other["J"]) <= 1e-14
+    assert np.abs(want["tau"] - other["tau"]).max() <= 1e-14
+    assert np.abs(want["G"] - other["G"]).max() <= 1e-12 * max(np.abs(other["G"]).max(), 1.0)
+    assert dev_cols <= 1e-12 * scale
+    assert np.abs(H - H.T).max() <= 1e-14 * scale
 
 
 # (mutation, the shapes it is tried on): the boundary term under sm and under ss (it vanishes under re)
