@@ -38,7 +38,8 @@ EXPORTS = ["grape_create", "grape_destroy", "grape_eval", "grape_forward", "grap
            "grape_open_eval_batch", "grape_get_open_batch_info", "grape_open_set_running_cost", "grape_open_backward_xi",
            "grape_hvp_forward", "grape_hvp_backward", "grape_hvp_backward_chi",
            "grape_open_hvp_forward", "grape_open_hvp_backward", "grape_open_hvp_backward_chi",
-           "grape_expect", "grape_get_expect_info", "grape_hessian", "grape_get_hessian_info"]
+           "grape_expect", "grape_get_expect_info", "grape_hessian", "grape_get_hessian_info",
+           "grape_open_hessian", "grape_get_open_hessian_info"]
 
 
 class GrapeHipError(RuntimeError):
@@ -106,7 +107,7 @@ def build_asm(verbose: bool = False, workdir: str | None = None) -> str:
 def _sources():
     srcs = [os.path.join(_CSRC, f) for f in ("grape_hip.hip", "grape_t18.hip", "grape_kernels.hip.h", "grape_large.hip.h",
                                              "grape_series.hip.h", "grape_cheby.hip.h", "grape_t18.hip.h", "grape_t18_coeffs.h",
-                                             "grape_deriv3.hip.h", "grape_timegrad.hip.h", "grape_batch.hip.h", "grape_lindblad.hip.h", "grape_lindblad_tg.hip.h", "grape_hvp.hip.h", "grape_hvp_split.hip.h", "grape_hessian.hip.h", "grape_lindblad_hvp.hip.h", "grape_lindblad_hvp_split.hip.h", "grape_lindblad_batch.hip.h", "grape_lindblad_rc.hip.h", "grape_devmem.h", "grape_cert.hip.h", "grape_expect.hip.h", "grape_econ_coeffs.h", os.path.join("asm", "gen_t16.py"), os.path.join("asm", "gen_t16q.py"), os.path.join("asm", "gen_t16r.py"), os.path.join("asm", "gen_t16p.py"), os.path.join("asm", "gen_t18g.py"), os.path.join("asm", "gen_t18gp.py"), os.path.join("asm", "gen_d3.py"), os.path.join("asm", "gen_d3s.py"), os.path.join("asm", "gen_lg.py"), os.path.join("asm", "gen_d4.py"), os.path.join("asm", "gcn.py"))]
+                                             "grape_deriv3.hip.h", "grape_timegrad.hip.h", "grape_batch.hip.h", "grape_lindblad.hip.h", "grape_lindblad_tg.hip.h", "grape_hvp.hip.h", "grape_hvp_split.hip.h", "grape_hessian.hip.h", "grape_lindblad_hvp.hip.h", "grape_lindblad_hessian.hip.h", "grape_lindblad_hvp_split.hip.h", "grape_lindblad_batch.hip.h", "grape_lindblad_rc.hip.h", "grape_devmem.h", "grape_cert.hip.h", "grape_expect.hip.h", "grape_econ_coeffs.h", os.path.join("asm", "gen_t16.py"), os.path.join("asm", "gen_t16q.py"), os.path.join("asm", "gen_t16r.py"), os.path.join("asm", "gen_t16p.py"), os.path.join("asm", "gen_t18g.py"), os.path.join("asm", "gen_t18gp.py"), os.path.join("asm", "gen_d3.py"), os.path.join("asm", "gen_d3s.py"), os.path.join("asm", "gen_lg.py"), os.path.join("asm", "gen_d4.py"), os.path.join("asm", "gcn.py"))]
     return srcs, os.path.join(_HERE, "..", "include", "grape_hip.h")
 
 
@@ -223,6 +224,8 @@ def load_library():
     lib.grape_get_hvp_info.argtypes = [vp, vp, ip]
     lib.grape_hessian.argtypes = [vp, vp]
     lib.grape_get_hessian_info.argtypes = [vp, vp, ip]
+    lib.grape_open_hessian.argtypes = [vp, vp]
+    lib.grape_get_open_hessian_info.argtypes = [vp, vp, ip]
     lib.grape_hvp_forward.argtypes = [vp, ip, vp, vp, vp, vp]
     lib.grape_hvp_backward.argtypes = [vp, ip, vp, vp, vp]
     lib.grape_hvp_backward_chi.argtypes = [vp, ip, vp, vp, vp]
@@ -813,6 +816,27 @@ class GrapeHipOpen(GrapeHip):
         self._lib.grape_get_open_hvp_info(self._h, out.ctypes.data, 7)
         return dict(series_terms=int(out[0]), series_steps=int(out[1]), dirs_per_group=int(out[2]), bytes=int(out[3]), ms=float(out[4]),
                     terms_forward=int(out[5]), terms_backward=int(out[6]))
+
+    def open_hessian(self):
+        """The exact Hessian of J at the pulses of the last evaluation as a matrix (grape_open_hessian): [L*N_T, L*N_T], indexed
+        as G, both triangles, bitwise symmetric.  Column q is what ``open_hvp`` gives for the unit direction e_q, to rounding, at
+        a fraction of its cost.  Valid whenever ``open_hvp`` is; the built-in functional only, L <= 4, L*N_T <= 8192
+        (include/grape_hip.h lists the refusals).  A method of its own: the inherited ``hessian`` stays grape_hessian, which
+        refuses an open handle."""
+        P = self.L * self.N_T
+        out = np.empty((P, P))
+        self._chk(self._lib.grape_open_hessian(self._h, out.ctypes.data))
+        return out
+
+    def open_hessian_info(self):
+        """What the last ``open_hessian`` did (grape_get_open_hessian_info): series terms and (sub-)steps summed over all
+        workgroups and per kernel (forward seeds, backward seeds, fan), trajectories per pass, bytes of Hessian storage the handle
+        holds, milliseconds of the call, columns per workgroup of the fan."""
+        out = np.zeros(12)
+        self._lib.grape_get_open_hessian_info(self._h, out.ctypes.data, 12)
+        return dict(series_terms=int(out[0]), series_steps=int(out[1]), traj_per_pass=int(out[2]), bytes=int(out[3]), ms=float(out[4]),
+                    terms_forward_seeds=int(out[5]), terms_backward_seeds=int(out[6]), terms_fan=int(out[7]),
+                    steps_forward_seeds=int(out[8]), steps_backward_seeds=int(out[9]), steps_fan=int(out[10]), fan_columns=int(out[11]))
 
     def open_hvp_forward(self, V, final_states=False):
         """First half of a split Hessian-vector product (grape_open_hvp_forward): the tangent forward sweep of ``V``

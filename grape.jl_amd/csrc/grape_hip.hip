@@ -19,6 +19,7 @@
 #include "grape_hvp.hip.h"
 #include "grape_hvp_split.hip.h"
 #include "grape_hessian.hip.h"
+#include "grape_lindblad_hessian.hip.h"
 #include "grape_lindblad_hvp.hip.h"
 #include "grape_lindblad_hvp_split.hip.h"
 #include "grape_lindblad_batch.hip.h"
@@ -1635,6 +1636,17 @@ struct OpenCtx {
         unsigned long long *d_obstats = nullptr;
         double info[7] = {0., 0., 0., 0., 0., 0., 0.};   // grape_get_open_batch_info
     } ob;
+    // grape_open_hessian (grape_lindblad_hessian.hip.h): the Hessian as a matrix.  Storage of its own -- the seeds,
+    // the overlaps, the accumulator and the result, and per trajectory of a pass a strip and the workspaces of its fan --
+    // allocated by the first call and freed by grape_destroy; nothing an evaluation, a getter or grape_open_hvp uses is touched.
+    struct HessStore {
+        GroupStore store;         // units: trajectories per pass; env: GRAPE_OPEN_HESS_TRAJ
+        int cols_env = 0;         // columns per workgroup of the fan; env: GRAPE_OPEN_HESS_COLS (0: the rule of open_hess_cols)
+        double *d_a = nullptr, *d_b = nullptr, *d_th = nullptr, *d_strip = nullptr, *d_acc = nullptr, *d_H = nullptr, *d_wsseed = nullptr, *d_wsfan = nullptr;
+        double2 *d_T = nullptr, *d_Sd = nullptr;
+        unsigned long long *d_stats = nullptr;   // statistics of the workgroups of a launch, then the flag word
+        double info[12] = {0., 0., 0., 0., 0., 0., 0., 0., 0., 0., 0., 0.};   // grape_get_open_hessian_info
+    } hess;
     // state running costs (grape_lindblad_rc.hip.h).  The built-in cost g_b = Re tr(D rho) of
     // grape_open_set_running_cost: Xi_k = -D_k^dagger / 2, the trapezoid weights of the current grid, g_b of every stored state.
     // d_xi_user holds the caller's xi of grape_open_backward_xi.  All four are allocated on first use.
@@ -1656,7 +1668,7 @@ void open_destroy(grape_handle *h) {
     OpenCtx *o = h->open;
     hipSetDevice(h->device);
     if (h->stream) hipStreamSynchronize(h->stream);
-    o->hv.store.release(); o->hvs.mem.release(); o->ob.store.release(); h->ex.mem.release(); o->mem.release();
+    o->hv.store.release(); o->hvs.mem.release(); o->ob.store.release(); o->hess.store.release(); h->ex.mem.release(); o->mem.release();
     for (hipEvent_t e : o->ev)
         if (e) hipEventDestroy(e);
     if (h->stream) hipStreamDestroy(h->stream);
@@ -2532,6 +2544,8 @@ int grape_create_open(grape_handle **out, const grape_problem *p, const grape_li
     o->J = diss->J; o->cops_per_traj = diss->cops_per_traj ? 1 : 0;
     if (const char *envh = getenv("GRAPE_HVP_DIRS")) o->hv.store.env = std::max(0, atoi(envh));   // (grape_open_hvp: as grape_create)
     if (const char *envb = getenv("GRAPE_OPEN_BATCH_SETS")) o->ob.store.env = std::max(0, atoi(envb));   // (grape_open_eval_batch: sets per launch group)
+    if (const char *envt = getenv("GRAPE_OPEN_HESS_TRAJ")) o->hess.store.env = std::max(0, atoi(envt));   // (grape_open_hessian: trajectories per pass)
+    if (const char *envc = getenv("GRAPE_OPEN_HESS_COLS")) o->hess.cols_env = std::max(0, std::min(16, atoi(envc)));   // (... columns per fan workgroup)
     o->Kj = o->cops_per_traj ? p->K : 1; o->Kc = p->hc_per_traj ? p->K : 1;
 
     auto fail = [&](int code) { g_create_error = h->err; return code; };   // (the guard releases the handle)
@@ -5646,6 +5660,214 @@ GRAPE_BARRIER(h ? &h->err : &g_create_error)
 int grape_get_hessian_info(grape_handle *h, double *out, int n) try {
     if (!h || !out) return GRAPE_ERR_INVALID;
     return copy_info(h->hess.info, 8, out, n);
+}
+GRAPE_BARRIER(h ? &h->err : &g_create_error)
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------
+// grape_open_hessian: the exact Hessian of J as a matrix on the stored density matrices of an open-system handle
+// (grape_lindblad_hessian.hip.h)
+// ---------------------------------------------------------------------------------------
+namespace {
+
+// workgroups of the forward seeds along the intervals: about four workgroups per compute unit over all trajectories and controls
+// (restated with open_hess_back_rows as seed_rows in tests/test_gpu_open_hessian.py, whose long case is chosen by them)
+int open_hess_seed_rows(const grape_handle *h) {
+    const int kl = h->K * h->L;
+    return std::max(1, std::min(h->N_T, (1024 + kl - 1) / kl));
+}
+
+// columns per workgroup of the fan: one, unless that makes more than 4096 workgroups per trajectory set (a column's bits do
+// not depend on it)
+int open_hess_cols(const grape_handle *h) {
+    if (h->open->hess.cols_env > 0) return h->open->hess.cols_env;
+    const size_t P = (size_t)h->L * h->N_T;
+    int cb = 1;
+    while (cb < 16 && (P + cb - 1) / cb * (size_t)h->K > 4096) cb *= 2;
+    return cb;
+}
+
+// ... of the backward seeds: about two workgroups per compute unit over all trajectories and pairs (their workspace is the
+// largest of the call, 14 + 4J matrices)
+int open_hess_back_rows(const grape_handle *h) {
+    const int kp = h->K * (h->L * (h->L + 1) / 2);
+    return std::max(1, std::min(h->N_T, (512 + kp - 1) / kp));
+}
+
+// matrices (2 NP^2 doubles) of the seed workspaces: the largest of the forward seeds, the theta sweep and the backward seeds
+size_t open_hess_seed_mats(const grape_handle *h) {
+    const size_t K = (size_t)h->K, L = (size_t)h->L, J = (size_t)h->open->J, pairs = L * (L + 1) / 2;
+    return std::max({K * (size_t)open_hess_seed_rows(h) * L * (6 + 2 * J), K * (4 + J), K * pairs * (size_t)open_hess_back_rows(h) * (14 + 4 * J)});
+}
+size_t open_hess_seed_groups(const grape_handle *h) {
+    const size_t K = (size_t)h->K, L = (size_t)h->L;
+    return std::max(K * (size_t)open_hess_seed_rows(h) * L, K * (L * (L + 1) / 2) * (size_t)open_hess_back_rows(h));
+}
+
+// bytes every call holds whatever the pass size | bytes per trajectory of a pass (strip, workspaces and statistics of its fan)
+size_t open_hess_bytes_fixed(const grape_handle *h) {
+    const size_t K = (size_t)h->K, N_T = (size_t)h->N_T, L = (size_t)h->L, P = L * N_T, m2 = 2 * (size_t)h->NP * h->NP;
+    return 2 * K * N_T * L * m2 * 8 + K * (N_T + 1) * m2 * 8 + K * P * 16 + K * N_T * HESS_PAIRS * 16 + 2 * P * P * 8 + open_hess_seed_mats(h) * m2 * 8 +
+           (2 * open_hess_seed_groups(h) + 1) * 8;
+}
+size_t open_hess_bytes_per_trajectory(const grape_handle *h, int cb) {
+    const size_t P = (size_t)h->L * h->N_T, m2 = 2 * (size_t)h->NP * h->NP, nblk = (P + cb - 1) / cb;
+    return P * P * 8 + nblk * (4 + (size_t)h->open->J + cb) * m2 * 8 + nblk * 16;
+}
+
+// trajectories per pass and the storage for that many: the budget rule of grape_devmem.h on what the fixed part leaves of 8 GB
+int open_hess_reserve(grape_handle *h, int cb, int *traj) {
+    auto &v = h->open->hess;
+    const size_t K = (size_t)h->K, N_T = (size_t)h->N_T, L = (size_t)h->L, P = L * N_T, m2 = 2 * (size_t)h->NP * h->NP, nblk = (P + cb - 1) / cb;
+    const size_t fixed = open_hess_bytes_fixed(h), per = open_hess_bytes_per_trajectory(h, cb);
+    hipError_t e = v.store.plan(h->K, per, std::max(0.0, 8.0 * 1073741824.0 - (double)fixed), traj);
+    if (e != hipSuccess) { h->err = std::string("hipMemGetInfo(&free_b, &total_b): ") + hipGetErrorString(e); return GRAPE_ERR_HIP; }
+    const GroupStore::Grow r = v.store.grow(*traj, h->stream, [&](GroupStore::Requests &get) {
+        const size_t n = (size_t)*traj;
+        get(&v.d_a, K * N_T * L * m2); get(&v.d_b, K * N_T * L * m2); get(&v.d_th, K * (N_T + 1) * m2); get(&v.d_T, K * P);
+        get(&v.d_Sd, K * N_T * HESS_PAIRS); get(&v.d_acc, P * P); get(&v.d_H, P * P); get(&v.d_wsseed, open_hess_seed_mats(h) * m2);
+        get(&v.d_strip, n * P * P); get(&v.d_wsfan, n * nblk * (4 + (size_t)h->open->J + cb) * m2);
+        get(&v.d_stats, 2 * std::max(open_hess_seed_groups(h), n * nblk) + 1);
+    }, &e);
+    if (r == GroupStore::Grow::sync_failed) { h->err = std::string("hipStreamSynchronize(h->stream): ") + hipGetErrorString(e); return GRAPE_ERR_HIP; }
+    if (r == GroupStore::Grow::alloc_failed) {
+        h->err = "grape_open_hessian: out of device memory for the seeds, the accumulator and the result (" + std::to_string(fixed >> 20) +
+                 " MB) and the strips of " + std::to_string(*traj) + " trajectories per pass (" + std::to_string(per * (size_t)*traj >> 20) +
+                 " MB); GRAPE_OPEN_HESS_TRAJ=<n> makes the passes smaller";
+        (void)hipGetLastError();
+        return GRAPE_ERR_HIP;
+    }
+    return GRAPE_OK;
+}
+
+// why this handle cannot give the Hessian (nullptr: it can); every test precedes the first HIP call
+const char *open_hess_refusal(const grape_handle *h) {
+    if (!h->open) return "not an open-system handle (grape_create_open); grape_hessian is the call for a closed one";
+    if (h->L > HESS_MAX_L)
+        return "L > 4 is out of scope (the backward seeds run one workgroup per pair of controls, ten at most): grape_open_hvp with "
+               "unit directions is the route";
+    if ((long long)h->L * h->N_T > 8192) return "L * N_T > 8192 is out of scope (the matrix and a strip per trajectory are (L * N_T)^2 doubles each)";
+    if (h->K != h->K_total) return "a split-phase shard (K < K_total) is out of scope: the boundary term couples all trajectories";
+    if (h->no_target) return "this handle has no target states (grape_problem.target == NULL): the functional would be the caller's";
+    if (h->open->rc_set)
+        return "a state running cost is set on this handle (grape_open_set_running_cost): its second-order terms are not carried";
+    switch (h->open->hv_state) {
+    case OpenCtx::HV_READY: return nullptr;
+    case OpenCtx::HV_NONE: return "no valid forward state: no evaluation on this handle yet";
+    case OpenCtx::HV_NEW_GRID: return "no valid forward state: grape_set_tlist came after the last evaluation, the stored states belong to the previous grid";
+    case OpenCtx::HV_NEW_COST: return "no valid forward state: grape_open_set_running_cost came after the last evaluation";
+    case OpenCtx::HV_BATCH: return "no valid forward state: the last call was grape_eval_batch, the stored states are not those of one defined evaluation";
+    default: return "no valid forward state: the last forward sweep failed";
+    }
+}
+
+// H = d^2 J / d eps^2 at the pulses of the last forward half, from the stored rho_k(t_n), tau, f and the device copy of the
+// pulses.  Touches nothing an evaluation, a getter or grape_open_hvp reads: storage, statistics and flag word of its own, no
+// timing event, no state word.
+int open_hessian(grape_handle *h, double *H) {
+    OpenCtx *o = h->open;
+    const auto t0 = std::chrono::steady_clock::now();
+    HIPCHK(h, hipSetDevice(h->device));
+    (void)hipGetLastError();
+    const int cb = open_hess_cols(h);
+    int ntraj = 0;
+    int rc = open_hess_reserve(h, cb, &ntraj);
+    if (rc) return rc;
+    auto &v = o->hess;
+    const size_t K = (size_t)h->K, L = (size_t)h->L, P = L * h->N_T, nblk = (P + cb - 1) / cb, pairs = L * (L + 1) / 2;
+    const int rows = open_hess_seed_rows(h);
+    hipStream_t s = h->stream;
+    LindHessArgs q{};
+    q.a = open_args(h);
+    q.a.f = o->d_out + 2 * K;   // sum_k w_k tau_k as the forward half reduced it (d_f belongs to the backward half)
+    q.a.ws = nullptr; q.a.tg = nullptr; q.a.stats = nullptr; q.a.rho = nullptr;
+    q.av = v.d_a; q.bv = v.d_b; q.th = v.d_th; q.T = v.d_T; q.Sd = v.d_Sd; q.strip = v.d_strip; q.stats = v.d_stats; q.cb = cb;
+    HessArgs a{};   // what hess_accumulate_kernel and hess_finish_kernel read: sizes, weights, functional, tau, f, T, Sd, strips
+    a.s.weights = o->d_weights; a.s.tau = (const double2 *)o->d_out; a.s.f = o->d_out + 2 * K;
+    a.s.K = h->K; a.s.K_total = h->K_total; a.s.L = h->L; a.s.N = h->N; a.s.N_T = h->N_T; a.s.functional = h->p.functional;
+    a.T = v.d_T; a.Sd = v.d_Sd; a.strip = v.d_strip; a.acc = v.d_acc; a.H = v.d_H;
+    std::vector<unsigned long long> st;
+    double terms[3] = {0., 0., 0.}, steps[3] = {0., 0., 0.};
+    bool taylor = false;
+    // the flag word sits behind the statistics of the launch
+    auto begin = [&](size_t nwg) {
+        q.a.flags = (int *)(v.d_stats + 2 * nwg);
+        return hipMemsetAsync(v.d_stats, 0, (2 * nwg + 1) * 8, s);
+    };
+    auto collect = [&](size_t nwg, int which) -> int {
+        st.assign(2 * nwg + 1, 0ull);
+        HIPCHK(h, hipMemcpyAsync(st.data(), v.d_stats, (2 * nwg + 1) * 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(h, hipStreamSynchronize(s));
+        for (size_t w = 0; w < nwg; ++w) { terms[which] += (double)st[2 * w]; steps[which] += (double)st[2 * w + 1]; }
+        if ((int)(st[2 * nwg] & 0xffffffffull) & 16) taylor = true;
+        return (int)GRAPE_OK;
+    };
+    {   // forward seeds
+        const size_t nwg = K * (size_t)rows * L;
+        HIPCHK(h, begin(nwg));
+        q.ws = v.d_wsseed;
+        OPEN_LAUNCH(lind_hess_forward_seeds_kernel, dim3((unsigned)K, (unsigned)rows, (unsigned)L), OPEN_FWD_THREADS, q)
+        HIPCHK(h, hipGetLastError());
+        if ((rc = collect(nwg, 0))) return rc;
+    }
+    if (!taylor) {   // the bare target chain (counted with the backward seeds)
+        HIPCHK(h, begin(K));
+        OPEN_LAUNCH(lind_hess_theta_kernel, dim3((unsigned)K), OPEN_FWD_THREADS, q)
+        HIPCHK(h, hipGetLastError());
+        if ((rc = collect(K, 1))) return rc;
+    }
+    if (!taylor) {   // backward seeds
+        const int brows = open_hess_back_rows(h);
+        const size_t nwg = K * pairs * (size_t)brows;
+        HIPCHK(h, begin(nwg));
+        OPEN_LAUNCH(lind_hess_backward_seeds_kernel, dim3((unsigned)K, (unsigned)pairs, (unsigned)brows), OPEN_BWD_THREADS, q)
+        HIPCHK(h, hipGetLastError());
+        if ((rc = collect(nwg, 1))) return rc;
+    }
+    if (!taylor) HIPCHK(h, hipMemsetAsync(v.d_acc, 0, P * P * 8, s));
+    const unsigned eblocks = (unsigned)((P * P + 255) / 256);
+    for (int k0 = 0; k0 < h->K && !taylor; k0 += ntraj) {   // the fan, pass by pass
+        const int ng = std::min(ntraj, h->K - k0);
+        const size_t nwg = (size_t)ng * nblk;
+        HIPCHK(h, begin(nwg));
+        q.ws = v.d_wsfan; q.k0 = k0;
+        OPEN_LAUNCH(lind_hess_fan_kernel, dim3((unsigned)nblk, (unsigned)ng), OPEN_FWD_THREADS, q)
+        hipLaunchKernelGGL(hess_accumulate_kernel, dim3(eblocks), dim3(256), 0, s, a, ng);
+        HIPCHK(h, hipGetLastError());
+        if ((rc = collect(nwg, 2))) return rc;
+    }
+    if (taylor) {
+        h->err = "grape_open_hessian: a series did not converge within 200 terms";
+        return GRAPE_ERR_TAYLOR;
+    }
+    hipLaunchKernelGGL(hess_finish_kernel, dim3(eblocks), dim3(256), 0, s, a);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipMemcpyAsync(H, v.d_H, P * P * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipStreamSynchronize(s));
+    v.info[0] = terms[0] + terms[1] + terms[2]; v.info[1] = steps[0] + steps[1] + steps[2]; v.info[2] = (double)ntraj;
+    v.info[3] = (double)v.store.mem.bytes();
+    v.info[4] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    v.info[5] = terms[0]; v.info[6] = terms[1]; v.info[7] = terms[2];
+    v.info[8] = steps[0]; v.info[9] = steps[1]; v.info[10] = steps[2]; v.info[11] = (double)cb;
+    return GRAPE_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int grape_open_hessian(grape_handle *h, double *H) try {
+    if (!h) { g_create_error = "grape_open_hessian: h == NULL"; return GRAPE_ERR_INVALID; }
+    if (!H) { h->err = "grape_open_hessian: H must not be NULL"; return GRAPE_ERR_INVALID; }
+    if (const char *why = open_hess_refusal(h)) { h->err = std::string("grape_open_hessian: ") + why; return GRAPE_ERR_INVALID; }
+    return open_hessian(h, H);
+}
+GRAPE_BARRIER(h ? &h->err : &g_create_error)
+
+int grape_get_open_hessian_info(grape_handle *h, double *out, int n) try {
+    if (!h || !out || !h->open) return GRAPE_ERR_INVALID;
+    return copy_info(h->open->hess.info, 12, out, n);
 }
 GRAPE_BARRIER(h ? &h->err : &g_create_error)
 

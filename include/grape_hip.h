@@ -503,6 +503,49 @@ int grape_hessian(grape_handle *h, double *H);
  * ([0] = [5] + [6] + [7]).  Returns the number of entries written (at most n). */
 int grape_get_hessian_info(grape_handle *h, double *out, int n);
 
+/* grape_hessian for a handle made by grape_create_open (entry points only: the ABI version stays 7, grape_problem and
+ * grape_lindblad are untouched; csrc/grape_lindblad_hessian.hip.h):
+ *   H[p][q] = d^2 J / d eps_p d eps_q,  p, q < P = L*N_T, indexed as G (p = l*N_T + n), at the pulses of the last evaluation;
+ *   H: [P][P] doubles, the full symmetric matrix (both triangles, bitwise symmetric).
+ * J is the handle's built-in functional (J_T_sm / ss / re with weights, K == K_total).  Column q is what grape_open_hvp returns
+ * for the unit direction e_q, to rounding -- without its two full sweeps and its four-chain backward recursion per control
+ * and direction: the first derivatives of every interval are formed once (forward from the stored rho_k(t_n), backward
+ * from the bare targets sigma_k), every forward derivative is carried on from the interval where it is born and overlapped
+ * at every later grid point, the diagonal blocks come from the second-order chain of the backward seeds, the coupling of the
+ * trajectories through f from a closed boundary term.  Hermitian and general drift, per-trajectory control and collapse
+ * operators, shape functions, non-uniform grids and weights are all inside; d <= 64, J <= 8 as the handle itself.
+ *   - Valid exactly when grape_open_hvp is valid: after a successful forward half on the current time grid.  It reads only
+ *     the stored rho_k(t_n), tau, f, the device copy of the pulses and the static data of the handle.
+ *   - The storage is the handle's, allocated by the first call and freed by grape_destroy: 2 K N_T L matrices (2 NP^2
+ *     doubles each) of first derivatives, K (N_T+1) of the bare target chain, two P x P matrices, seed workspaces (up to
+ *     about 512 (14 + 4J) matrices), and 8 P^2 bytes plus fan workspaces per
+ *     trajectory of a pass.  The trajectories are taken in passes under the memory budget of grape_open_hvp (8 GB, half of
+ *     the free memory; GRAPE_OPEN_HESS_TRAJ=<n>, read by grape_create_open, sets the pass size) and summed one after the
+ *     other in ascending k: the result does not depend on the passes, bit for bit.  GRAPE_OPEN_HESS_COLS=<n> (1 ... 16, read
+ *     by grape_create_open) sets how many columns one workgroup of the fan carries; a column's bits do not depend on it.
+ *     Two calls give the same bits.
+ *   - The call runs on the handle's stream and leaves alone the storage of grape_open_hvp and its halves, the validity
+ *     words, the statistics and the timings of the evaluation: grape_eval, grape_get_tau_grads, grape_open_time_gradient,
+ *     grape_open_hvp and grape_expect return the bits they returned before, a pending grape_open_hvp_backward still answers.
+ *   - Series as grape_open_hvp: m = ceil(beta_n dt_n / theta) sub-steps, a series stops when every chain has
+ *     ||term||_F <= prop_tolerance ||sum||_F, after at most 200 terms -- beyond that GRAPE_ERR_TAYLOR, the handle stays usable.
+ *   - GRAPE_ERR_INVALID with a message that begins "grape_open_hessian:" and names the reason, before anything touches the
+ *     device, the handle stays usable: h == NULL (message through grape_last_error(NULL)), H == NULL; a closed handle
+ *     (grape_hessian is the call); L > 4 (grape_open_hvp with unit directions is the route); L*N_T > 8192; a split-phase
+ *     shard (K < K_total); a handle without targets; a running cost set by grape_open_set_running_cost; no valid forward
+ *     state, with the distinctions of grape_open_hvp (no evaluation yet, the last forward sweep failed, grape_set_tlist or
+ *     grape_open_set_running_cost came since, the last call was grape_eval_batch).
+ *   - GRAPE_ERR_HIP with the sizes in the message when the storage cannot be allocated (even for one trajectory per pass);
+ *     nothing stays allocated then. */
+int grape_open_hessian(grape_handle *h, double *H);
+
+/* What the last grape_open_hessian of this handle did: [0] series terms and [1] (sub-)steps summed over all workgroups of
+ * the call;  [2] trajectories per pass;  [3] bytes of Hessian storage the handle holds;  [4] milliseconds of the last call
+ * (host wall time, copies included);  [5] / [6] / [7] the series terms and [8] / [9] / [10] the (sub-)steps of the forward
+ * seeds / the backward seeds / the fan;  [11] columns per workgroup of the fan.  Returns the number of entries written (at
+ * most n), GRAPE_ERR_INVALID on a closed handle. */
+int grape_get_open_hessian_info(grape_handle *h, double *out, int n);
+
 /* grape_hvp in two halves, cut at its one cross-trajectory dependency (entry points only, the ABI version stays 7;
  * csrc/grape_hvp_split.hip.h).  What grape_hvp refuses -- a trajectory shard (K < K_total) and a caller's
  * functional, handles without targets included -- goes through these, as the gradient goes through grape_forward +

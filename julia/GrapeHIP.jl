@@ -671,6 +671,35 @@ function open_hvp_info(h::Handle)
 end
 
 """
+    open_hessian!(H, h)
+
+The exact Hessian of `J` at the pulses of the last evaluation of a handle made by `create_open`, as a matrix
+(grape_open_hessian): `H` is `L*N_T × L*N_T`, indexed like the gradient, both triangles, bitwise symmetric.  Column `q` is what
+`open_hvp!` gives for the unit direction `e_q`, to rounding.  Valid whenever `open_hvp!` is, for `L ≤ 4` and `L*N_T ≤ 8192`.
+"""
+function open_hessian!(H::Matrix{Float64}, h::Handle)
+    isempty(h.fixed) || error("GrapeHIP.open_hessian!: handles with pseudo-controls are not supported (the matrix has no entries for them)")
+    size(H) == (h.L * h.N_T, h.L * h.N_T) || throw(DimensionMismatch("H must be L*N_T × L*N_T = $(h.L * h.N_T) × $(h.L * h.N_T)"))
+    check(h, GC.@preserve H ccall((:grape_open_hessian, libgrape), Cint, (Ptr{Cvoid}, Ptr{Float64}), h.ptr, H))
+    return H
+end
+
+"""
+    open_hessian_info(h)
+
+What the last `open_hessian!` did (grape_get_open_hessian_info): series `terms` and (sub-)`steps` summed over all workgroups,
+trajectories per pass, `bytes` of storage held by the handle, milliseconds of the call, and terms and steps of the forward
+seeds, the backward seeds and the fan, and the columns per workgroup of the fan.
+"""
+function open_hessian_info(h::Handle)
+    out = zeros(Float64, 12)
+    GC.@preserve out ccall((:grape_get_open_hessian_info, libgrape), Cint, (Ptr{Cvoid}, Ptr{Float64}, Cint), h.ptr, out, 12)
+    return (terms = Int(out[1]), steps = Int(out[2]), traj_per_pass = Int(out[3]), bytes = Int(out[4]), ms = out[5],
+            terms_forward_seeds = Int(out[6]), terms_backward_seeds = Int(out[7]), terms_fan = Int(out[8]),
+            steps_forward_seeds = Int(out[9]), steps_backward_seeds = Int(out[10]), steps_fan = Int(out[11]), fan_columns = Int(out[12]))
+end
+
+"""
     open_hvp_forward!(h, V; dtau=nothing, dsums=nothing, drhoT=nothing)
 
 First half of a split Hessian-vector product on a handle made by `create_open` (grape_open_hvp_forward): the tangent forward
