@@ -64,7 +64,14 @@ CASES = {
     "N49-L2-re": dict(N=49, L=2, K=2, f=2, nv=1),
     "N64-L2-sm-herm": dict(N=64, L=2, K=2, f=0, nv=1),
     "N64-L7-ss-general": dict(N=64, L=7, K=1, f=1, herm=False, amp=1.0, nv=1),
+    # L = 8 with more than one wave: 2 + 2 L = 18 chains take two 16-column tiles (hvp_backward_kernel<NP, 2>), NW = NP / 16
+    "N17-L8-sm-K2-shape": dict(N=17, L=8, K=2, f=0, amp=1.0, shape=True, weights=True, nonuniform=True, nv=1),   # NP 32, padded
+    "N48-L8-ss-general": dict(N=48, L=8, K=1, f=1, amp=1.0, herm=False, nv=1),                                   # NP 48, full
+    "N64-L8-re-pertraj": dict(N=64, L=8, K=2, f=2, amp=1.0, per_traj=True, nv=1),                                # NP 64
+    # every interval is cut: all eighteen chains carry from one sub-step to the next across both tiles
+    "N33-L8-ss-long": dict(N=33, L=8, K=1, f=1, amp=1.0, dt=4.0, nv=1),
 }
+LONG_INTERVALS = ("N48-L1-ss-K1-long-interval", "N33-L8-ss-long")
 _cache = {}
 
 
@@ -81,6 +88,17 @@ def case(name):
     return _cache[name]
 
 
+def assert_second_tile_agrees(got, want, L, label=""):
+    """L = 8: the chains p'_6, p'_7 live in the second column tile of the backward kernel, and only the rows of H v that belong
+    to the controls 6 and 7 depend on it.  Those rows by themselves, scaled by their own maximum -- which the reference alone must
+    put at 1e-3 or more, so that the bound is relative there too.  Nothing to do below L = 8 (one tile)."""
+    if L < 8:
+        return None
+    rows = lambda a: np.asarray(a, dtype=float).reshape(-1, L, N_T)[:, 6:8]   # noqa: E731 -- control-major [l * N_T + n]
+    assert np.abs(rows(want)).max() >= 1e-3, float(np.abs(rows(want)).max())
+    return hr.assert_hvp_agrees(rows(got), rows(want), label + " rows of the controls 6, 7")
+
+
 @pytest.mark.parametrize("name", list(CASES))
 def test_hvp_against_the_reference(name):
     pr, f, V, want = case(name)
@@ -91,9 +109,10 @@ def test_hvp_against_the_reference(name):
         info = h.hvp_info()
     assert abs(J - want["J"]) <= 1e-12 and np.abs(G - want["G"]).max() <= hr.tol_hv(want["G"])
     hr.assert_hvp_agrees(Hv, want["Hv"], name)
+    assert (assert_second_tile_agrees(Hv, want["Hv"], pr["L"], name) is not None) == (pr["L"] == 8)
     print(info)
     steps = 2 * pr["K"] * len(V) * N_T
-    if name == "N48-L1-ss-K1-long-interval":
+    if name in LONG_INTERVALS:
         # beta_n dt_n / theta: the norm estimate of the generator is ~ 1 (GUE scaled to spectral radius ~ 1) plus the control,
         # every interval is 4 long and theta = 3, so every interval is cut at least once
         assert info["series_steps"] >= 2 * steps, info
@@ -159,6 +178,37 @@ def test_symmetry_on_the_device():
         Hv = h.hvp(V)
     a, b = float(V[0] @ Hv[1]), float(V[1] @ Hv[0])
     print(dict(vHw=a, wHv=b))
+    assert abs(a - b) <= 1e-10 * max(abs(a), abs(b))
+
+
+def test_two_tile_directions_do_not_see_each_other(monkeypatch):
+    """L = 8 at NP = 32: three directions in one launch group and in three groups of one, bit for bit -- a direction does not
+    depend on its launch group when its chains take two column tiles"""
+    pr, f, _, _ = case("N17-L8-sm-K2-shape")
+    V = hr.directions(79, 3, pr["L"] * N_T)
+    with handle(pr, f) as h:
+        h.eval(pr["pulsevals"])
+        all3 = h.hvp(V)
+        assert h.hvp_info()["dirs_per_group"] == 3
+    monkeypatch.setenv("GRAPE_HVP_DIRS", "1")
+    with handle(pr, f) as h:
+        h.eval(pr["pulsevals"])
+        one_by_one = h.hvp(V)
+        assert h.hvp_info()["dirs_per_group"] == 1
+    assert np.abs(all3.reshape(3, pr["L"], N_T)[:, 6:8]).max() >= 1e-3
+    assert np.array_equal(all3, one_by_one)
+
+
+def test_two_tile_symmetry_on_the_device():
+    """v.(H w) = w.(H v) at L = 8, NP = 48: both sides mix rows of tile 0 with the rows of the controls 6 and 7 (tile 1)"""
+    pr, f, _, _ = case("N48-L8-ss-general")
+    V = hr.directions(78, 2, pr["L"] * N_T)
+    with handle(pr, f) as h:
+        h.eval(pr["pulsevals"])
+        Hv = h.hvp(V)
+    a, b = float(V[0] @ Hv[1]), float(V[1] @ Hv[0])
+    tile1 = [float(V[i].reshape(pr["L"], N_T)[6:8].ravel() @ Hv[1 - i].reshape(pr["L"], N_T)[6:8].ravel()) for i in (0, 1)]
+    print(dict(vHw=a, wHv=b, of_which_tile_1=tile1))
     assert abs(a - b) <= 1e-10 * max(abs(a), abs(b))
 
 

@@ -42,7 +42,8 @@ def builtin_reference(name):
     return _cache[("builtin", name)]
 
 
-@pytest.mark.parametrize("name", ["N3-L1-sm", "N16-L8-ss", "N16-L2-re", "N33-L2-sm-general-skewed"])
+@pytest.mark.parametrize("name", ["N3-L1-sm", "N16-L8-ss", "N16-L2-re", "N33-L2-sm-general-skewed", "N17-L8-sm-K2-shape",
+                                  "N64-L8-re-pertraj"])
 def test_unsharded_halves_give_the_bits_of_hvp(name):
     pr, f, V, want = base.case(name)
     ref = builtin_reference(name)
@@ -55,6 +56,7 @@ def test_unsharded_halves_give_the_bits_of_hvp(name):
         halves = h.hvp_backward(f_of(h.sums()), dsums)
         info_bw = h.hvp_info()
     hr.assert_hvp_agrees(whole, want["Hv"], name)
+    base.assert_second_tile_agrees(halves, want["Hv"], pr["L"], name)
     assert np.array_equal(whole, halves)
     for tag, got, exp in (("dtau", dtau, ref["dtau"]), ("dpsiT", dpsiT, ref["dpsiT"]),
                           ("dsums", dsums, (ref["dtau"] * pr["weights"][None, :]).sum(axis=1))):
@@ -109,6 +111,8 @@ CHI = {
     "N16-L8": dict(N=16, L=8, K=2, amp=1.0),
     "N17-L3-K3-weights-shape-nonuniform-no-targets": dict(N=17, L=3, K=3, weights=True, shape=True, nonuniform=True, target=False),
     "N33-L2-general-skewed": dict(N=33, L=2, K=2, herm=False, skew=3),
+    # two column tiles on three waves: hvp_backward_chi_kernel<48, 2>
+    "N33-L8": dict(N=33, L=8, K=2, amp=1.0),
     "N48-L1-K1-long-interval": dict(N=48, L=1, K=1, dt=4.0),
     "N64-L2-no-targets": dict(N=64, L=2, K=2, nv=1, target=False),
 }
@@ -147,6 +151,7 @@ def test_callers_functional_against_the_reference(name):
         info = h.hvp_info()
     assert abs(got["J"] - want["J"]) <= 1e-12 and np.abs(got["G"] - want["G"]).max() <= hr.tol_hv(want["G"])
     hr.assert_hvp_agrees(got["Hv"], want["Hv"], name)
+    base.assert_second_tile_agrees(got["Hv"], want["Hv"], pr["L"], name)
     dev, bound = float(np.abs(got["dpsiT"] - want["dpsiT"]).max()), 1e-12 * max(1.0, float(np.abs(want["dpsiT"]).max()))
     print(name, dict(dpsiT_dev=dev, bound=bound), info)
     assert dev <= bound

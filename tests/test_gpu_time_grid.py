@@ -7,7 +7,8 @@ import pytest
 
 import grape_jl_amd as g
 from grape_jl_amd import synth
-from test_time_grid_host import central_dJdt, pseudo_control_dJdt, running_cost_weight_term
+from test_time_grid_host import (LONG_CASES, LONG_IDS, assert_every_block_has_signal, central_dJdt, intervals_per_workgroup,
+                                 long_case, padded_size, pseudo_control_dJdt, running_cost_weight_term)
 
 pytestmark = pytest.mark.gpu
 
@@ -101,6 +102,141 @@ def test_against_the_oracle(ref, monkeypatch, case):
         assert wk["asm_kernel"] == 1 and wk["walk_steps"] > 0, wk
     if cid == "n16-scan":
         assert wk["scan_block"] > 0, wk
+
+
+# ---- beyond the first workgroup of time_grad_kernel -------------------------------------------------------------------------
+# A workgroup owns CW = intervals_per_workgroup(NP) intervals (64 / 32 / 16); every case above stays inside one.  LONG_CASES
+# (tests/test_time_grid_host.py, where the table is checked without a GPU) reaches n0 = blockIdx.x * CW > 0, the guarded tail of
+# the last block, the g_b read across a block boundary and the reduction over more than four groups of 16 intervals.
+
+def _report(label, got, ref_, tol=TOL):
+    """deviation / tolerance of ``_close``, printed before it asserts"""
+    scale = max(np.abs(ref_).max(), 1e-3)
+    print(label, dict(ratio=float(np.abs(got - ref_).max() / (tol * scale)), scale=float(scale)))
+    _close(got, ref_, tol)
+
+
+def _long_handle(ref, cid, **kw):
+    _, N, L, K, N_T, fn, herm, blocks = LONG_CASES[LONG_IDS.index(cid)]
+    pr, tl, w, want = long_case(ref, cid)
+    CW = intervals_per_workgroup(padded_size(N))
+    assert -(-N_T // CW) == blocks, (N_T, CW)
+    assert_every_block_has_signal(want, CW, cid)
+    return g.GrapeHip(pr["H0"], pr["Hc"], tl, pr["psi0"], pr["target"], w, functional=fn, **kw), pr, want
+
+
+@pytest.mark.parametrize("cid", LONG_IDS)
+def test_long_grids_against_the_oracle(ref, cid):
+    h, pr, want = _long_handle(ref, cid)
+    with h:
+        h.eval(pr["pulsevals"])
+        d = h.time_gradient()
+        wk = h.work()
+    _report(cid, d, want)
+    if cid.startswith("n64-"):
+        assert wk["asm_kernel"] == 1, wk   # the headline route
+
+
+@pytest.mark.parametrize("fused", [True, False], ids=["as-created-z", "sequential-rho"])
+@pytest.mark.parametrize("cid", ["n16-one-column-over", "n64-three-blocks"])
+def test_long_grids_in_both_backward_layouts(ref, cid, fused):
+    """The two arms of the kernel's epilogue: after the concurrent sweeps the backward storage holds the unit states and the
+    factor is z_k; after sequential sweeps it holds the true ones and the factor is rho_k."""
+    h, pr, want = _long_handle(ref, cid)
+    with h:
+        if not fused:
+            assert h.set_fused_sweeps(False) is False
+        h.eval(pr["pulsevals"])
+        d = h.time_gradient()
+        wk = h.work()
+        # (what the handle reports as active is what grape_eval ran: a handle as created has the switch on)
+        assert h.set_fused_sweeps(fused) is fused
+    print(cid, dict(fused=fused, scan_block=wk["scan_block"]))
+    _report(f"{cid} fused={fused}", d, want)
+    # 64 time steps and more, few trajectories: both layouts are written by the scanned sweeps
+    assert wk["scan_block"] > 0, wk
+
+
+def test_long_grid_running_cost_across_a_block_boundary(ref):
+    """g_b(t_n) + g_b(t_{n+1}) at n = 63 reads the last point of block 0 and the first of block 1; n = 64 is block 1 alone"""
+    N, L, K, N_T, lam = 16, 2, 2, 65, 0.3
+    pr = synth.make_problem(N, L, N_T, K, seed=9)
+    tl = _nonuniform(N_T, seed=11)
+    D = _dpen(N)
+    args = (pr["H0"], pr["Hc"], tl, pr["pulsevals"], pr["psi0"], pr["target"])
+    weight = running_cost_weight_term(ref, pr["H0"], pr["Hc"], tl, pr["pulsevals"], pr["psi0"], D, lam)
+    want = pseudo_control_dJdt(ref, *args, D=D, lambda_b=lam) + weight
+    print(dict(weight_63=float(weight[63]), weight_64=float(weight[64])))
+    assert abs(weight[63]) >= 1e-3 and abs(weight[64]) >= 1e-3
+    assert_every_block_has_signal(want, intervals_per_workgroup(padded_size(N)), "running cost")
+    with g.GrapeHip(pr["H0"], pr["Hc"], tl, pr["psi0"], pr["target"], D=D, lambda_b=lam) as h:
+        h.eval(pr["pulsevals"])
+        d = h.time_gradient()
+    _report("running cost, N_T = 65", d, want)
+
+
+def test_long_grid_with_shape_and_per_trajectory_controls(ref):
+    """n16-one-column-over with a shape and H_l per trajectory against the library's own pseudo-control route (the identity of
+    test_shapes_against_the_pseudo_control_route_and_differences, without its differences)"""
+    cid = "n16-one-column-over"
+    _, N, L, K, N_T, fn, _, _ = LONG_CASES[LONG_IDS.index(cid)]
+    pr, tl, w, _ = long_case(ref, cid)
+    Hc = np.stack([pr["Hc"] * (1.0 + 0.1 * k) for k in range(K)])
+    shape = 0.5 + synth.uniform01(23, L * N_T).reshape(L, N_T)
+    x = pr["pulsevals"]
+    with g.GrapeHip(pr["H0"], Hc, tl, pr["psi0"], pr["target"], w, functional=fn, shape=shape) as h:
+        h.eval(x)
+        d = h.time_gradient()
+    Hp = np.concatenate([pr["H0"][:, None], Hc], axis=1)
+    sp = np.concatenate([np.ones((1, N_T)), shape])
+    with g.GrapeHip(np.zeros_like(pr["H0"]), Hp, tl, pr["psi0"], pr["target"], w, functional=fn, shape=sp) as hp:
+        _, Gp, _ = hp.eval(np.concatenate([np.ones(N_T), x]))
+    Gp = Gp.reshape(L + 1, N_T)
+    want = (Gp[0] + np.sum(x.reshape(L, N_T) * Gp[1:], axis=0)) / np.diff(tl)
+    assert_every_block_has_signal(want, intervals_per_workgroup(padded_size(N)), "shape, per-trajectory controls")
+    _report("shape, per-trajectory controls, N_T = 65", d, want)
+
+
+def test_long_grid_sharding():
+    """n16-one-column-over with K = 4: two device shards behind one handle, and a 1 + 3 split-phase pair"""
+    cid = "n16-one-column-over"
+    _, N, L, _, N_T, fn, _, _ = LONG_CASES[LONG_IDS.index(cid)]
+    K = 4
+    pr = synth.make_problem(N, L, N_T, K, seed=31 + N)
+    tl = _nonuniform(N_T, seed=N)
+    w = np.linspace(0.5, 1.5, K)
+    x = pr["pulsevals"]
+    with g.GrapeHip(pr["H0"], pr["Hc"], tl, pr["psi0"], pr["target"], w, functional=fn) as h:
+        h.eval(x)
+        d1 = h.time_gradient()
+    assert np.abs(d1[:64]).max() >= 1e-3 and abs(d1[64]) >= 1e-3, d1
+    with g.GrapeHip(pr["H0"], pr["Hc"], tl, pr["psi0"], pr["target"], w, functional=fn, devices=[0, 0]) as h:
+        h.eval(x)
+        d2 = h.time_gradient()
+    _report("devices=[0, 0]", d2, d1, tol=1e-14)
+    parts, taus = [], []
+    for lo, hi in ((0, 1), (1, 4)):
+        sl = slice(lo, hi)
+        hs = g.GrapeHip(pr["H0"][sl], pr["Hc"], tl, pr["psi0"][sl], pr["target"][sl], w[sl], functional=fn, K_total=K)
+        taus.append((hs, hs.forward(x), hs.sums()))
+    f = sum(complex(s[0], s[1]) for _, _, s in taus)
+    for hs, _, _ in taus:
+        hs.backward(f)
+        parts.append(hs.time_gradient())
+        hs.close()
+    _report("1 + 3 split-phase", parts[0] + parts[1], d1, tol=1e-14)
+
+
+@pytest.mark.parametrize("cid", ["n16-one-column-over", "n64-three-blocks"])
+def test_long_grid_replay_gives_the_same_bits(ref, cid):
+    h, pr, want = _long_handle(ref, cid)
+    with h:
+        got = []
+        for _ in range(3):   # (N <= 64: the third evaluation replays the captured graph)
+            h.eval(pr["pulsevals"])
+            got.append(h.time_gradient())
+    _report(cid + ", first evaluation", got[0], want)
+    assert np.array_equal(got[2], got[0])
 
 
 def test_gate_problem_with_generator_classes(ref):

@@ -196,6 +196,85 @@ def test_pseudo_control_identity_with_running_cost(ref):
     assert np.abs(prop + expl - fd).max() <= 1e-8 * max(np.abs(fd).max(), 1e-3)
 
 
+def intervals_per_workgroup(NP):
+    """CW = 16 nct of time_grad_kernel: `const int nct = h->NP <= 64 ? 4 : h->NP <= 128 ? 2 : 1;` in grape_get_time_gradient
+    (csrc/grape_hip.hip), restated.  LONG_CASES is chosen by it: the two move together."""
+    return 16 * (4 if NP <= 64 else 2 if NP <= 128 else 1)
+
+
+def padded_size(N):
+    """NP of a handle with the default propagator (grape_create, csrc/grape_hip.hip): 16-wide tiles up to 64, then 128 / 256 / 512"""
+    return 16 * ((N + 15) // 16) if N <= 64 else 128 if N <= 128 else 256 if N <= 256 else 512
+
+
+# Time grids beyond the first workgroup of time_grad_kernel (the GPU side is tests/test_gpu_time_grid.py): n0 > 0, the guarded
+# tail of the last block, the g_b read and the reduction across block boundaries.
+LONG_CASES = [
+    # id, N, L, K, N_T, functional, hermitian, blocks = ceil(N_T / CW)
+    ("n16-one-full-block", 16, 2, 3, 64, 0, True, 1),      # CW = 64, exactly full: the boundary without a tail
+    ("n16-one-column-over", 16, 2, 3, 65, 1, True, 2),     # the last block holds one interval, 63 guarded columns
+    ("n33-three-blocks", 33, 2, 2, 130, 2, False, 3),      # NP = 48: padded rows, three of the four waves have a row tile
+    ("n64-one-column-over", 64, 2, 2, 65, 0, True, 2),     # the headline route (asm_kernel == 1)
+    ("n64-three-blocks", 64, 2, 2, 130, 1, True, 3),
+    ("n100-two-blocks", 100, 1, 2, 33, 0, True, 2),        # nct = 2, CW = 32, a tail of 1
+    ("n65-three-blocks", 65, 1, 2, 70, 2, False, 3),       # the smallest N padded to 128, a tail of 6
+    ("n130-two-blocks", 130, 1, 1, 17, 0, True, 2),        # nct = 1, CW = 16, a tail of 1
+    ("n129-three-blocks", 129, 1, 1, 35, 1, True, 3),      # a tail of 3
+]
+LONG_IDS = [c[0] for c in LONG_CASES]
+_long = {}
+
+
+def long_grid(N_T, seed):
+    """the non-uniform grid of the GPU tests (``_nonuniform`` of tests/test_gpu_time_grid.py)"""
+    u = synth.uniform01(seed, N_T)
+    return np.concatenate([[0.0], np.cumsum(0.3 + 0.4 * u)])
+
+
+def long_case(ref, cid):
+    """(problem, grid, weights, the oracle's dJ/d(dt_n)) of a LONG_CASES entry, built as test_against_the_oracle builds its
+    cases.  Computed once per session and shared; nobody writes to it."""
+    if cid not in _long:
+        _, N, L, K, N_T, fn, herm, _ = LONG_CASES[LONG_IDS.index(cid)]
+        pr = synth.make_problem(N, L, N_T, K, seed=31 + N, hermitian=herm)
+        tl = long_grid(N_T, seed=N)
+        w = np.linspace(0.5, 1.5, K)
+        want = pseudo_control_dJdt(ref, pr["H0"], pr["Hc"], tl, pr["pulsevals"], pr["psi0"], pr["target"], weights=w,
+                                   functional=fn)
+        want.setflags(write=False)
+        _long[cid] = (pr, tl, w, want)
+    return _long[cid]
+
+
+def assert_every_block_has_signal(want, CW, label=""):
+    """On the reference alone: every block of CW intervals reaches 1e-3, the floor of the bar.  An error confined to a later
+    block can then hide neither under the first block's scale nor under the floor."""
+    peaks = [float(np.abs(want[b:b + CW]).max()) for b in range(0, len(want), CW)]
+    print(label, dict(block_peaks=peaks, overall=float(np.abs(want).max())))
+    assert min(peaks) >= 1e-3, (label, peaks)
+    return peaks
+
+
+@pytest.mark.parametrize("cid", LONG_IDS)
+def test_long_cases_cross_blocks_and_every_block_has_signal(ref, cid):
+    _, N, L, K, N_T, fn, herm, blocks = LONG_CASES[LONG_IDS.index(cid)]
+    CW = intervals_per_workgroup(padded_size(N))
+    assert -(-N_T // CW) == blocks, (N_T, CW)
+    _, _, _, want = long_case(ref, cid)
+    assert want.shape == (N_T,) and np.all(np.isfinite(want))
+    assert len(assert_every_block_has_signal(want, CW, cid)) == blocks
+
+
+def test_the_block_rule_is_the_launch_code():
+    """intervals_per_workgroup and padded_size against the lines of csrc/grape_hip.hip they restate"""
+    src = open(os.path.join(ROOT, "grape.jl_amd", "csrc", "grape_hip.hip")).read()
+    assert "const int nct = h->NP <= 64 ? 4 : h->NP <= 128 ? 2 : 1;" in src
+    assert "const dim3 grid((unsigned)((N_T + 16 * nct - 1) / (16 * nct)), (unsigned)h->K);" in src
+    assert "h->NP = p->N <= 128 ? 128 : (p->N <= 256 ? 256 : 512)" in src
+    assert [intervals_per_workgroup(p) for p in (16, 48, 64, 128, 256, 512)] == [64, 64, 64, 32, 16, 16]
+    assert [padded_size(n) for n in (16, 17, 33, 64, 65, 128, 129, 256, 257)] == [16, 32, 48, 64, 128, 128, 256, 256, 512]
+
+
 class _FakeShard:
     """Split-phase stand-in with a fixed partial time gradient and a record of the grids it was given."""
 
