@@ -107,7 +107,7 @@ def build_asm(verbose: bool = False, workdir: str | None = None) -> str:
 def _sources():
     srcs = [os.path.join(_CSRC, f) for f in ("grape_hip.hip", "grape_t18.hip", "grape_kernels.hip.h", "grape_large.hip.h",
                                              "grape_series.hip.h", "grape_cheby.hip.h", "grape_t18.hip.h", "grape_t18_coeffs.h",
-                                             "grape_deriv3.hip.h", "grape_timegrad.hip.h", "grape_batch.hip.h", "grape_lindblad.hip.h", "grape_lindblad_tg.hip.h", "grape_hvp.hip.h", "grape_hvp_split.hip.h", "grape_hessian.hip.h", "grape_lindblad_hvp.hip.h", "grape_lindblad_hessian.hip.h", "grape_lindblad_hvp_split.hip.h", "grape_lindblad_batch.hip.h", "grape_lindblad_rc.hip.h", "grape_devmem.h", "grape_cert.hip.h", "grape_expect.hip.h", "grape_econ_coeffs.h", os.path.join("asm", "gen_t16.py"), os.path.join("asm", "gen_t16q.py"), os.path.join("asm", "gen_t16r.py"), os.path.join("asm", "gen_t16p.py"), os.path.join("asm", "gen_t18g.py"), os.path.join("asm", "gen_t18gp.py"), os.path.join("asm", "gen_d3.py"), os.path.join("asm", "gen_d3s.py"), os.path.join("asm", "gen_lg.py"), os.path.join("asm", "gen_d4.py"), os.path.join("asm", "gcn.py"))]
+                                             "grape_deriv3.hip.h", "grape_timegrad.hip.h", "grape_batch.hip.h", "grape_lindblad.hip.h", "grape_lindblad_tg.hip.h", "grape_hvp.hip.h", "grape_hvp_split.hip.h", "grape_hessian.hip.h", "grape_lindblad_hvp.hip.h", "grape_lindblad_hessian.hip.h", "grape_lindblad_hvp_split.hip.h", "grape_lindblad_batch.hip.h", "grape_lindblad_rc.hip.h", "grape_devmem.h", "grape_evalstate.h", "grape_cert.hip.h", "grape_expect.hip.h", "grape_econ_coeffs.h", os.path.join("asm", "gen_t16.py"), os.path.join("asm", "gen_t16q.py"), os.path.join("asm", "gen_t16r.py"), os.path.join("asm", "gen_t16p.py"), os.path.join("asm", "gen_t18g.py"), os.path.join("asm", "gen_t18gp.py"), os.path.join("asm", "gen_d3.py"), os.path.join("asm", "gen_d3s.py"), os.path.join("asm", "gen_lg.py"), os.path.join("asm", "gen_d4.py"), os.path.join("asm", "gcn.py"))]
     return srcs, os.path.join(_HERE, "..", "include", "grape_hip.h")
 
 

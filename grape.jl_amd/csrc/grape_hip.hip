@@ -25,6 +25,7 @@
 #include "grape_lindblad_batch.hip.h"
 #include "grape_lindblad_rc.hip.h"
 #include "grape_devmem.h"
+#include "grape_evalstate.h"
 #include "grape_cert.hip.h"
 #include "grape_expect.hip.h"
 
@@ -243,6 +244,9 @@ struct grape_handle {
     Phase ph[kRing][kPhases]{};
     long n_fwd = 0, n_bwd = 0;  // evaluations recorded since the last grape_reset_timings
     std::string err;
+    // have_forward gates the split-phase protocol (grape_backward*, grape_get_sums, grape_get_final_states, grape_get_storage,
+    // grape_open_backward_xi): "a forward half has been enqueued since the grid (open: or the cost) was set".  It stays outside
+    // `ev` below because it is coarser: a batch call and a failed closed evaluation leave it alone.
     bool have_forward = false, in_eval = false;
     double chi_min_norm = 1e-100, taylor_tol = 1e-16;
     int taylor_max_order = 100;
@@ -323,12 +327,10 @@ struct grape_handle {
     bool graph_fuse_on = true;     // the setting the graph was captured with
     bool graph_bw_unit = false, graph_z_valid = false, graph_credit = false;   // host-side state the captured calls leave behind
     long n_eval = 0;               // grape_eval calls on the single-wait path
-    // ABI v7, grape_get_time_gradient: what the stored states of the last evaluation can give.  0: no evaluation (or the
-    // last one failed, or the grid changed since), 1: functional only, 2: forward done, backward pending, 3: complete
-    int tg_state = 0;
-    bool tg_unit = false;          // ... d_bw holds the unit backward states (factor z_k instead of rho_k)
-    bool tg_xi_user = false;       // ... the running cost was the caller's (grape_backward_xi): no explicit weight term
-    bool graph_tg_unit = false;    // tg_unit of the captured evaluation
+    // what the stored states of the last evaluation are and can give (grape_evalstate.h): every handle has
+    // one -- the shards of a composite, whose own stays empty, and an open handle included
+    StoredEval ev;
+    bool graph_unit = false;       // ev.unit of the captured evaluation
     int graph_walk_fuse = 0;       // last_walk_fuse of the captured evaluation (grape_get_work[17] after a replay)
     double2 *d_tq = nullptr;       // [K][N_T] per-trajectory terms of dJ/d(dt_n) (allocated on first use)
     double *d_dJdt = nullptr;      // [N_T]
@@ -370,16 +372,12 @@ struct grape_handle {
     // share the tangent storage above; what only they need lives here, allocated by the first split call, so that a handle
     // which never makes one holds -- and reports -- what it held before.
     struct HvpSplit {
-        enum { NONE = 0, READY, EVAL, TLIST, BATCH, HVP, FAILED };
         DeviceBufs mem;
         int cap = 0;               // directions the extras hold
         double2 *d_chi = nullptr, *d_dchi = nullptr, *d_ztarget = nullptr;   // chi~ [K][NP] | chi~' [cap][K][NP] | zeros [K][N]
         double2 *d_dpsiT = nullptr;                                          // Psi~'(T) [cap][K][N], packed for the host
         double *d_ftot = nullptr, *d_dftot = nullptr, *d_psums = nullptr;     // f_total [2] | f'_total [cap][2] | partial sums [cap][2]
-        int state = NONE, nv = 0;  // what came since the last successful forward half, and its directions
-        double terms_fw = 0., steps_fw = 0.;
         std::vector<double> stage; // host staging of chi~, chi~'
-        void came(int what) { if (state != NONE) state = what; }
     } hvs;
     // grape_create_open (grape_lindblad.hip.h): the states are d x d density matrices under a Lindblad
     // generator.  Such a handle owns none of the buffers above: everything it holds hangs off this pointer, and the entry
@@ -387,10 +385,8 @@ struct grape_handle {
     OpenCtx *open = nullptr;
     // grape_expect (grape_expect.hip.h): observables on the stored forward states.  The operators on the device and
     // the result are buffers of its own -- allocated by the first call, grown on demand, freed by grape_destroy; nothing an
-    // evaluation, a getter or a derivative call uses is touched.  ex_state: whether the store of a closed single-device handle
-    // is that of one successful forward half on the current grid (an open handle asks OpenCtx::hv_state, a composite its shards).
+    // evaluation, a getter or a derivative call uses is touched.
     struct ExpectStore {
-        enum { NONE = 0, READY, FAILED, TLIST, BATCH };
         DeviceBufs mem;
         double *d_ops = nullptr;
         double2 *d_res = nullptr;
@@ -398,7 +394,6 @@ struct grape_handle {
         std::vector<double> stage;          // the operators in the device layout
         double info[4] = {0., 0., 0., 0.};  // grape_get_expect_info
     } ex;
-    int ex_state = ExpectStore::NONE;
 };
 
 namespace {
@@ -1589,20 +1584,12 @@ struct OpenCtx {
     long n_fwd = 0, n_bwd = 0;
     std::vector<double> out;      // host copy of tau [2K] | sums [8] of the last forward sweep
     std::vector<double> stage;    // host staging of matrices in the device layout
-    bool have_bwd = false;
-    // grape_open_time_gradient (grape_lindblad_tg.hip.h): what the stored states and the boundary data on the
-    // device can give.  Validity is a flag of its own (have_bwd belongs to grape_get_tau_grads).
-    enum { TG_NONE, TG_NO_GRADIENT, TG_FORWARD_ONLY, TG_READY, TG_FAILED, TG_NEW_GRID, TG_BATCH, TG_NEW_COST, TG_RUNNING_COST };
-    int tg_state = TG_NONE;
-    bool tg_chi_user = false;     // ... the last backward half took the caller's chi_k(T) (still in d_chi)
+    // grape_open_time_gradient (grape_lindblad_tg.hip.h)
     size_t ws_mats = 0;           // matrices (2 NP^2 doubles) d_ws holds
     double2 *d_tq = nullptr;      // [K][N_T] per-trajectory terms of dJ/d(dt_n) (allocated on first use)
     double *d_dJdt = nullptr;     // [N_T]
-    // grape_open_hvp (grape_lindblad_hvp.hip.h): Hessian-vector products on the stored rho_k(t_n).  Validity is a
-    // word of its own: tg_state asks for a backward half, this call needs the forward half alone.  The storage is allocated
-    // by the first call and grows with the directions of a launch group.
-    enum { HV_NONE, HV_READY, HV_FAILED, HV_NEW_GRID, HV_BATCH, HV_NEW_COST };
-    int hv_state = HV_NONE;
+    // grape_open_hvp (grape_lindblad_hvp.hip.h): Hessian-vector products on the stored rho_k(t_n).  The storage
+    // is allocated by the first call and grows with the directions of a launch group.
     struct HvpStore {
         GroupStore store;         // units: directions; env: GRAPE_HVP_DIRS
         double *d_hvV = nullptr, *d_hvws = nullptr, *d_hvds = nullptr, *d_hvout = nullptr;
@@ -1614,16 +1601,12 @@ struct OpenCtx {
     // DESIGN.md 22): the two halves share the tangent storage above; what only they need lives here, allocated by the first
     // split call, so that a handle which never makes one holds -- and reports -- what it held before.
     struct HvpSplit {
-        enum { NONE = 0, READY, EVAL, TLIST, BATCH, COST, HVP, FAILED };
         DeviceBufs mem;
         int cap = 0;               // directions the extras hold
         double *d_chi = nullptr, *d_dchi = nullptr, *d_ztarget = nullptr;   // chi [K] | chi' [cap][K] | zeros [K] matrices (2 NP^2 doubles)
         double *d_drhoT = nullptr;                                          // rho'(T) [cap][K] matrices, packed for the host
         double *d_ftot = nullptr, *d_dftot = nullptr, *d_psums = nullptr;   // f_total [2] | f'_total [cap][2] | partial sums [cap][2]
-        int state = NONE, nv = 0;  // what came since the last successful forward half, and its directions
-        double terms_fw = 0., steps_fw = 0.;
         std::vector<double> stage; // host staging of chi, chi', rho'(T)
-        void came(int what) { if (state != NONE) state = what; }
     } hvs;
     // grape_open_eval_batch (grape_lindblad_batch.hip.h): every per-set buffer belongs to the call -- pulses, stored
     // states, workspaces, tau | sums, ||chi||, tau_grads, G, flags, statistics.  Allocated by the first call, grows with the sets
@@ -1758,10 +1741,7 @@ int open_forward(grape_handle *h, const double *pulsevals, double *tau) {
     (void)hipGetLastError();   // see grape_forward_device
     const size_t nl = (size_t)h->L * h->N_T, K = (size_t)h->K;
     h->have_forward = false;
-    o->have_bwd = false;
-    o->tg_state = OpenCtx::TG_FAILED;   // (until this sweep has succeeded)
-    o->hv_state = OpenCtx::HV_FAILED;
-    o->hvs.came(OpenCtx::HvpSplit::EVAL);
+    h->ev.forward_begun();   // (failed until this sweep has succeeded)
     HIPCHK(h, hipMemcpyAsync(o->d_eps, pulsevals, nl * 8, hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemsetAsync(o->d_flags, 0, 8 * sizeof(int), h->stream));
     HIPCHK(h, hipMemsetAsync(o->d_stats, 0, 2 * (K + K * h->L) * sizeof(unsigned long long), h->stream));
@@ -1789,8 +1769,7 @@ int open_forward(grape_handle *h, const double *pulsevals, double *tau) {
     const int rc = open_status(h, flags[0]);
     if (rc) return rc;
     h->have_forward = true;
-    o->tg_state = OpenCtx::TG_FORWARD_ONLY;
-    o->hv_state = OpenCtx::HV_READY;
+    h->ev.forward_succeeded();
     if (tau) memcpy(tau, o->out.data(), 2 * K * 8);
     return GRAPE_OK;
 }
@@ -1803,8 +1782,7 @@ int open_backward(grape_handle *h, const double f_total[2], const double *chi, d
     HIPCHK(h, hipSetDevice(h->device));
     (void)hipGetLastError();
     const size_t nl = (size_t)h->L * h->N_T, K = (size_t)h->K, np2 = (size_t)h->NP * h->NP;
-    o->have_bwd = false;
-    o->tg_state = OpenCtx::TG_FAILED;   // (until this half has succeeded)
+    h->ev.backward_failed();   // (until this half has succeeded)
     LindArgs a = open_args(h);
     if (chi) {
         if (!o->d_chi) HIPCHK(h, open_alloc(o, &o->d_chi, K * 2 * np2));
@@ -1839,8 +1817,7 @@ int open_backward(grape_handle *h, const double f_total[2], const double *chi, d
     if (hipEventElapsedTime(&ms, o->ev[0], o->ev[1]) == hipSuccess) { o->ms_bwd += ms; o->n_bwd++; }
     const int rc = open_status(h, flags[0]);
     if (rc) return rc;
-    o->have_bwd = true;
-    o->tg_state = with_cost ? OpenCtx::TG_RUNNING_COST : OpenCtx::TG_READY; o->tg_chi_user = chi != nullptr;
+    h->ev.backward_succeeded(false, with_cost, chi != nullptr);
     return GRAPE_OK;
 }
 
@@ -1866,7 +1843,7 @@ int open_eval(grape_handle *h, const double *pulsevals, double *J, double *G, do
         rc = open_backward(h, f, nullptr, G);
         if (rc) return rc;
     } else {
-        h->open->tg_state = OpenCtx::TG_NO_GRADIENT;
+        h->ev.no_gradient();
     }
     if (psiT) return open_final_states(h, psiT);
     return GRAPE_OK;
@@ -1938,14 +1915,9 @@ int open_set_tlist(grape_handle *h, const double *tlist) {
     o->tlist.assign(tlist, tlist + h->N_T + 1);
     if (o->d_wq) { const int rc = open_upload_wq(h); if (rc) return rc; }
     h->have_forward = false;
-    o->have_bwd = false;
-    o->tg_state = OpenCtx::TG_NEW_GRID;
-    o->hv_state = OpenCtx::HV_NEW_GRID;
-    o->hvs.came(OpenCtx::HvpSplit::TLIST);
+    h->ev.new_grid();
     return GRAPE_OK;
 }
-
-#define OPEN_TG_REFUSE(text) do { h->err = "grape_open_time_gradient: " text; return GRAPE_ERR_INVALID; } while (0)
 
 // dJdt[n] = -2 Re sum_k <<L_kn^dagger chi_k(t_{n+1}) | rho_k(t_{n+1})>> from the stored states and the boundary data of the last
 // backward half (grape_lindblad_tg.hip.h).  Touches nothing an evaluation or a getter reads: terms and result are buffers of
@@ -1953,27 +1925,17 @@ int open_set_tlist(grape_handle *h, const double *tlist) {
 // statistics are left alone.
 int open_time_gradient(grape_handle *h, double *dJdt) {
     OpenCtx *o = h->open;
-    switch (o->tg_state) {
-    case OpenCtx::TG_READY: break;
-    case OpenCtx::TG_NONE: OPEN_TG_REFUSE("no evaluation on this handle yet");
-    case OpenCtx::TG_NO_GRADIENT: OPEN_TG_REFUSE("the last evaluation had no gradient (grape_eval with G == NULL)");
-    case OpenCtx::TG_FORWARD_ONLY: OPEN_TG_REFUSE("called between grape_forward and the backward half");
-    case OpenCtx::TG_NEW_GRID: OPEN_TG_REFUSE("grape_set_tlist came after the last evaluation: the stored states belong to the previous grid");
-    case OpenCtx::TG_BATCH: OPEN_TG_REFUSE("the last call was grape_eval_batch: the stored states are not those of one defined evaluation");
-    case OpenCtx::TG_NEW_COST: OPEN_TG_REFUSE("grape_open_set_running_cost came after the last evaluation: its backward half belongs to the previous cost");
-    case OpenCtx::TG_RUNNING_COST: OPEN_TG_REFUSE("the last backward half carried a state running cost (grape_open_set_running_cost or "
-                                                  "grape_open_backward_xi): the time-gradient kernel does not carry the inhomogeneity");
-    default: OPEN_TG_REFUSE("the last evaluation failed");
-    }
+    const char *why = h->ev.gradient_stale();
     const size_t K = (size_t)h->K, N_T = (size_t)h->N_T;
-    if (K * (4 + (size_t)o->J) > o->ws_mats) OPEN_TG_REFUSE("internal: the workspace of this handle is smaller than K (4 + J) matrices");
+    if (!why && K * (4 + (size_t)o->J) > o->ws_mats) why = "internal: the workspace of this handle is smaller than K (4 + J) matrices";
+    if (why) { h->err = std::string("grape_open_time_gradient: ") + why; return GRAPE_ERR_INVALID; }
     HIPCHK(h, hipSetDevice(h->device));
     (void)hipGetLastError();
     if (!o->d_tq) HIPCHK(h, open_alloc(o, &o->d_tq, K * N_T));
     if (!o->d_dJdt) HIPCHK(h, open_alloc(o, &o->d_dJdt, N_T));
     LindArgs a = open_args(h);
     a.tg = o->d_tq;
-    a.chi_in = o->tg_chi_user ? o->d_chi : nullptr;
+    a.chi_in = h->ev.chi_user ? o->d_chi : nullptr;
     HIPCHK(h, hipMemsetAsync(o->d_flags, 0, 8 * sizeof(int), h->stream));
     OPEN_LAUNCH(lind_timegrad_kernel, dim3((unsigned)K), OPEN_FWD_THREADS, a)
     hipLaunchKernelGGL(grad_reduce_kernel, dim3((unsigned)((N_T + 15) / 16)), dim3(256), 0, h->stream, o->d_tq, h->K, (int)N_T, o->d_dJdt,
@@ -1987,6 +1949,11 @@ int open_time_gradient(grape_handle *h, double *dJdt) {
 }
 
 #define OPEN_HV_REFUSE(text) do { h->err = "grape_open_hvp: " text; return GRAPE_ERR_INVALID; } while (0)
+// the refusal of a call that needs the stored forward states; why: StoredEval::forward_stale
+int refuse_stale_forward(grape_handle *h, const char *call, const char *why) {
+    h->err = std::string(call) + ": no valid forward state: " + why;
+    return GRAPE_ERR_INVALID;
+}
 #define OPEN_HVF_THREADS(np) ((np) * (np) / 4)
 
 // bytes of storage one direction needs: the workspaces of its K L backward workgroups (the K forward ones fit inside),
@@ -2018,15 +1985,8 @@ int open_hvp(grape_handle *h, int nv, const double *V, double *HV) {
     if (h->K != h->K_total) OPEN_HV_REFUSE("a split-phase shard (K < K_total) is out of scope: f' would need an all-reduce of its own");
     if (h->no_target) OPEN_HV_REFUSE("this handle has no target states (grape_problem.target == NULL): chi'(T) would be the caller's");
     if (o->rc_set) OPEN_HV_REFUSE("a state running cost is set on this handle (grape_open_set_running_cost): its second-order terms are not carried");
-    switch (o->hv_state) {
-    case OpenCtx::HV_READY: break;
-    case OpenCtx::HV_NONE: OPEN_HV_REFUSE("no valid forward state: no evaluation on this handle yet");
-    case OpenCtx::HV_NEW_GRID: OPEN_HV_REFUSE("no valid forward state: grape_set_tlist came after the last evaluation, the stored states belong to the previous grid");
-    case OpenCtx::HV_NEW_COST: OPEN_HV_REFUSE("no valid forward state: grape_open_set_running_cost came after the last evaluation");
-    case OpenCtx::HV_BATCH: OPEN_HV_REFUSE("no valid forward state: the last call was grape_eval_batch, the stored states are not those of one defined evaluation");
-    default: OPEN_HV_REFUSE("no valid forward state: the last forward sweep failed");
-    }
-    o->hvs.came(OpenCtx::HvpSplit::HVP);   // (the tangent storage of a forward half is overwritten)
+    if (const char *why = h->ev.forward_stale()) return refuse_stale_forward(h, "grape_open_hvp", why);
+    h->ev.tangent_overwritten();   // (the tangent storage of a forward half is overwritten)
     const auto t0 = std::chrono::steady_clock::now();
     HIPCHK(h, hipSetDevice(h->device));
     (void)hipGetLastError();
@@ -2155,16 +2115,7 @@ int open_hvs_stats(grape_handle *h, int nv, int which, double *terms, double *st
 int open_hvs_forward(grape_handle *h, int nv, const double *V, double *dtau, double *dsums, double *drhoT) {
     OpenCtx *o = h->open;
     OpenHvpSplit &x = o->hvs;
-    const char *why = nullptr;
-    switch (o->hv_state) {
-    case OpenCtx::HV_READY: break;
-    case OpenCtx::HV_NONE: why = "no evaluation on this handle yet"; break;
-    case OpenCtx::HV_NEW_GRID: why = "grape_set_tlist came after the last evaluation, the stored states belong to the previous grid"; break;
-    case OpenCtx::HV_NEW_COST: why = "grape_open_set_running_cost came after the last evaluation"; break;
-    case OpenCtx::HV_BATCH: why = "the last call was grape_eval_batch, the stored states are not those of one defined evaluation"; break;
-    default: why = "the last forward sweep failed"; break;
-    }
-    if (why) { h->err = std::string("grape_open_hvp_forward: no valid forward state: ") + why; return GRAPE_ERR_INVALID; }
+    if (const char *why = h->ev.forward_stale()) return refuse_stale_forward(h, "grape_open_hvp_forward", why);
     const auto t0 = std::chrono::steady_clock::now();
     HIPCHK(h, hipSetDevice(h->device));
     (void)hipGetLastError();
@@ -2178,7 +2129,7 @@ int open_hvs_forward(grape_handle *h, int nv, const double *V, double *dtau, dou
                  "groups of that size";
         return GRAPE_ERR_INVALID;
     }
-    x.state = OpenHvpSplit::FAILED;   // (until this half has succeeded: the tangent storage is being overwritten)
+    h->ev.split_forward_begun();   // (failed until this half has succeeded: the tangent storage is being overwritten)
     int rc = open_hvp_reserve(h, nv, &nd);
     if (rc) return rc;
     rc = open_hvs_reserve(h, nv);
@@ -2212,7 +2163,7 @@ int open_hvs_forward(grape_handle *h, int nv, const double *V, double *dtau, dou
         if (dtau) std::fill(dtau, dtau + 2 * (size_t)nv * K, nan);
         if (dsums) std::fill(dsums, dsums + 2 * (size_t)nv, nan);
     }
-    x.state = OpenHvpSplit::READY; x.nv = nv; x.terms_fw = terms; x.steps_fw = steps;
+    h->ev.split_forward_succeeded(nv, terms, steps);
     double *info = o->hv.info;
     info[0] = terms; info[1] = steps; info[2] = (double)nv; info[3] = (double)(o->hv.store.mem.bytes() + x.mem.bytes());
     info[4] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -2220,28 +2171,10 @@ int open_hvs_forward(grape_handle *h, int nv, const double *V, double *dtau, dou
     return GRAPE_OK;
 }
 
-// is there a forward half whose tangent states a backward half of nv directions may read?  (no HIP call)
-int open_hvs_ready(grape_handle *h, const char *call, int nv) {
-    const OpenHvpSplit &x = h->open->hvs;
-    const char *why = nullptr;
-    switch (x.state) {
-        case OpenHvpSplit::READY: break;
-        case OpenHvpSplit::NONE: why = "no grape_open_hvp_forward on this handle yet"; break;
-        case OpenHvpSplit::EVAL: why = "a forward evaluation came since the last grape_open_hvp_forward"; break;
-        case OpenHvpSplit::TLIST: why = "grape_set_tlist came since the last grape_open_hvp_forward"; break;
-        case OpenHvpSplit::BATCH: why = "grape_eval_batch came since the last grape_open_hvp_forward"; break;
-        case OpenHvpSplit::COST: why = "grape_open_set_running_cost came since the last grape_open_hvp_forward"; break;
-        case OpenHvpSplit::HVP:
-            why = "grape_open_hvp came since the last grape_open_hvp_forward (it shares the tangent storage and overwrites it)";
-            break;
-        default: why = "the last grape_open_hvp_forward failed"; break;
-    }
-    if (why) { h->err = std::string(call) + ": " + why; return GRAPE_ERR_INVALID; }
-    if (h->open->hv_state != OpenCtx::HV_READY) { h->err = std::string(call) + ": no valid forward state on this time grid"; return GRAPE_ERR_INVALID; }
-    if (nv != x.nv) {
-        h->err = std::string(call) + ": nv = " + std::to_string(nv) + ", but the last grape_open_hvp_forward took nv = " + std::to_string(x.nv);
-        return GRAPE_ERR_INVALID;
-    }
+// is there a forward half whose tangent states a backward half of nv directions may read?  (no HIP call; closed and open handles)
+int hvs_ready(grape_handle *h, const char *call, int nv) {
+    const std::string why = h->ev.tangent_stale(nv);
+    if (!why.empty()) { h->err = std::string(call) + ": " + why; return GRAPE_ERR_INVALID; }
     return GRAPE_OK;
 }
 
@@ -2288,10 +2221,10 @@ int open_hvs_backward(grape_handle *h, const char *call, int nv, const double *f
     if (rc) return rc;
     if (taylor) { h->err = std::string(call) + ": a series did not converge within 200 terms"; return GRAPE_ERR_TAYLOR; }
     double *info = o->hv.info;
-    info[0] = x.terms_fw + terms; info[1] = x.steps_fw + steps; info[2] = (double)nv;
+    info[0] = h->ev.terms_fw + terms; info[1] = h->ev.steps_fw + steps; info[2] = (double)nv;
     info[3] = (double)(o->hv.store.mem.bytes() + x.mem.bytes());
     info[4] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    info[5] = x.terms_fw; info[6] = terms;
+    info[5] = h->ev.terms_fw; info[6] = terms;
     return GRAPE_OK;
 }
 
@@ -2405,10 +2338,7 @@ int open_set_running_cost(grape_handle *h, const double *D, int d_per_traj, doub
     HIPCHK(h, hipStreamSynchronize(h->stream));
     const size_t K = (size_t)h->K, np2 = (size_t)h->NP * h->NP, m2 = 2 * np2, nn = (size_t)h->N * h->N;
     h->have_forward = false;
-    o->have_bwd = false;
-    o->tg_state = OpenCtx::TG_NEW_COST;
-    o->hv_state = OpenCtx::HV_NEW_COST;
-    o->hvs.came(OpenCtx::HvpSplit::COST);
+    h->ev.new_cost();
     o->rc_set = false; o->rc_lambda = 0.0; o->rc_per_traj = 0;
     if (!D || lambda_b == 0.0) return GRAPE_OK;
     int rc;
@@ -2532,6 +2462,7 @@ int grape_create_open(grape_handle **out, const grape_problem *p, const grape_li
     HandleGuard guard(h);
     OpenCtx *o = new OpenCtx();
     h->open = o;
+    h->ev.open = true;
     h->p = *p;
     h->p.Dpen = nullptr;
     h->no_target = p->target == nullptr;
@@ -3706,9 +3637,7 @@ int grape_forward_device(grape_handle *h, const double *d_pulsevals, double *d_o
     }
 #endif
     h->last_walk_fuse = walk_fuse;
-    h->tg_state = h->want_bw ? 2 : 1;
-    h->ex_state = grape_handle::ExpectStore::READY;
-    h->hvs.came(grape_handle::HvpSplit::EVAL);
+    h->ev.forward_succeeded(h->want_bw);   // (present from enqueue; withdrawn where the flags are read)
     // ---- phase 1: forward sweep + tau ----
     SweepArgs sa{};
     sa.U = h->d_U; sa.cls = h->d_cls; sa.psi0 = h->d_psi0; sa.target = h->d_target; sa.weights = h->d_weights;
@@ -3999,7 +3928,7 @@ int backward_device_impl(grape_handle *h, const double *d_f, double *d_G, hipStr
     HIPCHK(h, hipGetLastError());
     phase_end(h, 4, s);
     if (!h->capturing) h->n_bwd++;
-    h->tg_state = 3; h->tg_unit = unit; h->tg_xi_user = h->xi_user != nullptr;
+    h->ev.backward_succeeded(unit, h->xi_user != nullptr, d_chi != nullptr);
     return GRAPE_OK;
 }
 }  // namespace
@@ -4167,7 +4096,7 @@ int backward_enqueue(grape_handle *h, const double f_total[2], const double *chi
 }
 int backward_finish(grape_handle *h, double *G, bool accumulate) {
     const int rc = grape_check(h, h->stream);
-    if (rc) { h->tg_state = 0; h->ex_state = grape_handle::ExpectStore::FAILED; return rc; }
+    if (rc) { h->ev.forward_failed(); return rc; }
     if (!G) return GRAPE_OK;
     const size_t nl = (size_t)h->L * h->N_T;
     if (accumulate) for (size_t i = 0; i < nl; ++i) G[i] += h->h_pin[i];
@@ -4392,7 +4321,7 @@ int grape_forward(grape_handle *h, const double *pulsevals, double *tau) try {
     if (!h->shards.empty()) {
         int rc = multi_forward(h, pulsevals, tau);
         if (rc == GRAPE_ERR_AGAIN) rc = multi_forward(h, pulsevals, tau);   // launch plan adapted: once more
-        if (rc) for (grape_handle *c : h->shards) c->ex_state = grape_handle::ExpectStore::FAILED;   // (grape_expect asks the shards)
+        if (rc) for (grape_handle *c : h->shards) c->ev.forward_failed();   // (grape_expect asks the shards)
         return rc;
     }
     int rc = forward_enqueue(h, pulsevals);
@@ -4403,7 +4332,7 @@ int grape_forward(grape_handle *h, const double *pulsevals, double *tau) try {
         if (rc) return rc;
         rc = forward_finish(h, tau);
     }
-    if (rc) { h->tg_state = 0; h->ex_state = grape_handle::ExpectStore::FAILED; }   // (the stored states of a failed sweep are nobody's input)
+    if (rc) h->ev.forward_failed();   // (the stored states of a failed sweep are nobody's input)
     return rc;
 }
 GRAPE_BARRIER(h ? &h->err : &g_create_error)
@@ -4527,7 +4456,7 @@ int grape_eval(grape_handle *h, const double *pulsevals, double *J, double *G, d
                     if (ok) {
                         h->graph = gph; h->graph_fuse_on = h->fuse_on;
                         h->graph_bw_unit = h->bw_unit; h->graph_z_valid = h->z_valid; h->graph_credit = h->credit_pending;
-                        h->graph_tg_unit = h->tg_unit;
+                        h->graph_unit = h->ev.unit;
                         h->graph_walk_fuse = h->last_walk_fuse;
                     } else {
                         if (gph) hipGraphDestroy(gph);
@@ -4542,10 +4471,8 @@ int grape_eval(grape_handle *h, const double *pulsevals, double *J, double *G, d
                 HIPCHK(h, hipGraphLaunch(h->graph_exec, h->stream));
                 h->foreign_stream = false; h->have_forward = true; h->bw_done = false;
                 h->bw_unit = h->graph_bw_unit; h->z_valid = h->graph_z_valid; h->credit_pending = h->graph_credit;
-                h->tg_state = 3; h->tg_unit = h->graph_tg_unit; h->tg_xi_user = false;
-                h->ex_state = grape_handle::ExpectStore::READY;
+                h->ev.replayed(h->graph_unit);
                 h->last_walk_fuse = h->graph_walk_fuse;   // (an evaluation without a gradient in between carries one end only)
-                h->hvs.came(grape_handle::HvpSplit::EVAL);
                 replayed = true;
             }
         }
@@ -4565,7 +4492,7 @@ int grape_eval(grape_handle *h, const double *pulsevals, double *J, double *G, d
         }
         HIPCHK(h, hipStreamSynchronize(h->stream));
         rc = digest_flags(h, pinned_flags(h));
-        if (rc) { h->tg_state = 0; h->ex_state = grape_handle::ExpectStore::FAILED; return rc; }
+        if (rc) { h->ev.forward_failed(); return rc; }
         if (tau) memcpy(tau, h->h_pin + (size_t)h->L * h->N_T, (size_t)2 * h->K * 8);
         *J = functional_from_sums(h, forward_sums(h));
         memcpy(G, gpin, (size_t)h->L * h->N_T * 8);
@@ -4599,7 +4526,7 @@ GRAPE_BARRIER(h ? &h->err : &g_create_error)
 int grape_get_tau_grads(grape_handle *h, double *out) try {
     if (!h || !out) return GRAPE_ERR_INVALID;
     if (h->open) {
-        if (!h->open->have_bwd) { h->err = "grape_get_tau_grads: the last evaluation of this handle had no (successful) backward half"; return GRAPE_ERR_INVALID; }
+        if (!h->ev.backward_complete()) { h->err = "grape_get_tau_grads: the last evaluation of this handle had no (successful) backward half"; return GRAPE_ERR_INVALID; }
         HIPCHK(h, hipSetDevice(h->device));
         HIPCHK(h, hipMemcpy(out, h->open->d_tg, (size_t)h->K * h->L * h->N_T * 16, hipMemcpyDeviceToHost));
         return GRAPE_OK;
@@ -4952,11 +4879,8 @@ int grape_get_time_gradient(grape_handle *h, double *dJdt) try {
         }
         return GRAPE_OK;
     }
-    if (h->tg_state != 3) {
-        h->err = h->tg_state == 0 ? "grape_get_time_gradient: no complete gradient evaluation on this time grid (none yet, the last "
-                                    "one failed, or grape_set_tlist came after it)"
-               : h->tg_state == 1 ? "grape_get_time_gradient: the last evaluation had no gradient (grape_eval with G == NULL)"
-                                  : "grape_get_time_gradient called between grape_forward and the backward half";
+    if (const char *why = h->ev.gradient_stale()) {   // (one of the three sentences has always come without the colon)
+        h->err = std::string("grape_get_time_gradient") + (why == StoredEval::between_halves ? " " : ": ") + why;
         return GRAPE_ERR_INVALID;
     }
     HIPCHK(h, hipSetDevice(h->device));
@@ -4967,8 +4891,8 @@ int grape_get_time_gradient(grape_handle *h, double *dJdt) try {
     if (!h->d_dJdt) HIPCHK(h, h->mem.alloc(&h->d_dJdt, (size_t)N_T));
     TimeGradArgs ta{};
     ta.H0f = h->d_H0f; ta.Hcf = h->d_Hcf; ta.eps = h->d_eps; ta.shape = h->d_shape;
-    ta.fw = h->d_fw; ta.bw = h->d_bw; ta.rho = h->d_rho; ta.z = h->tg_unit ? h->d_z : nullptr;
-    ta.gb = (h->have_gb && !h->tg_xi_user) ? h->d_gb : nullptr; ta.lambda_q = 0.25 * h->p.lambda_b;
+    ta.fw = h->d_fw; ta.bw = h->d_bw; ta.rho = h->d_rho; ta.z = h->ev.unit ? h->d_z : nullptr;
+    ta.gb = (h->have_gb && !h->ev.xi_user) ? h->d_gb : nullptr; ta.lambda_q = 0.25 * h->p.lambda_b;
     ta.out = h->d_tq;
     ta.K = h->K; ta.L = h->L; ta.N = h->N; ta.NP = h->NP; ta.N_T = N_T; ta.hc_per_traj = h->p.hc_per_traj;
     // columns per workgroup: the state block in the LDS stays at 64 KB (128 KB at NP = 512, one column tile)
@@ -5042,7 +4966,7 @@ int grape_open_hvp_backward(grape_handle *h, int nv, const double f_total[2], co
         return GRAPE_ERR_INVALID;
     }
     if (const char *why = open_hvs_refusal(h, true)) { h->err = std::string("grape_open_hvp_backward: ") + why; return GRAPE_ERR_INVALID; }
-    if (const int rc = open_hvs_ready(h, "grape_open_hvp_backward", nv)) return rc;
+    if (const int rc = hvs_ready(h, "grape_open_hvp_backward", nv)) return rc;
     return open_hvs_backward(h, "grape_open_hvp_backward", nv, f_total, df_total, nullptr, nullptr, HV);
 }
 GRAPE_BARRIER(h ? &h->err : &g_create_error)
@@ -5054,7 +4978,7 @@ int grape_open_hvp_backward_chi(grape_handle *h, int nv, const double *chi, cons
         return GRAPE_ERR_INVALID;
     }
     if (const char *why = open_hvs_refusal(h, false)) { h->err = std::string("grape_open_hvp_backward_chi: ") + why; return GRAPE_ERR_INVALID; }
-    if (const int rc = open_hvs_ready(h, "grape_open_hvp_backward_chi", nv)) return rc;
+    if (const int rc = hvs_ready(h, "grape_open_hvp_backward_chi", nv)) return rc;
     return open_hvs_backward(h, "grape_open_hvp_backward_chi", nv, nullptr, nullptr, chi, dchi, HV);
 }
 GRAPE_BARRIER(h ? &h->err : &g_create_error)
@@ -5108,9 +5032,7 @@ int grape_set_tlist(grape_handle *h, const double *tlist) try {
             return GRAPE_ERR_INVALID;
         }
     if (h->open) return open_set_tlist(h, tlist);
-    h->tg_state = 0;
-    h->ex_state = grape_handle::ExpectStore::TLIST;
-    h->hvs.came(grape_handle::HvpSplit::TLIST);
+    h->ev.new_grid();
     h->have_forward = false;
     if (!h->shards.empty()) {
         for (grape_handle *c : h->shards) {
@@ -5292,14 +5214,8 @@ int batch_group(grape_handle *h, const BatchStrides &st, int p0, int Pg, const d
 
 // the stored states no longer belong to "the last evaluation": grape_get_time_gradient refuses until the next ordinary one
 void batch_invalidate(grape_handle *h) {
-    h->tg_state = 0;
-    h->ex_state = grape_handle::ExpectStore::BATCH;
-    h->hvs.came(grape_handle::HvpSplit::BATCH);
-    for (grape_handle *c : h->shards) { c->tg_state = 0; c->ex_state = grape_handle::ExpectStore::BATCH; }
-    if (h->open) {
-        h->open->tg_state = OpenCtx::TG_BATCH; h->open->hv_state = OpenCtx::HV_BATCH;
-        h->open->hvs.came(OpenCtx::HvpSplit::BATCH);
-    }
+    h->ev.batch_call();
+    for (grape_handle *c : h->shards) c->ev.batch_call();
 }
 
 }  // namespace
@@ -5403,10 +5319,7 @@ const char *hvp_refusal(const grape_handle *h) {
     if (h->K != h->K_total) return "a split-phase shard (K < K_total) is out of scope: f' would need an all-reduce of its own";
     if (h->no_target) return "this handle has no target states (grape_problem.target == NULL): chi'(T) would be the caller's";
     if (h->have_gb || (h->p.Dpen && h->p.lambda_b != 0.0)) return "the built-in running cost (Dpen, lambda_b != 0) is out of scope";
-    if (h->tg_state < 1)
-        return "no valid forward state on this time grid (no evaluation yet, the last one failed, grape_set_tlist came since, "
-               "or the last call was grape_eval_batch)";
-    return nullptr;
+    return h->ev.forward_stale() ? StoredEval::no_forward_on_grid : nullptr;
 }
 
 }  // namespace
@@ -5417,7 +5330,7 @@ int grape_hvp(grape_handle *h, int nv, const double *V, double *HV) try {
     if (!h) { g_create_error = "grape_hvp: h == NULL"; return GRAPE_ERR_INVALID; }
     if (nv <= 0 || !V || !HV) { h->err = "grape_hvp: nv must be positive, V and HV must not be NULL"; return GRAPE_ERR_INVALID; }
     if (const char *why = hvp_refusal(h)) { h->err = std::string("grape_hvp: ") + why; return GRAPE_ERR_INVALID; }
-    h->hvs.came(grape_handle::HvpSplit::HVP);   // (the tangent storage of a forward half is overwritten)
+    h->ev.tangent_overwritten();   // (the tangent storage of a forward half is overwritten)
     const auto t0 = std::chrono::steady_clock::now();
     HIPCHK(h, hipSetDevice(h->device));
     if (h->foreign_stream) HIPCHK(h, hipDeviceSynchronize());   // (see grape_get_time_gradient)
@@ -5562,11 +5475,8 @@ const char *hess_refusal(const grape_handle *h) {
     if (h->K != h->K_total) return "a split-phase shard (K < K_total) is out of scope: the boundary term couples all trajectories";
     if (h->no_target) return "this handle has no target states (grape_problem.target == NULL): the functional would be the caller's";
     if (h->have_gb || (h->p.Dpen && h->p.lambda_b != 0.0)) return "the built-in running cost (Dpen, lambda_b != 0) is out of scope";
-    if (h->tg_xi_user) return "the last backward half took a caller's xi (grape_backward_xi): running costs are out of scope";
-    if (h->tg_state < 1)
-        return "no valid forward state on this time grid (no evaluation yet, the last one failed, grape_set_tlist came since, "
-               "or the last call was grape_eval_batch)";
-    return nullptr;
+    if (h->ev.xi_user) return "the last backward half took a caller's xi (grape_backward_xi): running costs are out of scope";
+    return h->ev.forward_stale() ? StoredEval::no_forward_on_grid : nullptr;
 }
 
 // the statistics of `nwg` workgroups and the flag word of the launch before, summed on the host
@@ -5752,14 +5662,7 @@ const char *open_hess_refusal(const grape_handle *h) {
     if (h->no_target) return "this handle has no target states (grape_problem.target == NULL): the functional would be the caller's";
     if (h->open->rc_set)
         return "a state running cost is set on this handle (grape_open_set_running_cost): its second-order terms are not carried";
-    switch (h->open->hv_state) {
-    case OpenCtx::HV_READY: return nullptr;
-    case OpenCtx::HV_NONE: return "no valid forward state: no evaluation on this handle yet";
-    case OpenCtx::HV_NEW_GRID: return "no valid forward state: grape_set_tlist came after the last evaluation, the stored states belong to the previous grid";
-    case OpenCtx::HV_NEW_COST: return "no valid forward state: grape_open_set_running_cost came after the last evaluation";
-    case OpenCtx::HV_BATCH: return "no valid forward state: the last call was grape_eval_batch, the stored states are not those of one defined evaluation";
-    default: return "no valid forward state: the last forward sweep failed";
-    }
+    return nullptr;
 }
 
 // H = d^2 J / d eps^2 at the pulses of the last forward half, from the stored rho_k(t_n), tau, f and the device copy of the
@@ -5861,6 +5764,7 @@ int grape_open_hessian(grape_handle *h, double *H) try {
     if (!h) { g_create_error = "grape_open_hessian: h == NULL"; return GRAPE_ERR_INVALID; }
     if (!H) { h->err = "grape_open_hessian: H must not be NULL"; return GRAPE_ERR_INVALID; }
     if (const char *why = open_hess_refusal(h)) { h->err = std::string("grape_open_hessian: ") + why; return GRAPE_ERR_INVALID; }
+    if (const char *why = h->ev.forward_stale()) return refuse_stale_forward(h, "grape_open_hessian", why);
     return open_hessian(h, H);
 }
 GRAPE_BARRIER(h ? &h->err : &g_create_error)
@@ -5881,31 +5785,11 @@ namespace {
 #define EXPECT_REFUSE(text) do { h->err = "grape_expect: " text; return GRAPE_ERR_INVALID; } while (0)
 
 // why the store of this handle is not that of one successful forward half on the current grid (nullptr: it is)
+// (a composite asks its shards; an open handle counts a backward half that failed behind a good forward half as a failure)
 const char *expect_stale(const grape_handle *h) {
-    typedef grape_handle::ExpectStore X;
-    if (h->open) {
-        switch (h->open->hv_state) {
-        case OpenCtx::HV_READY:   // (the forward half stands; a backward half that failed behind it fails the evaluation)
-            return h->open->tg_state == OpenCtx::TG_FAILED ? "no valid forward state: the last evaluation failed" : nullptr;
-        case OpenCtx::HV_NONE: return "no valid forward state: no evaluation on this handle yet";
-        case OpenCtx::HV_NEW_GRID: return "no valid forward state: grape_set_tlist came after the last evaluation, the stored states belong to the previous grid";
-        case OpenCtx::HV_NEW_COST: return "no valid forward state: grape_open_set_running_cost came after the last evaluation";
-        case OpenCtx::HV_BATCH: return "no valid forward state: the last call was grape_eval_batch, the stored states are not those of one defined evaluation";
-        default: return "no valid forward state: the last evaluation failed";
-        }
-    }
-    if (!h->shards.empty()) {
-        for (const grape_handle *c : h->shards)
-            if (const char *why = expect_stale(c)) return why;
-        return nullptr;
-    }
-    switch (h->ex_state) {
-    case X::READY: return nullptr;
-    case X::NONE: return "no valid forward state: no evaluation on this handle yet";
-    case X::TLIST: return "no valid forward state: grape_set_tlist came after the last evaluation, the stored states belong to the previous grid";
-    case X::BATCH: return "no valid forward state: the last call was grape_eval_batch, the stored states are not those of one defined evaluation";
-    default: return "no valid forward state: the last evaluation failed";
-    }
+    for (const grape_handle *c : h->shards)
+        if (const char *why = expect_stale(c)) return why;
+    return h->shards.empty() ? h->ev.forward_stale(StoredEval::EVALUATION) : nullptr;
 }
 
 // the two buffers of the call, through the handle's allocator; they only grow.  A failure names the size and leaves nothing
@@ -5993,7 +5877,7 @@ int grape_expect(grape_handle *h, int M, const double *ops, int ops_per_traj, do
     if (M <= 0) EXPECT_REFUSE("M must be positive");
     if (M > 16) EXPECT_REFUSE("M > 16: at most 16 observables per call");
     if (ops_per_traj != 0 && ops_per_traj != 1) EXPECT_REFUSE("ops_per_traj must be 0 (one set of operators for all trajectories) or 1 (one per trajectory)");
-    if (const char *why = expect_stale(h)) { h->err = std::string("grape_expect: ") + why; return GRAPE_ERR_INVALID; }
+    if (const char *why = expect_stale(h)) return refuse_stale_forward(h, "grape_expect", why);
     if (!h->shards.empty()) {   // [k][n][m], operators [k][m]: the shards are contiguous blocks of k
         const auto t0 = std::chrono::steady_clock::now();
         double bytes = 0., flop = 0.;
@@ -6036,7 +5920,7 @@ const char *hvp_split_refusal(const grape_handle *h, bool builtin) {
     if (builtin && h->no_target)
         return "this handle has no target states (grape_problem.target == NULL): grape_hvp_backward_chi is the route";
     if (h->have_gb || (h->p.Dpen && h->p.lambda_b != 0.0)) return "the built-in running cost (Dpen, lambda_b != 0) is out of scope";
-    if (h->tg_xi_user) return "the last backward half took a caller's xi (grape_backward_xi): running costs are out of scope";
+    if (h->ev.xi_user) return "the last backward half took a caller's xi (grape_backward_xi): running costs are out of scope";
     return nullptr;
 }
 
@@ -6119,7 +6003,7 @@ int hvp_split_forward(grape_handle *h, int nv, const double *V, double *dtau, do
                  "free memory, GRAPE_HVP_DIRS): at most " + std::to_string(nd) + " stay resident between the halves; loop over groups of that size";
         return GRAPE_ERR_INVALID;
     }
-    x.state = HvpSplit::FAILED;   // (until this half has succeeded: the tangent storage is being overwritten)
+    h->ev.split_forward_begun();   // (failed until this half has succeeded: the tangent storage is being overwritten)
     int rc = hvp_reserve(h, nv, &nd);
     if (rc) return rc;
     rc = hvs_reserve(h, nv);
@@ -6160,33 +6044,11 @@ int hvp_split_forward(grape_handle *h, int nv, const double *V, double *dtau, do
         if (dtau) std::fill(dtau, dtau + 2 * (size_t)nv * K, nan);
         if (dsums) std::fill(dsums, dsums + 2 * (size_t)nv, nan);
     }
-    x.state = HvpSplit::READY; x.nv = nv; x.terms_fw = terms; x.steps_fw = steps;
+    h->ev.split_forward_succeeded(nv, terms, steps);
     double *info = h->hvp.info;
     info[0] = terms; info[1] = steps; info[2] = (double)nv; info[3] = (double)(h->hvp.store.mem.bytes() + x.mem.bytes());
     info[4] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     info[5] = terms; info[6] = 0.;
-    return GRAPE_OK;
-}
-
-// is there a forward half whose tangent states a backward half of nv directions may read?  (no HIP call)
-int hvp_split_ready(grape_handle *h, const char *call, int nv) {
-    const HvpSplit &x = h->hvs;
-    const char *why = nullptr;
-    switch (x.state) {
-        case HvpSplit::READY: break;
-        case HvpSplit::NONE: why = "no grape_hvp_forward on this handle yet"; break;
-        case HvpSplit::EVAL: why = "a forward evaluation came since the last grape_hvp_forward"; break;
-        case HvpSplit::TLIST: why = "grape_set_tlist came since the last grape_hvp_forward"; break;
-        case HvpSplit::BATCH: why = "grape_eval_batch came since the last grape_hvp_forward"; break;
-        case HvpSplit::HVP: why = "grape_hvp came since the last grape_hvp_forward (it shares the tangent storage and overwrites it)"; break;
-        default: why = "the last grape_hvp_forward failed"; break;
-    }
-    if (why) { h->err = std::string(call) + ": " + why; return GRAPE_ERR_INVALID; }
-    if (h->tg_state < 1) { h->err = std::string(call) + ": no valid forward state on this time grid"; return GRAPE_ERR_INVALID; }
-    if (nv != x.nv) {
-        h->err = std::string(call) + ": nv = " + std::to_string(nv) + ", but the last grape_hvp_forward took nv = " + std::to_string(x.nv);
-        return GRAPE_ERR_INVALID;
-    }
     return GRAPE_OK;
 }
 
@@ -6248,10 +6110,10 @@ int hvp_split_backward(grape_handle *h, const char *call, int nv, const double *
     if (rc) return rc;
     if (taylor) { h->err = std::string(call) + ": a series did not converge within 200 terms"; return GRAPE_ERR_TAYLOR; }
     double *info = h->hvp.info;
-    info[0] = x.terms_fw + terms; info[1] = x.steps_fw + steps; info[2] = (double)nv;
+    info[0] = h->ev.terms_fw + terms; info[1] = h->ev.steps_fw + steps; info[2] = (double)nv;
     info[3] = (double)(h->hvp.store.mem.bytes() + x.mem.bytes());
     info[4] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    info[5] = x.terms_fw; info[6] = terms;
+    info[5] = h->ev.terms_fw; info[6] = terms;
     return GRAPE_OK;
 }
 
@@ -6263,11 +6125,7 @@ int grape_hvp_forward(grape_handle *h, int nv, const double *V, double *dtau, do
     if (!h) { g_create_error = "grape_hvp_forward: h == NULL"; return GRAPE_ERR_INVALID; }
     if (nv <= 0 || !V) { h->err = "grape_hvp_forward: nv must be positive, V must not be NULL"; return GRAPE_ERR_INVALID; }
     if (const char *why = hvp_split_refusal(h, false)) { h->err = std::string("grape_hvp_forward: ") + why; return GRAPE_ERR_INVALID; }
-    if (h->tg_state < 1) {
-        h->err = "grape_hvp_forward: no valid forward state on this time grid (no evaluation yet, the last one failed, grape_set_tlist "
-                 "came since, or the last call was grape_eval_batch)";
-        return GRAPE_ERR_INVALID;
-    }
+    if (h->ev.forward_stale()) { h->err = std::string("grape_hvp_forward: ") + StoredEval::no_forward_on_grid; return GRAPE_ERR_INVALID; }
     return hvp_split_forward(h, nv, V, dtau, dsums, dpsiT);
 }
 GRAPE_BARRIER(h ? &h->err : &g_create_error)
@@ -6279,7 +6137,7 @@ int grape_hvp_backward(grape_handle *h, int nv, const double f_total[2], const d
         return GRAPE_ERR_INVALID;
     }
     if (const char *why = hvp_split_refusal(h, true)) { h->err = std::string("grape_hvp_backward: ") + why; return GRAPE_ERR_INVALID; }
-    if (const int rc = hvp_split_ready(h, "grape_hvp_backward", nv)) return rc;
+    if (const int rc = hvs_ready(h, "grape_hvp_backward", nv)) return rc;
     return hvp_split_backward(h, "grape_hvp_backward", nv, f_total, df_total, nullptr, nullptr, HV);
 }
 GRAPE_BARRIER(h ? &h->err : &g_create_error)
@@ -6291,7 +6149,7 @@ int grape_hvp_backward_chi(grape_handle *h, int nv, const double *chi, const dou
         return GRAPE_ERR_INVALID;
     }
     if (const char *why = hvp_split_refusal(h, false)) { h->err = std::string("grape_hvp_backward_chi: ") + why; return GRAPE_ERR_INVALID; }
-    if (const int rc = hvp_split_ready(h, "grape_hvp_backward_chi", nv)) return rc;
+    if (const int rc = hvs_ready(h, "grape_hvp_backward_chi", nv)) return rc;
     return hvp_split_backward(h, "grape_hvp_backward_chi", nv, nullptr, nullptr, chi, dchi, HV);
 }
 GRAPE_BARRIER(h ? &h->err : &g_create_error)
