@@ -461,22 +461,12 @@ class GrapeHip:
         """Exact Hessian-vector products at the pulses of the last evaluation (grape_hvp): ``V`` [L*N_T] -> H v [L*N_T], or
         [nv, L*N_T] -> [nv, L*N_T] (all directions in one call, side by side on the GPU).  Needs a successful ``eval`` or
         ``forward`` on the current time grid; the built-in functional only (include/grape_hip.h lists the refusals)."""
-        v = np.ascontiguousarray(V, dtype=np.float64)
-        LN = self.L * self.N_T
-        if v.ndim not in (1, 2) or v.shape[-1] != LN or v.size == 0:
-            raise ValueError(f"V must be [L*N_T] = [{LN}] or [nv, {LN}] with nv >= 1, got {v.shape}")
-        nv = 1 if v.ndim == 1 else v.shape[0]
-        out = np.empty_like(v)
-        self._chk(self._lib.grape_hvp(self._h, nv, v.ctypes.data, out.ctypes.data))
-        return out
+        return self._hvp_call("grape_hvp", V)
 
     def hvp_info(self):
         """What the last ``hvp`` did (grape_get_hvp_info): series terms and (sub-)steps summed over the workgroups of both
         sweeps, directions per launch group, bytes of HVP storage the handle holds, milliseconds of the call."""
-        out = np.zeros(7)
-        self._lib.grape_get_hvp_info(self._h, out.ctypes.data, 7)
-        return dict(series_terms=int(out[0]), series_steps=int(out[1]), dirs_per_group=int(out[2]), bytes=int(out[3]), ms=float(out[4]),
-                    terms_forward=int(out[5]), terms_backward=int(out[6]))
+        return self._hvp_info("grape_get_hvp_info")
 
     def hessian(self):
         """The exact Hessian of J at the pulses of the last evaluation as a matrix (grape_hessian): [L*N_T, L*N_T], indexed as
@@ -526,6 +516,31 @@ class GrapeHip:
             raise ValueError(f"V must be [L*N_T] = [{LN}] or [nv, {LN}] with nv >= 1, got {v.shape}")
         return v, (1 if v.ndim == 1 else v.shape[0])
 
+    # the bodies the closed calls share with their open-system counterparts: the same arrays around another C symbol (cfn: its
+    # name, looked up once the arguments have passed their checks)
+    def _hvp_call(self, cfn, V):
+        v, nv = self._hvp_dirs(V)
+        out = np.empty_like(v)
+        self._chk(getattr(self._lib, cfn)(self._h, nv, v.ctypes.data, out.ctypes.data))
+        return out
+
+    def _hvp_info(self, cfn):
+        out = np.zeros(7)
+        getattr(self._lib, cfn)(self._h, out.ctypes.data, 7)
+        return dict(series_terms=int(out[0]), series_steps=int(out[1]), dirs_per_group=int(out[2]), bytes=int(out[3]), ms=float(out[4]),
+                    terms_forward=int(out[5]), terms_backward=int(out[6]))
+
+    def _hvp_backward_call(self, cfn, f_total, df_total):
+        one = np.ndim(df_total) == 0
+        df = np.ascontiguousarray(df_total, dtype=np.complex128)   # (at least one-dimensional)
+        if np.ndim(df_total) > 1 or df.size == 0:
+            raise ValueError(f"df_total must be a complex scalar or [nv] with nv >= 1, got {np.shape(df_total)}")
+        nv = df.size
+        out = np.empty((nv, self.L * self.N_T))
+        f = np.array([complex(f_total).real, complex(f_total).imag], dtype=np.float64)
+        self._chk(getattr(self._lib, cfn)(self._h, nv, f.ctypes.data, df.ctypes.data, out.ctypes.data))
+        return out[0] if one else out
+
     def hvp_forward(self, V, final_states=False):
         """First half of a split Hessian-vector product (grape_hvp_forward): the tangent forward sweep of ``V`` [nv, L*N_T]
         at the pulses of the last evaluation.  Returns ``(dtau [nv, K], dsums [nv] complex)`` -- tau'_k and this handle's
@@ -547,15 +562,7 @@ class GrapeHip:
         as for ``backward``), ``df_total`` [nv] complex the all-reduced ``dsums`` of ``hvp_forward`` (a scalar for a single
         direction given as a vector).  Returns this handle's H v [nv, L*N_T] (or [L*N_T]): the partial sum over its
         trajectories, the full product when K == K_total."""
-        one = np.ndim(df_total) == 0
-        df = np.ascontiguousarray(df_total, dtype=np.complex128)   # (at least one-dimensional)
-        if np.ndim(df_total) > 1 or df.size == 0:
-            raise ValueError(f"df_total must be a complex scalar or [nv] with nv >= 1, got {np.shape(df_total)}")
-        nv = df.size
-        out = np.empty((nv, self.L * self.N_T))
-        f = np.array([complex(f_total).real, complex(f_total).imag], dtype=np.float64)
-        self._chk(self._lib.grape_hvp_backward(self._h, nv, f.ctypes.data, df.ctypes.data, out.ctypes.data))
-        return out[0] if one else out
+        return self._hvp_backward_call("grape_hvp_backward", f_total, df_total)
 
     def hvp_backward_chi(self, chi, dchi):
         """Second half for a caller's functional (grape_hvp_backward_chi): ``chi`` [K, N] as for ``backward_chi`` (not
@@ -800,22 +807,12 @@ class GrapeHipOpen(GrapeHip):
         [nv, L*N_T] -> [nv, L*N_T] (all directions in one call, side by side on the GPU).  Needs a successful ``eval`` or
         ``forward`` on the current time grid; the built-in functional only (include/grape_hip.h lists the refusals).  A method of
         its own, as the C call is: the inherited ``hvp`` stays grape_hvp, which refuses an open handle."""
-        v = np.ascontiguousarray(V, dtype=np.float64)
-        LN = self.L * self.N_T
-        if v.ndim not in (1, 2) or v.shape[-1] != LN or v.size == 0:
-            raise ValueError(f"V must be [L*N_T] = [{LN}] or [nv, {LN}] with nv >= 1, got {v.shape}")
-        nv = 1 if v.ndim == 1 else v.shape[0]
-        out = np.empty_like(v)
-        self._chk(self._lib.grape_open_hvp(self._h, nv, v.ctypes.data, out.ctypes.data))
-        return out
+        return self._hvp_call("grape_open_hvp", V)
 
     def open_hvp_info(self):
         """What the last ``open_hvp`` did (grape_get_open_hvp_info): series terms and (sub-)steps summed over the workgroups of both
         sweeps, directions per launch group, bytes of HVP storage the handle holds, milliseconds of the call."""
-        out = np.zeros(7)
-        self._lib.grape_get_open_hvp_info(self._h, out.ctypes.data, 7)
-        return dict(series_terms=int(out[0]), series_steps=int(out[1]), dirs_per_group=int(out[2]), bytes=int(out[3]), ms=float(out[4]),
-                    terms_forward=int(out[5]), terms_backward=int(out[6]))
+        return self._hvp_info("grape_get_open_hvp_info")
 
     def open_hessian(self):
         """The exact Hessian of J at the pulses of the last evaluation as a matrix (grape_open_hessian): [L*N_T, L*N_T], indexed
@@ -862,15 +859,7 @@ class GrapeHipOpen(GrapeHip):
         (complex, as for ``backward``), ``df_total`` [nv] complex the all-reduced ``dsums`` of ``open_hvp_forward`` (a scalar
         for a single direction given as a vector).  Returns this handle's H v [nv, L*N_T] (or [L*N_T]): the partial sum over
         its trajectories, the full product when K == K_total."""
-        one = np.ndim(df_total) == 0
-        df = np.ascontiguousarray(df_total, dtype=np.complex128)   # (at least one-dimensional)
-        if np.ndim(df_total) > 1 or df.size == 0:
-            raise ValueError(f"df_total must be a complex scalar or [nv] with nv >= 1, got {np.shape(df_total)}")
-        nv = df.size
-        out = np.empty((nv, self.L * self.N_T))
-        f = np.array([complex(f_total).real, complex(f_total).imag], dtype=np.float64)
-        self._chk(self._lib.grape_open_hvp_backward(self._h, nv, f.ctypes.data, df.ctypes.data, out.ctypes.data))
-        return out[0] if one else out
+        return self._hvp_backward_call("grape_open_hvp_backward", f_total, df_total)
 
     def open_hvp_backward_chi(self, chi, dchi):
         """Second half for a caller's functional (grape_open_hvp_backward_chi): ``chi`` [K, d, d] as for ``backward_chi`` (not

@@ -43,6 +43,7 @@
 #include <stdexcept>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 namespace {
@@ -80,6 +81,19 @@ void test_throw_point(const char *where) {
 constexpr int kRing = 64;   // evaluations kept for phase timing
 constexpr int kPhases = 6;
 struct Phase { hipEvent_t e0, e1; bool used; };
+
+// What only the split Hessian-vector calls need: the two halves share the tangent storage of the one-call
+// product; this lives in a store of its own, allocated by the first split call, so that a handle which never makes one holds --
+// and reports -- what it held before.  T: double2 on a closed handle (vectors), double on an open one (planar matrices).
+template <typename T>
+struct SplitExtras {
+    DeviceBufs mem;
+    int cap = 0;               // directions the extras hold
+    T *d_chi = nullptr, *d_dchi = nullptr, *d_ztarget = nullptr;      // chi | chi' [cap] | a zero target (closed: chi~ [K][NP], zeros [K][N])
+    T *d_dfinal = nullptr;                                            // Psi~'(T) [cap][K][N] | rho'(T) [cap][K] matrices, packed for the host
+    double *d_ftot = nullptr, *d_dftot = nullptr, *d_psums = nullptr; // f_total [2] | f'_total [cap][2] | partial sums [cap][2]
+    std::vector<double> stage; // host staging of chi, chi' (open handles: rho'(T) too)
+};
 
 }  // namespace
 
@@ -368,17 +382,7 @@ struct grape_handle {
         unsigned long long *d_stats = nullptr;   // statistics of the workgroups of a launch, then the flag word
         double info[8] = {0., 0., 0., 0., 0., 0., 0., 0.};   // grape_get_hessian_info
     } hess;
-    // grape_hvp_forward / grape_hvp_backward / grape_hvp_backward_chi (grape_hvp_split.hip.h): the two halves
-    // share the tangent storage above; what only they need lives here, allocated by the first split call, so that a handle
-    // which never makes one holds -- and reports -- what it held before.
-    struct HvpSplit {
-        DeviceBufs mem;
-        int cap = 0;               // directions the extras hold
-        double2 *d_chi = nullptr, *d_dchi = nullptr, *d_ztarget = nullptr;   // chi~ [K][NP] | chi~' [cap][K][NP] | zeros [K][N]
-        double2 *d_dpsiT = nullptr;                                          // Psi~'(T) [cap][K][N], packed for the host
-        double *d_ftot = nullptr, *d_dftot = nullptr, *d_psums = nullptr;     // f_total [2] | f'_total [cap][2] | partial sums [cap][2]
-        std::vector<double> stage; // host staging of chi~, chi~'
-    } hvs;
+    SplitExtras<double2> hvs;  // grape_hvp_forward / grape_hvp_backward / grape_hvp_backward_chi (grape_hvp_split.hip.h)
     // grape_create_open (grape_lindblad.hip.h): the states are d x d density matrices under a Lindblad
     // generator.  Such a handle owns none of the buffers above: everything it holds hangs off this pointer, and the entry
     // points dispatch on it.
@@ -423,6 +427,121 @@ int group_reserve(grape_handle *h, GroupStore &g, int want, size_t per, double b
         return GRAPE_ERR_HIP;
     }
     return GRAPE_OK;
+}
+
+// ---------------------------------------------------------------------------------------
+// The host scaffold of the second-order calls (grape_hvp and its halves, grape_hessian, their open-system counterparts;
+// DESIGN.md 28): arguments, prologue, statistics, reduction, dispatch, extras, residency, info.
+// ---------------------------------------------------------------------------------------
+
+// what every closed-handle kernel of these calls reads of the handle and its stored evaluation; the call adds V, the tangent
+// buffers, flags and stats, and replaces f and target where the caller passes them
+HvpArgs closed_series_args(const grape_handle *h) {
+    HvpArgs a{};
+    a.H0f = h->d_H0f; a.Hcf = h->d_Hcf; a.eps = h->d_eps; a.shape = h->d_shape; a.dts = h->d_dts; a.rb = h->d_rb;
+    a.fw = h->d_fw; a.target = h->d_target; a.weights = h->d_weights;
+    a.tau = (const double2 *)h->d_out; a.f = h->d_out + 2 * (size_t)h->K;
+    a.tol = h->series_tol; a.theta = h->series_theta;
+    a.K = h->K; a.K_total = h->K_total; a.L = h->L; a.N = h->N; a.N_T = h->N_T; a.functional = h->p.functional;
+    a.hc_per_traj = h->p.hc_per_traj;
+    return a;
+}
+
+// the prologue of a call.  The wait is for a forward half enqueued on a caller's stream (see grape_get_time_gradient); an open
+// handle never has foreign_stream set -- grape_forward_device refuses one at its first line -- so the test is dead code there
+int second_order_begin(grape_handle *h) {
+    HIPCHK(h, hipSetDevice(h->device));
+    if (h->foreign_stream) HIPCHK(h, hipDeviceSynchronize());
+    (void)hipGetLastError();
+    return GRAPE_OK;
+}
+
+// The work statistics of the launches enqueued before: (terms, steps) of nwg workgroups at d_stats into *acc, of nwg2 more right
+// behind them into *acc2, and bit 16 ("a series did not converge") of the 32-bit flag word at d_flag.  One synchronisation.
+// (A 64-bit flag word behind the statistics is read by its first four bytes; where it directly follows, one copy fetches both.)
+struct WorkStats { double terms = 0., steps = 0.; bool taylor = false; };
+int read_stats(grape_handle *h, const unsigned long long *d_stats, size_t nwg, const int *d_flag, WorkStats *acc, size_t nwg2 = 0,
+               WorkStats *acc2 = nullptr) {
+    const size_t n = 2 * (nwg + nwg2);
+    const bool adjacent = (const void *)d_flag == (const void *)(d_stats + n);
+    std::vector<unsigned long long> st(n + 1, 0ull);
+    HIPCHK(h, hipMemcpyAsync(st.data(), d_stats, (n + adjacent) * 8, hipMemcpyDeviceToHost, h->stream));
+    if (!adjacent) HIPCHK(h, hipMemcpyAsync(&st[n], d_flag, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    for (size_t w = 0; w < nwg + nwg2; ++w) {
+        WorkStats *to = w < nwg ? acc : acc2;
+        to->terms += (double)st[2 * w]; to->steps += (double)st[2 * w + 1];
+    }
+    if ((int)(st[n] & 0xffffffffull) & 16) acc->taylor = true;
+    return GRAPE_OK;
+}
+
+// (H v)_j = -2 Re sum_k of the per-trajectory terms tg [n][K][L N_T]: the gradient's reduction, fixed order
+void reduce_directions(grape_handle *h, double2 *tg, double *out, int n) {
+    const size_t LN = (size_t)h->L * h->N_T;
+    for (int j = 0; j < n; ++j)
+        hipLaunchKernelGGL(grad_reduce_kernel, dim3((unsigned)((LN + 15) / 16)), dim3(256), 0, h->stream, tg + (size_t)j * h->K * LN, h->K,
+                           (int)LN, out + (size_t)j * LN, (const double2 *)nullptr);
+}
+
+// fn(std::integral_constant<int, NP>) for the padded size of the handle: the kernels of these calls are templates on it
+template <class F>
+void with_np(int NP, F &&fn) {
+    switch (NP) {
+        case 16: fn(std::integral_constant<int, 16>{}); break;
+        case 32: fn(std::integral_constant<int, 32>{}); break;
+        case 48: fn(std::integral_constant<int, 48>{}); break;
+        default: fn(std::integral_constant<int, 64>{}); break;
+    }
+}
+
+// the extras of the split calls for nv directions: chi of state_elems elements and nv chi', a zero target of final_elems and nv
+// final tangents
+template <typename T>
+int split_reserve(grape_handle *h, SplitExtras<T> &x, int nv, size_t state_elems, size_t final_elems, const char *call) {
+    if (nv <= x.cap) return GRAPE_OK;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    x.mem.release(); x.cap = 0;
+    const size_t n = (size_t)nv;
+    hipError_t e = x.mem.alloc(&x.d_chi, state_elems);
+    if (e == hipSuccess) e = x.mem.alloc(&x.d_dchi, n * state_elems);
+    if (e == hipSuccess) e = x.mem.alloc(&x.d_ztarget, final_elems);
+    if (e == hipSuccess) e = x.mem.alloc(&x.d_dfinal, n * final_elems);
+    if (e == hipSuccess) e = x.mem.alloc(&x.d_ftot, (size_t)2);
+    if (e == hipSuccess) e = x.mem.alloc(&x.d_dftot, 2 * n);
+    if (e == hipSuccess) e = x.mem.alloc(&x.d_psums, 2 * n);
+    if (e == hipSuccess) e = hipMemsetAsync(x.d_ztarget, 0, final_elems * sizeof(T), h->stream);
+    if (e != hipSuccess) {
+        x.mem.release();
+        (void)hipGetLastError();
+        h->err = std::string(call) + ": storage of the split calls: " + hipGetErrorString(e);
+        return GRAPE_ERR_HIP;
+    }
+    x.cap = nv;
+    return GRAPE_OK;
+}
+
+// all nv directions of a forward half stay resident for the backward half: the budget of `owner`, the one-call product whose
+// store (`per` bytes a direction) they live in, decides how many that can be
+int split_resident(grape_handle *h, const GroupStore &store, int nv, size_t per, const char *call, const char *owner) {
+    int nd = 0;
+    const hipError_t e = store.plan(nv, per, 8.0 * 1073741824.0, &nd);
+    if (e != hipSuccess) { h->err = std::string("hipMemGetInfo(&free_b, &total_b): ") + hipGetErrorString(e); return GRAPE_ERR_HIP; }
+    if (nd < nv) {
+        h->err = std::string(call) + ": nv = " + std::to_string(nv) + " directions do not fit the storage budget of " + owner +
+                 " (8 GB, half of the free memory, GRAPE_HVP_DIRS): at most " + std::to_string(nd) +
+                 " stay resident between the halves; loop over groups of that size";
+        return GRAPE_ERR_INVALID;
+    }
+    return GRAPE_OK;
+}
+
+// the seven slots every info array of these calls begins with
+void fill_info(double *info, double terms, double steps, int units, size_t bytes, std::chrono::steady_clock::time_point t0, double fw,
+               double bw) {
+    info[0] = terms; info[1] = steps; info[2] = (double)units; info[3] = (double)bytes;
+    info[4] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    info[5] = fw; info[6] = bw;
 }
 
 int copy_info(const double *info, int len, double *out, int n) {
@@ -1597,17 +1716,9 @@ struct OpenCtx {
         unsigned long long *d_hvstats = nullptr;
         double info[7] = {0., 0., 0., 0., 0., 0., 0.};   // grape_get_open_hvp_info
     } hv;
-    // grape_open_hvp_forward / grape_open_hvp_backward / grape_open_hvp_backward_chi (grape_lindblad_hvp_split.hip.h,
-    // DESIGN.md 22): the two halves share the tangent storage above; what only they need lives here, allocated by the first
-    // split call, so that a handle which never makes one holds -- and reports -- what it held before.
-    struct HvpSplit {
-        DeviceBufs mem;
-        int cap = 0;               // directions the extras hold
-        double *d_chi = nullptr, *d_dchi = nullptr, *d_ztarget = nullptr;   // chi [K] | chi' [cap][K] | zeros [K] matrices (2 NP^2 doubles)
-        double *d_drhoT = nullptr;                                          // rho'(T) [cap][K] matrices, packed for the host
-        double *d_ftot = nullptr, *d_dftot = nullptr, *d_psums = nullptr;   // f_total [2] | f'_total [cap][2] | partial sums [cap][2]
-        std::vector<double> stage; // host staging of chi, chi', rho'(T)
-    } hvs;
+    // grape_open_hvp_forward / grape_open_hvp_backward / grape_open_hvp_backward_chi (grape_lindblad_hvp_split.hip.h);
+    // chi, chi', the zero target and rho'(T) are matrices of 2 NP^2 doubles
+    SplitExtras<double> hvs;
     // grape_open_eval_batch (grape_lindblad_batch.hip.h): every per-set buffer belongs to the call -- pulses, stored
     // states, workspaces, tau | sums, ||chi||, tau_grads, G, flags, statistics.  Allocated by the first call, grows with the sets
     // of a launch group.  Nothing an ordinary evaluation or a getter reads is touched, no state word changes.
@@ -1694,6 +1805,14 @@ LindArgs open_args(const grape_handle *h) {
     a.tol = h->series_tol; a.theta = h->series_theta; a.chi_min_norm = h->chi_min_norm;
     a.K = h->K; a.K_total = h->K_total; a.L = h->L; a.J = o->J; a.N_T = h->N_T; a.functional = h->p.functional;
     a.hc_per_traj = h->p.hc_per_traj; a.cops_per_traj = o->cops_per_traj;
+    return a;
+}
+
+// ... of a second-order call: the stored evaluation read-only, workspace and statistics the call's own
+LindArgs open_stored_args(const grape_handle *h) {
+    LindArgs a = open_args(h);
+    a.f = h->open->d_out + 2 * (size_t)h->K;   // sum_k w_k tau_k as the forward half reduced it (d_f belongs to the backward half)
+    a.ws = nullptr; a.tg = nullptr; a.stats = nullptr; a.rho = nullptr;
     return a;
 }
 
@@ -1977,6 +2096,17 @@ int open_hvp_reserve(grape_handle *h, int nv, int *dirs) {
     });
 }
 
+// the arguments of the kernels for nd directions side by side: the stored evaluation, the tangent storage
+LindHvpArgs open_hvp_args(const grape_handle *h, int nd) {
+    const OpenCtx *o = h->open;
+    LindHvpArgs q{};
+    q.a = open_stored_args(h);
+    q.V = o->hv.d_hvV; q.dstore = o->hv.d_hvds; q.dtau = o->hv.d_hvdtau; q.dcoef = o->hv.d_hvdcoef; q.tg = o->hv.d_hvtg; q.ws = o->hv.d_hvws;
+    q.stats = o->hv.d_hvstats;
+    q.nd = nd;
+    return q;
+}
+
 // HV[j] = (d^2 J / d eps^2) V[j] at the pulses of the last forward half, from the stored rho_k(t_n), tau, f and the device copy
 // of the pulses (grape_lindblad_hvp.hip.h).  Touches nothing an evaluation or a getter reads: storage of its own, the timing
 // events and the statistics of the evaluation are left alone; d_flags is cleared by every launch group, as by every launch.
@@ -1988,55 +2118,34 @@ int open_hvp(grape_handle *h, int nv, const double *V, double *HV) {
     if (const char *why = h->ev.forward_stale()) return refuse_stale_forward(h, "grape_open_hvp", why);
     h->ev.tangent_overwritten();   // (the tangent storage of a forward half is overwritten)
     const auto t0 = std::chrono::steady_clock::now();
-    HIPCHK(h, hipSetDevice(h->device));
-    (void)hipGetLastError();
+    if (const int rc = second_order_begin(h)) return rc;
     int nd = 0;
-    const int rc = open_hvp_reserve(h, nv, &nd);
-    if (rc) return rc;
+    if (const int rc = open_hvp_reserve(h, nv, &nd)) return rc;
     const size_t K = (size_t)h->K, L = (size_t)h->L, LN = L * h->N_T;
     hipStream_t s = h->stream;
-    LindHvpArgs q{};
-    q.a = open_args(h);
-    q.a.f = o->d_out + 2 * K;   // sum_k w_k tau_k as the forward half reduced it (d_f belongs to the backward half)
-    q.a.ws = nullptr; q.a.tg = nullptr; q.a.stats = nullptr; q.a.rho = nullptr;
-    q.V = o->hv.d_hvV; q.dstore = o->hv.d_hvds; q.dtau = o->hv.d_hvdtau; q.dcoef = o->hv.d_hvdcoef; q.tg = o->hv.d_hvtg; q.ws = o->hv.d_hvws;
-    q.stats = o->hv.d_hvstats;
-    std::vector<unsigned long long> st;
-    double terms_fw = 0., terms_bw = 0., substeps = 0.;
+    LindHvpArgs q = open_hvp_args(h, 0);
+    WorkStats fw, bw;
     for (int j0 = 0; j0 < nv; j0 += nd) {
         const int ng = std::min(nd, nv - j0);
-        const size_t nst = 2 * (size_t)ng * (K + K * L);
+        const size_t nf = (size_t)ng * K;   // forward workgroups; nf L backward ones
         q.nd = ng;
         HIPCHK(h, hipMemcpyAsync(o->hv.d_hvV, V + (size_t)j0 * LN, (size_t)ng * LN * 8, hipMemcpyHostToDevice, s));
         HIPCHK(h, hipMemsetAsync(o->d_flags, 0, 8 * sizeof(int), s));
-        HIPCHK(h, hipMemsetAsync(o->hv.d_hvstats, 0, nst * sizeof(unsigned long long), s));
+        HIPCHK(h, hipMemsetAsync(o->hv.d_hvstats, 0, 2 * (nf + nf * L) * sizeof(unsigned long long), s));
         OPEN_LAUNCH(lind_hvp_forward_kernel, dim3((unsigned)K, (unsigned)ng), OPEN_HVF_THREADS, q)
         hipLaunchKernelGGL(lind_hvp_boundary_kernel, dim3((unsigned)ng), dim3(64), 0, s, q);
         OPEN_LAUNCH(lind_hvp_backward_kernel, dim3((unsigned)K, (unsigned)L, (unsigned)ng), OPEN_BWD_THREADS, q)
         HIPCHK(h, hipGetLastError());
-        // (H v)_j = -2 Re sum_k of the per-trajectory terms: the gradient's reduction, fixed order
-        for (int j = 0; j < ng; ++j)
-            hipLaunchKernelGGL(grad_reduce_kernel, dim3((unsigned)((LN + 15) / 16)), dim3(256), 0, s, o->hv.d_hvtg + (size_t)j * K * LN, h->K,
-                               (int)LN, o->hv.d_hvout + (size_t)j * LN, (const double2 *)nullptr);
+        reduce_directions(h, o->hv.d_hvtg, o->hv.d_hvout, ng);
         HIPCHK(h, hipGetLastError());
-        int flags[8] = {0};
-        st.assign(nst, 0ull);
         HIPCHK(h, hipMemcpyAsync(HV + (size_t)j0 * LN, o->hv.d_hvout, (size_t)ng * LN * 8, hipMemcpyDeviceToHost, s));
-        HIPCHK(h, hipMemcpyAsync(st.data(), o->hv.d_hvstats, nst * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-        HIPCHK(h, hipMemcpyAsync(flags, o->d_flags, sizeof(flags), hipMemcpyDeviceToHost, s));
-        HIPCHK(h, hipStreamSynchronize(s));
-        for (size_t w = 0; w < nst / 2; ++w) {
-            (w < (size_t)ng * K ? terms_fw : terms_bw) += (double)st[2 * w];
-            substeps += (double)st[2 * w + 1];
-        }
-        if (flags[0] & 16) {
+        if (const int rc = read_stats(h, o->hv.d_hvstats, nf, o->d_flags, &fw, nf * L, &bw)) return rc;
+        if (fw.taylor) {
             h->err = "grape_open_hvp: a series did not converge within 200 terms (direction group starting at " + std::to_string(j0) + ")";
             return GRAPE_ERR_TAYLOR;
         }
     }
-    o->hv.info[0] = terms_fw + terms_bw; o->hv.info[1] = substeps; o->hv.info[2] = (double)nd; o->hv.info[3] = (double)o->hv.store.mem.bytes();
-    o->hv.info[4] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    o->hv.info[5] = terms_fw; o->hv.info[6] = terms_bw;
+    fill_info(o->hv.info, fw.terms + bw.terms, fw.steps + bw.steps, nd, o->hv.store.mem.bytes(), t0, fw.terms, bw.terms);
     return GRAPE_OK;
 }
 
@@ -2044,8 +2153,6 @@ int open_hvp(grape_handle *h, int nv, const double *V, double *HV) {
 // grape_open_hvp_forward / grape_open_hvp_backward / grape_open_hvp_backward_chi: grape_open_hvp cut at its one
 // cross-trajectory dependency (grape_lindblad_hvp_split.hip.h)
 // ---------------------------------------------------------------------------------------
-typedef OpenCtx::HvpSplit OpenHvpSplit;
-
 // why this handle cannot take a split call (nullptr: it can); every test precedes the first HIP call
 const char *open_hvs_refusal(const grape_handle *h, bool builtin) {
     if (!h->open)
@@ -2058,83 +2165,29 @@ const char *open_hvs_refusal(const grape_handle *h, bool builtin) {
     return nullptr;
 }
 
-// the extras of the split calls for nv directions, in a store of their own
-int open_hvs_reserve(grape_handle *h, int nv) {
-    OpenHvpSplit &x = h->open->hvs;
-    if (nv <= x.cap) return GRAPE_OK;
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    x.mem.release(); x.cap = 0;
-    const size_t K = (size_t)h->K, m2 = 2 * (size_t)h->NP * h->NP, n = (size_t)nv;
-    hipError_t e = x.mem.alloc(&x.d_chi, K * m2);
-    if (e == hipSuccess) e = x.mem.alloc(&x.d_dchi, n * K * m2);
-    if (e == hipSuccess) e = x.mem.alloc(&x.d_ztarget, K * m2);
-    if (e == hipSuccess) e = x.mem.alloc(&x.d_drhoT, n * K * m2);
-    if (e == hipSuccess) e = x.mem.alloc(&x.d_ftot, (size_t)2);
-    if (e == hipSuccess) e = x.mem.alloc(&x.d_dftot, 2 * n);
-    if (e == hipSuccess) e = x.mem.alloc(&x.d_psums, 2 * n);
-    if (e == hipSuccess) e = hipMemsetAsync(x.d_ztarget, 0, K * m2 * 8, h->stream);
-    if (e != hipSuccess) {
-        x.mem.release();
-        (void)hipGetLastError();
-        h->err = std::string("grape_open_hvp_forward: storage of the split calls: ") + hipGetErrorString(e);
-        return GRAPE_ERR_HIP;
-    }
-    x.cap = nv;
-    return GRAPE_OK;
-}
-
 LindHvpArgs open_hvs_args(const grape_handle *h, int nv) {
-    const OpenCtx *o = h->open;
-    LindHvpArgs q{};
-    q.a = open_args(h);
-    q.a.f = o->hvs.d_ftot;   // the all-reduced sum_k w_k tau_k the caller passes
-    if (h->no_target) q.a.target = o->hvs.d_ztarget;
-    q.a.ws = nullptr; q.a.tg = nullptr; q.a.stats = nullptr; q.a.rho = nullptr;
-    q.V = o->hv.d_hvV; q.dstore = o->hv.d_hvds; q.dtau = o->hv.d_hvdtau; q.dcoef = o->hv.d_hvdcoef; q.tg = o->hv.d_hvtg; q.ws = o->hv.d_hvws;
-    q.stats = o->hv.d_hvstats;
-    q.nd = nv;
+    LindHvpArgs q = open_hvp_args(h, nv);
+    q.a.f = h->open->hvs.d_ftot;   // the all-reduced sum_k w_k tau_k the caller passes
+    if (h->no_target) q.a.target = h->open->hvs.d_ztarget;
     return q;
-}
-
-// the statistics of one half (which = 0: the nv K forward workgroups, 1: the nv K L backward workgroups) and the flag word
-int open_hvs_stats(grape_handle *h, int nv, int which, double *terms, double *steps, bool *taylor) {
-    OpenCtx *o = h->open;
-    const size_t nf = (size_t)nv * h->K, n = which ? nf * h->L : nf;
-    std::vector<unsigned long long> st(2 * n, 0ull);
-    int flags[8] = {0};
-    HIPCHK(h, hipMemcpyAsync(st.data(), o->hv.d_hvstats + (which ? 2 * nf : 0), 2 * n * sizeof(unsigned long long), hipMemcpyDeviceToHost,
-                             h->stream));
-    HIPCHK(h, hipMemcpyAsync(flags, o->d_flags, sizeof(flags), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    *terms = 0.; *steps = 0.;
-    for (size_t w = 0; w < n; ++w) { *terms += (double)st[2 * w]; *steps += (double)st[2 * w + 1]; }
-    *taylor = (flags[0] & 16) != 0;
-    return GRAPE_OK;
 }
 
 int open_hvs_forward(grape_handle *h, int nv, const double *V, double *dtau, double *dsums, double *drhoT) {
     OpenCtx *o = h->open;
-    OpenHvpSplit &x = o->hvs;
+    SplitExtras<double> &x = o->hvs;
     if (const char *why = h->ev.forward_stale()) return refuse_stale_forward(h, "grape_open_hvp_forward", why);
     const auto t0 = std::chrono::steady_clock::now();
-    HIPCHK(h, hipSetDevice(h->device));
-    (void)hipGetLastError();
-    // all nv directions stay resident between the halves: the budget of grape_open_hvp decides how many that can be
-    int nd = 0;
-    const hipError_t ep = o->hv.store.plan(nv, open_hvp_bytes_per_direction(h), 8.0 * 1073741824.0, &nd);
-    if (ep != hipSuccess) { h->err = std::string("hipMemGetInfo(&free_b, &total_b): ") + hipGetErrorString(ep); return GRAPE_ERR_HIP; }
-    if (nd < nv) {
-        h->err = "grape_open_hvp_forward: nv = " + std::to_string(nv) + " directions do not fit the storage budget of grape_open_hvp (8 GB, "
-                 "half of the free memory, GRAPE_HVP_DIRS): at most " + std::to_string(nd) + " stay resident between the halves; loop over "
-                 "groups of that size";
-        return GRAPE_ERR_INVALID;
-    }
-    h->ev.split_forward_begun();   // (failed until this half has succeeded: the tangent storage is being overwritten)
-    int rc = open_hvp_reserve(h, nv, &nd);
-    if (rc) return rc;
-    rc = open_hvs_reserve(h, nv);
-    if (rc) return rc;
     const size_t K = (size_t)h->K, L = (size_t)h->L, LN = L * h->N_T, m2 = 2 * (size_t)h->NP * h->NP, nn = (size_t)h->N * h->N;
+    int rc = second_order_begin(h);
+    if (rc) return rc;
+    rc = split_resident(h, o->hv.store, nv, open_hvp_bytes_per_direction(h), "grape_open_hvp_forward", "grape_open_hvp");
+    if (rc) return rc;
+    h->ev.split_forward_begun();   // (failed until this half has succeeded: the tangent storage is being overwritten)
+    int nd = 0;
+    rc = open_hvp_reserve(h, nv, &nd);
+    if (rc) return rc;
+    rc = split_reserve(h, x, nv, K * m2, K * m2, "grape_open_hvp_forward");
+    if (rc) return rc;
     hipStream_t s = h->stream;
     const LindHvpArgs q = open_hvs_args(h, nv);
     HIPCHK(h, hipMemcpyAsync(o->hv.d_hvV, V, (size_t)nv * LN * 8, hipMemcpyHostToDevice, s));
@@ -2146,16 +2199,15 @@ int open_hvs_forward(grape_handle *h, int nv, const double *V, double *dtau, dou
     if (dtau) HIPCHK(h, hipMemcpyAsync(dtau, o->hv.d_hvdtau, (size_t)nv * K * 16, hipMemcpyDeviceToHost, s));
     if (dsums) HIPCHK(h, hipMemcpyAsync(dsums, x.d_psums, (size_t)nv * 16, hipMemcpyDeviceToHost, s));
     if (drhoT) {   // rho'_k(T): row N_T of every (direction, trajectory) block, packed on the device, one copy on this stream
-        hipLaunchKernelGGL(lind_hvp_final_tangent_kernel, dim3((unsigned)((size_t)nv * K)), dim3(256), 0, s, q, (int)m2, x.d_drhoT);
+        hipLaunchKernelGGL(lind_hvp_final_tangent_kernel, dim3((unsigned)((size_t)nv * K)), dim3(256), 0, s, q, (int)m2, x.d_dfinal);
         HIPCHK(h, hipGetLastError());
         x.stage.resize((size_t)nv * K * m2);
-        HIPCHK(h, hipMemcpyAsync(x.stage.data(), x.d_drhoT, (size_t)nv * K * m2 * 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(h, hipMemcpyAsync(x.stage.data(), x.d_dfinal, (size_t)nv * K * m2 * 8, hipMemcpyDeviceToHost, s));
     }
-    double terms = 0., steps = 0.;
-    bool taylor = false;
-    rc = open_hvs_stats(h, nv, 0, &terms, &steps, &taylor);
+    WorkStats w;
+    rc = read_stats(h, o->hv.d_hvstats, (size_t)nv * K, o->d_flags, &w);
     if (rc) return rc;
-    if (taylor) { h->err = "grape_open_hvp_forward: a series did not converge within 200 terms"; return GRAPE_ERR_TAYLOR; }
+    if (w.taylor) { h->err = "grape_open_hvp_forward: a series did not converge within 200 terms"; return GRAPE_ERR_TAYLOR; }
     if (drhoT)
         for (size_t r = 0; r < (size_t)nv * K; ++r) open_from_planar(x.stage.data() + r * m2, h->N, h->NP, drhoT + 2 * r * nn);
     if (h->no_target) {   // tau is NaN on such a handle, so are its derivatives
@@ -2163,11 +2215,8 @@ int open_hvs_forward(grape_handle *h, int nv, const double *V, double *dtau, dou
         if (dtau) std::fill(dtau, dtau + 2 * (size_t)nv * K, nan);
         if (dsums) std::fill(dsums, dsums + 2 * (size_t)nv, nan);
     }
-    h->ev.split_forward_succeeded(nv, terms, steps);
-    double *info = o->hv.info;
-    info[0] = terms; info[1] = steps; info[2] = (double)nv; info[3] = (double)(o->hv.store.mem.bytes() + x.mem.bytes());
-    info[4] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    info[5] = terms; info[6] = 0.;
+    h->ev.split_forward_succeeded(nv, w.terms, w.steps);
+    fill_info(o->hv.info, w.terms, w.steps, nv, o->hv.store.mem.bytes() + x.mem.bytes(), t0, w.terms, 0.);
     return GRAPE_OK;
 }
 
@@ -2183,9 +2232,8 @@ int open_hvs_backward(grape_handle *h, const char *call, int nv, const double *f
                       const double *dchi, double *HV) {
     const auto t0 = std::chrono::steady_clock::now();
     OpenCtx *o = h->open;
-    OpenHvpSplit &x = o->hvs;
-    HIPCHK(h, hipSetDevice(h->device));
-    (void)hipGetLastError();
+    SplitExtras<double> &x = o->hvs;
+    if (const int rc = second_order_begin(h)) return rc;
     const size_t K = (size_t)h->K, L = (size_t)h->L, LN = L * h->N_T, m2 = 2 * (size_t)h->NP * h->NP, nn = (size_t)h->N * h->N;
     hipStream_t s = h->stream;
     const LindHvpArgs q = open_hvs_args(h, nv);
@@ -2209,22 +2257,14 @@ int open_hvs_backward(grape_handle *h, const char *call, int nv, const double *f
         OPEN_LAUNCH(lind_hvp_backward_kernel, grid, OPEN_BWD_THREADS, q)
     }
     HIPCHK(h, hipGetLastError());
-    // (H v)_j = -2 Re sum_k of the per-trajectory terms: the gradient's reduction, fixed order
-    for (int j = 0; j < nv; ++j)
-        hipLaunchKernelGGL(grad_reduce_kernel, dim3((unsigned)((LN + 15) / 16)), dim3(256), 0, s, o->hv.d_hvtg + (size_t)j * K * LN, h->K,
-                           (int)LN, o->hv.d_hvout + (size_t)j * LN, (const double2 *)nullptr);
+    reduce_directions(h, o->hv.d_hvtg, o->hv.d_hvout, nv);
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipMemcpyAsync(HV, o->hv.d_hvout, (size_t)nv * LN * 8, hipMemcpyDeviceToHost, s));
-    double terms = 0., steps = 0.;
-    bool taylor = false;
-    const int rc = open_hvs_stats(h, nv, 1, &terms, &steps, &taylor);
-    if (rc) return rc;
-    if (taylor) { h->err = std::string(call) + ": a series did not converge within 200 terms"; return GRAPE_ERR_TAYLOR; }
-    double *info = o->hv.info;
-    info[0] = h->ev.terms_fw + terms; info[1] = h->ev.steps_fw + steps; info[2] = (double)nv;
-    info[3] = (double)(o->hv.store.mem.bytes() + x.mem.bytes());
-    info[4] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    info[5] = h->ev.terms_fw; info[6] = terms;
+    WorkStats w;   // (the nv K L backward workgroups, behind the forward ones)
+    if (const int rc = read_stats(h, o->hv.d_hvstats + 2 * (size_t)nv * K, (size_t)nv * K * L, o->d_flags, &w)) return rc;
+    if (w.taylor) { h->err = std::string(call) + ": a series did not converge within 200 terms"; return GRAPE_ERR_TAYLOR; }
+    fill_info(o->hv.info, h->ev.terms_fw + w.terms, h->ev.steps_fw + w.steps, nv, o->hv.store.mem.bytes() + x.mem.bytes(), t0, h->ev.terms_fw,
+              w.terms);
     return GRAPE_OK;
 }
 
@@ -5302,13 +5342,12 @@ int hvp_reserve(grape_handle *h, int nv, int *dirs) {
     });
 }
 
-template <int NP>
-void hvp_launch(const HvpArgs &a, int nd, int nct, hipStream_t s) {
-    const dim3 grid((unsigned)a.K, (unsigned)nd), blk(4 * NP);
-    hipLaunchKernelGGL(hvp_forward_kernel<NP>, grid, blk, 0, s, a);
-    hipLaunchKernelGGL(hvp_boundary_kernel, dim3((unsigned)nd), dim3(64), 0, s, a);
-    if (nct == 1) hipLaunchKernelGGL((hvp_backward_kernel<NP, 1>), grid, blk, 0, s, a);
-    else hipLaunchKernelGGL((hvp_backward_kernel<NP, 2>), grid, blk, 0, s, a);
+// the arguments of the kernels: the stored evaluation, the tangent storage; the flag word sits behind the statistics of the capacity
+HvpArgs hvp_args(const grape_handle *h) {
+    HvpArgs a = closed_series_args(h);
+    a.V = h->hvp.d_hvV; a.dpsi = h->hvp.d_hvdpsi; a.dtau = h->hvp.d_hvdtau; a.dcoef = h->hvp.d_hvdcoef; a.tg = h->hvp.d_hvtg; a.ws = h->hvp.d_hvws;
+    a.flags = (int *)(h->hvp.d_hvstats + 4 * (size_t)h->hvp.store.cap * h->K); a.stats = h->hvp.d_hvstats;
+    return a;
 }
 
 // why this handle cannot give H v (nullptr: it can); every test precedes the first HIP call
@@ -5332,61 +5371,38 @@ int grape_hvp(grape_handle *h, int nv, const double *V, double *HV) try {
     if (const char *why = hvp_refusal(h)) { h->err = std::string("grape_hvp: ") + why; return GRAPE_ERR_INVALID; }
     h->ev.tangent_overwritten();   // (the tangent storage of a forward half is overwritten)
     const auto t0 = std::chrono::steady_clock::now();
-    HIPCHK(h, hipSetDevice(h->device));
-    if (h->foreign_stream) HIPCHK(h, hipDeviceSynchronize());   // (see grape_get_time_gradient)
-    (void)hipGetLastError();
+    if (const int rc = second_order_begin(h)) return rc;
     int nd = 0;
-    int rc = hvp_reserve(h, nv, &nd);
-    if (rc) return rc;
+    if (const int rc = hvp_reserve(h, nv, &nd)) return rc;
     const size_t LN = (size_t)h->L * h->N_T, K = (size_t)h->K;
     hipStream_t s = h->stream;
-    int *d_flag = (int *)(h->hvp.d_hvstats + 4 * (size_t)h->hvp.store.cap * K);
-    HvpArgs a{};
-    a.H0f = h->d_H0f; a.Hcf = h->d_Hcf; a.eps = h->d_eps; a.shape = h->d_shape; a.dts = h->d_dts; a.rb = h->d_rb;
-    a.V = h->hvp.d_hvV; a.fw = h->d_fw; a.target = h->d_target; a.weights = h->d_weights;
-    a.tau = (const double2 *)h->d_out; a.f = h->d_out + 2 * K;
-    a.dpsi = h->hvp.d_hvdpsi; a.dtau = h->hvp.d_hvdtau; a.dcoef = h->hvp.d_hvdcoef; a.tg = h->hvp.d_hvtg; a.ws = h->hvp.d_hvws;
-    a.flags = d_flag; a.stats = h->hvp.d_hvstats;
-    a.tol = h->series_tol; a.theta = h->series_theta;
-    a.K = h->K; a.K_total = h->K_total; a.L = h->L; a.N = h->N; a.N_T = h->N_T; a.functional = h->p.functional;
-    a.hc_per_traj = h->p.hc_per_traj;
+    const HvpArgs a = hvp_args(h);
     const int nct = 2 + 2 * h->L > 16 ? 2 : 1;
-    std::vector<unsigned long long> st;
-    double terms = 0., substeps = 0., terms_fw = 0.;
+    WorkStats fw, bw;
     for (int j0 = 0; j0 < nv; j0 += nd) {
         const int ng = std::min(nd, nv - j0);
         HIPCHK(h, hipMemcpyAsync(h->hvp.d_hvV, V + (size_t)j0 * LN, (size_t)ng * LN * 8, hipMemcpyHostToDevice, s));
         HIPCHK(h, hipMemsetAsync(h->hvp.d_hvstats, 0, (4 * (size_t)h->hvp.store.cap * K + 1) * 8, s));
-        switch (h->NP) {
-            case 16: hvp_launch<16>(a, ng, nct, s); break;
-            case 32: hvp_launch<32>(a, ng, nct, s); break;
-            case 48: hvp_launch<48>(a, ng, nct, s); break;
-            default: hvp_launch<64>(a, ng, nct, s); break;
-        }
+        with_np(h->NP, [&](auto np) {
+            constexpr int NP = decltype(np)::value;
+            const dim3 grid((unsigned)K, (unsigned)ng), blk(4 * NP);
+            hipLaunchKernelGGL(hvp_forward_kernel<NP>, grid, blk, 0, s, a);
+            hipLaunchKernelGGL(hvp_boundary_kernel, dim3((unsigned)ng), dim3(64), 0, s, a);
+            if (nct == 1) hipLaunchKernelGGL((hvp_backward_kernel<NP, 1>), grid, blk, 0, s, a);
+            else hipLaunchKernelGGL((hvp_backward_kernel<NP, 2>), grid, blk, 0, s, a);
+        });
         HIPCHK(h, hipGetLastError());
-        // (H v)_j = -2 Re sum_k of the per-trajectory terms: the gradient's reduction, fixed order
-        for (int j = 0; j < ng; ++j)
-            hipLaunchKernelGGL(grad_reduce_kernel, dim3((unsigned)((LN + 15) / 16)), dim3(256), 0, s, h->hvp.d_hvtg + (size_t)j * K * LN, h->K,
-                               (int)LN, h->hvp.d_hvout + (size_t)j * LN, (const double2 *)nullptr);
+        reduce_directions(h, h->hvp.d_hvtg, h->hvp.d_hvout, ng);
         HIPCHK(h, hipGetLastError());
         HIPCHK(h, hipMemcpyAsync(HV + (size_t)j0 * LN, h->hvp.d_hvout, (size_t)ng * LN * 8, hipMemcpyDeviceToHost, s));
-        st.assign(4 * (size_t)ng * K + 1, 0ull);
-        // (the statistics of this group: forward workgroups, then backward workgroups; the flag word sits behind the capacity)
-        HIPCHK(h, hipMemcpyAsync(st.data(), h->hvp.d_hvstats, 4 * (size_t)ng * K * 8, hipMemcpyDeviceToHost, s));
-        HIPCHK(h, hipMemcpyAsync(&st[4 * (size_t)ng * K], d_flag, 8, hipMemcpyDeviceToHost, s));
-        HIPCHK(h, hipStreamSynchronize(s));
-        for (size_t q = 0; q < 2 * (size_t)ng * K; ++q) {
-            terms += (double)st[2 * q]; substeps += (double)st[2 * q + 1];
-            if (q < (size_t)ng * K) terms_fw += (double)st[2 * q];
-        }
-        if ((int)(st[4 * (size_t)ng * K] & 0xffffffffull) & 16) {
+        // (the statistics of this group: forward workgroups, then backward workgroups)
+        if (const int rc = read_stats(h, a.stats, (size_t)ng * K, a.flags, &fw, (size_t)ng * K, &bw)) return rc;
+        if (fw.taylor) {
             h->err = "grape_hvp: a series did not converge within 200 terms (direction group starting at " + std::to_string(j0) + ")";
             return GRAPE_ERR_TAYLOR;
         }
     }
-    h->hvp.info[0] = terms; h->hvp.info[1] = substeps; h->hvp.info[2] = (double)nd; h->hvp.info[3] = (double)h->hvp.store.mem.bytes();
-    h->hvp.info[4] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    h->hvp.info[5] = terms_fw; h->hvp.info[6] = terms - terms_fw;
+    fill_info(h->hvp.info, fw.terms + bw.terms, fw.steps + bw.steps, nd, h->hvp.store.mem.bytes(), t0, fw.terms, bw.terms);
     return GRAPE_OK;
 }
 GRAPE_BARRIER(h ? &h->err : &g_create_error)
@@ -5443,26 +5459,6 @@ int hess_reserve(grape_handle *h, int *traj) {
     return GRAPE_OK;
 }
 
-template <int NP>
-void hess_launch_seeds(const HessArgs &a, int rows, hipStream_t s) {
-    hipLaunchKernelGGL(hess_forward_seeds_kernel<NP>, dim3((unsigned)a.s.K, (unsigned)rows), dim3(4 * NP), 0, s, a);
-}
-template <int NP>
-void hess_launch_backward(const HessArgs &a, hipStream_t s) {
-    hipLaunchKernelGGL(hess_backward_seeds_kernel<NP>, dim3((unsigned)a.s.K), dim3(4 * NP), 0, s, a);
-}
-template <int NP>
-void hess_launch_fan(const HessArgs &a, int nblk, int ntraj, hipStream_t s) {
-    hipLaunchKernelGGL(hess_fan_kernel<NP>, dim3((unsigned)nblk, (unsigned)ntraj), dim3(4 * NP), 0, s, a);
-}
-#define HESS_DISPATCH(fn, ...)                                   \
-    switch (h->NP) {                                             \
-        case 16: fn<16>(__VA_ARGS__); break;                     \
-        case 32: fn<32>(__VA_ARGS__); break;                     \
-        case 48: fn<48>(__VA_ARGS__); break;                     \
-        default: fn<64>(__VA_ARGS__); break;                     \
-    }
-
 // why this handle cannot give the Hessian (nullptr: it can); every test precedes the first HIP call
 const char *hess_refusal(const grape_handle *h) {
     if (h->open) return "open-system handles are out of scope (DESIGN.md 25): grape_open_hvp with unit directions is the route";
@@ -5479,17 +5475,6 @@ const char *hess_refusal(const grape_handle *h) {
     return h->ev.forward_stale() ? StoredEval::no_forward_on_grid : nullptr;
 }
 
-// the statistics of `nwg` workgroups and the flag word of the launch before, summed on the host
-int hess_collect(grape_handle *h, size_t nwg, std::vector<unsigned long long> &st, double *terms, double *steps, bool *taylor) {
-    hipStream_t s = h->stream;
-    st.assign(2 * nwg + 1, 0ull);
-    HIPCHK(h, hipMemcpyAsync(st.data(), h->hess.d_stats, (2 * nwg + 1) * 8, hipMemcpyDeviceToHost, s));
-    HIPCHK(h, hipStreamSynchronize(s));
-    for (size_t q = 0; q < nwg; ++q) { *terms += (double)st[2 * q]; *steps += (double)st[2 * q + 1]; }
-    if ((int)(st[2 * nwg] & 0xffffffffull) & 16) *taylor = true;
-    return GRAPE_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -5499,58 +5484,52 @@ int grape_hessian(grape_handle *h, double *H) try {
     if (!H) { h->err = "grape_hessian: H must not be NULL"; return GRAPE_ERR_INVALID; }
     if (const char *why = hess_refusal(h)) { h->err = std::string("grape_hessian: ") + why; return GRAPE_ERR_INVALID; }
     const auto t0 = std::chrono::steady_clock::now();
-    HIPCHK(h, hipSetDevice(h->device));
-    if (h->foreign_stream) HIPCHK(h, hipDeviceSynchronize());   // (see grape_get_time_gradient)
-    (void)hipGetLastError();
-    int ntraj = 0;
-    int rc = hess_reserve(h, &ntraj);
-    if (rc) return rc;
+    int ntraj = 0, rc = second_order_begin(h);
+    if (rc || (rc = hess_reserve(h, &ntraj))) return rc;
     auto &v = h->hess;
     const size_t K = (size_t)h->K, P = (size_t)h->L * h->N_T, nblk = (P + 15) / 16;
     const int rows = hess_seed_rows(h);
     hipStream_t s = h->stream;
     HessArgs a{};
-    a.s.H0f = h->d_H0f; a.s.Hcf = h->d_Hcf; a.s.eps = h->d_eps; a.s.shape = h->d_shape; a.s.dts = h->d_dts; a.s.rb = h->d_rb;
-    a.s.fw = h->d_fw; a.s.target = h->d_target; a.s.weights = h->d_weights;
-    a.s.tau = (const double2 *)h->d_out; a.s.f = h->d_out + 2 * K;
-    a.s.tol = h->series_tol; a.s.theta = h->series_theta;
-    a.s.K = h->K; a.s.K_total = h->K_total; a.s.L = h->L; a.s.N = h->N; a.s.N_T = h->N_T; a.s.functional = h->p.functional;
-    a.s.hc_per_traj = h->p.hc_per_traj;
+    a.s = closed_series_args(h);
     a.av = v.d_a; a.bv = v.d_b; a.T = v.d_T; a.Sd = v.d_Sd; a.strip = v.d_strip; a.acc = v.d_acc; a.H = v.d_H;
     a.stats = v.d_stats;
-    std::vector<unsigned long long> st;
-    double terms_f = 0., terms_b = 0., terms_fan = 0., steps = 0.;
+    WorkStats seeds_f, seeds_b, fan;
     bool taylor = false;
-    // the flag word sits behind the statistics of the launch
-    auto begin = [&](size_t nwg) {
+    // one launch of nwg workgroups: the flag word sits behind the statistics of the launch
+    auto run = [&](size_t nwg, WorkStats *w, auto &&launch) -> int {
         a.s.flags = (int *)(v.d_stats + 2 * nwg);
-        return hipMemsetAsync(v.d_stats, 0, (2 * nwg + 1) * 8, s);
+        HIPCHK(h, hipMemsetAsync(v.d_stats, 0, (2 * nwg + 1) * 8, s));
+        with_np(h->NP, launch);
+        HIPCHK(h, hipGetLastError());
+        const int rs = read_stats(h, v.d_stats, nwg, a.s.flags, w);
+        taylor = w->taylor;
+        return rs;
     };
-    {   // forward seeds
-        const size_t nwg = K * (size_t)rows;
-        HIPCHK(h, begin(nwg));
-        a.ws = v.d_wsf;
-        HESS_DISPATCH(hess_launch_seeds, a, rows, s)
-        HIPCHK(h, hipGetLastError());
-        if ((rc = hess_collect(h, nwg, st, &terms_f, &steps, &taylor))) return rc;
-    }
+    a.ws = v.d_wsf;
+    rc = run(K * (size_t)rows, &seeds_f, [&](auto np) {
+        constexpr int NP = decltype(np)::value;
+        hipLaunchKernelGGL(hess_forward_seeds_kernel<NP>, dim3((unsigned)K, (unsigned)rows), dim3(4 * NP), 0, s, a);
+    });
+    if (rc) return rc;
     if (!taylor) {   // backward seeds (the step matrices of K workgroups fit those of the forward seeds)
-        HIPCHK(h, begin(K));
-        HESS_DISPATCH(hess_launch_backward, a, s)
-        HIPCHK(h, hipGetLastError());
-        if ((rc = hess_collect(h, K, st, &terms_b, &steps, &taylor))) return rc;
+        rc = run(K, &seeds_b, [&](auto np) {
+            constexpr int NP = decltype(np)::value;
+            hipLaunchKernelGGL(hess_backward_seeds_kernel<NP>, dim3((unsigned)K), dim3(4 * NP), 0, s, a);
+        });
+        if (rc) return rc;
     }
     if (!taylor) HIPCHK(h, hipMemsetAsync(v.d_acc, 0, P * P * 8, s));
     const unsigned eblocks = (unsigned)((P * P + 255) / 256);
     for (int k0 = 0; k0 < h->K && !taylor; k0 += ntraj) {   // the fan, pass by pass
         const int ng = std::min(ntraj, h->K - k0);
-        const size_t nwg = (size_t)ng * nblk;
-        HIPCHK(h, begin(nwg));
         a.ws = v.d_wsfan; a.k0 = k0;
-        HESS_DISPATCH(hess_launch_fan, a, (int)nblk, ng, s)
-        hipLaunchKernelGGL(hess_accumulate_kernel, dim3(eblocks), dim3(256), 0, s, a, ng);
-        HIPCHK(h, hipGetLastError());
-        if ((rc = hess_collect(h, nwg, st, &terms_fan, &steps, &taylor))) return rc;
+        rc = run((size_t)ng * nblk, &fan, [&](auto np) {
+            constexpr int NP = decltype(np)::value;
+            hipLaunchKernelGGL(hess_fan_kernel<NP>, dim3((unsigned)nblk, (unsigned)ng), dim3(4 * NP), 0, s, a);
+            hipLaunchKernelGGL(hess_accumulate_kernel, dim3(eblocks), dim3(256), 0, s, a, ng);
+        });
+        if (rc) return rc;
     }
     if (taylor) {
         h->err = "grape_hessian: a series did not converge within 200 terms";
@@ -5560,9 +5539,9 @@ int grape_hessian(grape_handle *h, double *H) try {
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipMemcpyAsync(H, v.d_H, P * P * 8, hipMemcpyDeviceToHost, s));
     HIPCHK(h, hipStreamSynchronize(s));
-    v.info[0] = terms_f + terms_b + terms_fan; v.info[1] = steps; v.info[2] = (double)ntraj; v.info[3] = (double)v.store.mem.bytes();
-    v.info[4] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    v.info[5] = terms_f; v.info[6] = terms_b; v.info[7] = terms_fan;
+    fill_info(v.info, seeds_f.terms + seeds_b.terms + fan.terms, seeds_f.steps + seeds_b.steps + fan.steps, ntraj, v.store.mem.bytes(), t0,
+              seeds_f.terms, seeds_b.terms);
+    v.info[7] = fan.terms;
     return GRAPE_OK;
 }
 GRAPE_BARRIER(h ? &h->err : &g_create_error)
@@ -5671,74 +5650,52 @@ const char *open_hess_refusal(const grape_handle *h) {
 int open_hessian(grape_handle *h, double *H) {
     OpenCtx *o = h->open;
     const auto t0 = std::chrono::steady_clock::now();
-    HIPCHK(h, hipSetDevice(h->device));
-    (void)hipGetLastError();
     const int cb = open_hess_cols(h);
-    int ntraj = 0;
-    int rc = open_hess_reserve(h, cb, &ntraj);
-    if (rc) return rc;
+    int ntraj = 0, rc = second_order_begin(h);
+    if (rc || (rc = open_hess_reserve(h, cb, &ntraj))) return rc;
     auto &v = o->hess;
     const size_t K = (size_t)h->K, L = (size_t)h->L, P = L * h->N_T, nblk = (P + cb - 1) / cb, pairs = L * (L + 1) / 2;
-    const int rows = open_hess_seed_rows(h);
+    const int rows = open_hess_seed_rows(h), brows = open_hess_back_rows(h);
     hipStream_t s = h->stream;
     LindHessArgs q{};
-    q.a = open_args(h);
-    q.a.f = o->d_out + 2 * K;   // sum_k w_k tau_k as the forward half reduced it (d_f belongs to the backward half)
-    q.a.ws = nullptr; q.a.tg = nullptr; q.a.stats = nullptr; q.a.rho = nullptr;
+    q.a = open_stored_args(h);
     q.av = v.d_a; q.bv = v.d_b; q.th = v.d_th; q.T = v.d_T; q.Sd = v.d_Sd; q.strip = v.d_strip; q.stats = v.d_stats; q.cb = cb;
     HessArgs a{};   // what hess_accumulate_kernel and hess_finish_kernel read: sizes, weights, functional, tau, f, T, Sd, strips
     a.s.weights = o->d_weights; a.s.tau = (const double2 *)o->d_out; a.s.f = o->d_out + 2 * K;
     a.s.K = h->K; a.s.K_total = h->K_total; a.s.L = h->L; a.s.N = h->N; a.s.N_T = h->N_T; a.s.functional = h->p.functional;
     a.T = v.d_T; a.Sd = v.d_Sd; a.strip = v.d_strip; a.acc = v.d_acc; a.H = v.d_H;
-    std::vector<unsigned long long> st;
-    double terms[3] = {0., 0., 0.}, steps[3] = {0., 0., 0.};
+    WorkStats w[3];   // forward seeds | the bare target chain and the backward seeds | fan
     bool taylor = false;
-    // the flag word sits behind the statistics of the launch
-    auto begin = [&](size_t nwg) {
+    // one launch of nwg workgroups: the flag word sits behind the statistics of the launch
+    auto run = [&](size_t nwg, int which, auto &&launch) -> int {
         q.a.flags = (int *)(v.d_stats + 2 * nwg);
-        return hipMemsetAsync(v.d_stats, 0, (2 * nwg + 1) * 8, s);
+        HIPCHK(h, hipMemsetAsync(v.d_stats, 0, (2 * nwg + 1) * 8, s));
+        launch();
+        HIPCHK(h, hipGetLastError());
+        const int rs = read_stats(h, v.d_stats, nwg, q.a.flags, &w[which]);
+        taylor = w[which].taylor;
+        return rs;
     };
-    auto collect = [&](size_t nwg, int which) -> int {
-        st.assign(2 * nwg + 1, 0ull);
-        HIPCHK(h, hipMemcpyAsync(st.data(), v.d_stats, (2 * nwg + 1) * 8, hipMemcpyDeviceToHost, s));
-        HIPCHK(h, hipStreamSynchronize(s));
-        for (size_t w = 0; w < nwg; ++w) { terms[which] += (double)st[2 * w]; steps[which] += (double)st[2 * w + 1]; }
-        if ((int)(st[2 * nwg] & 0xffffffffull) & 16) taylor = true;
-        return (int)GRAPE_OK;
-    };
-    {   // forward seeds
-        const size_t nwg = K * (size_t)rows * L;
-        HIPCHK(h, begin(nwg));
-        q.ws = v.d_wsseed;
+    q.ws = v.d_wsseed;
+    rc = run(K * (size_t)rows * L, 0, [&] {
         OPEN_LAUNCH(lind_hess_forward_seeds_kernel, dim3((unsigned)K, (unsigned)rows, (unsigned)L), OPEN_FWD_THREADS, q)
-        HIPCHK(h, hipGetLastError());
-        if ((rc = collect(nwg, 0))) return rc;
-    }
-    if (!taylor) {   // the bare target chain (counted with the backward seeds)
-        HIPCHK(h, begin(K));
-        OPEN_LAUNCH(lind_hess_theta_kernel, dim3((unsigned)K), OPEN_FWD_THREADS, q)
-        HIPCHK(h, hipGetLastError());
-        if ((rc = collect(K, 1))) return rc;
-    }
-    if (!taylor) {   // backward seeds
-        const int brows = open_hess_back_rows(h);
-        const size_t nwg = K * pairs * (size_t)brows;
-        HIPCHK(h, begin(nwg));
-        OPEN_LAUNCH(lind_hess_backward_seeds_kernel, dim3((unsigned)K, (unsigned)pairs, (unsigned)brows), OPEN_BWD_THREADS, q)
-        HIPCHK(h, hipGetLastError());
-        if ((rc = collect(nwg, 1))) return rc;
-    }
+    });
+    if (!rc && !taylor) rc = run(K, 1, [&] { OPEN_LAUNCH(lind_hess_theta_kernel, dim3((unsigned)K), OPEN_FWD_THREADS, q) });
+    if (!rc && !taylor)
+        rc = run(K * pairs * (size_t)brows, 1, [&] {
+            OPEN_LAUNCH(lind_hess_backward_seeds_kernel, dim3((unsigned)K, (unsigned)pairs, (unsigned)brows), OPEN_BWD_THREADS, q)
+        });
+    if (rc) return rc;
     if (!taylor) HIPCHK(h, hipMemsetAsync(v.d_acc, 0, P * P * 8, s));
     const unsigned eblocks = (unsigned)((P * P + 255) / 256);
     for (int k0 = 0; k0 < h->K && !taylor; k0 += ntraj) {   // the fan, pass by pass
         const int ng = std::min(ntraj, h->K - k0);
-        const size_t nwg = (size_t)ng * nblk;
-        HIPCHK(h, begin(nwg));
         q.ws = v.d_wsfan; q.k0 = k0;
-        OPEN_LAUNCH(lind_hess_fan_kernel, dim3((unsigned)nblk, (unsigned)ng), OPEN_FWD_THREADS, q)
-        hipLaunchKernelGGL(hess_accumulate_kernel, dim3(eblocks), dim3(256), 0, s, a, ng);
-        HIPCHK(h, hipGetLastError());
-        if ((rc = collect(nwg, 2))) return rc;
+        rc = run((size_t)ng * nblk, 2, [&] {
+            OPEN_LAUNCH(lind_hess_fan_kernel, dim3((unsigned)nblk, (unsigned)ng), OPEN_FWD_THREADS, q)
+            hipLaunchKernelGGL(hess_accumulate_kernel, dim3(eblocks), dim3(256), 0, s, a, ng);
+        });
+        if (rc) return rc;
     }
     if (taylor) {
         h->err = "grape_open_hessian: a series did not converge within 200 terms";
@@ -5748,11 +5705,9 @@ int open_hessian(grape_handle *h, double *H) {
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipMemcpyAsync(H, v.d_H, P * P * 8, hipMemcpyDeviceToHost, s));
     HIPCHK(h, hipStreamSynchronize(s));
-    v.info[0] = terms[0] + terms[1] + terms[2]; v.info[1] = steps[0] + steps[1] + steps[2]; v.info[2] = (double)ntraj;
-    v.info[3] = (double)v.store.mem.bytes();
-    v.info[4] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    v.info[5] = terms[0]; v.info[6] = terms[1]; v.info[7] = terms[2];
-    v.info[8] = steps[0]; v.info[9] = steps[1]; v.info[10] = steps[2]; v.info[11] = (double)cb;
+    fill_info(v.info, w[0].terms + w[1].terms + w[2].terms, w[0].steps + w[1].steps + w[2].steps, ntraj, v.store.mem.bytes(), t0, w[0].terms,
+              w[1].terms);
+    v.info[7] = w[2].terms; v.info[8] = w[0].steps; v.info[9] = w[1].steps; v.info[10] = w[2].steps; v.info[11] = (double)cb;
     return GRAPE_OK;
 }
 
@@ -5835,12 +5790,7 @@ int expect_single(grape_handle *h, int M, const double *ops, int ops_per_traj, d
         a.store = h->open->d_store; a.ops = x.d_ops; a.stride_k = ops_per_traj ? (size_t)M * m2 : 0; a.out = x.d_res;
         a.N = h->N; a.N_T = h->N_T; a.M = M;
         const dim3 grid((unsigned)(K * pts)), blk(EXPECT_NTH);
-        switch (h->NP) {
-        case 16: hipLaunchKernelGGL(expect_open_kernel<16>, grid, blk, 0, s, a); break;
-        case 32: hipLaunchKernelGGL(expect_open_kernel<32>, grid, blk, 0, s, a); break;
-        case 48: hipLaunchKernelGGL(expect_open_kernel<48>, grid, blk, 0, s, a); break;
-        default: hipLaunchKernelGGL(expect_open_kernel<64>, grid, blk, 0, s, a); break;
-        }
+        with_np(h->NP, [&](auto np) { hipLaunchKernelGGL(expect_open_kernel<decltype(np)::value>, grid, blk, 0, s, a); });
     } else {
         ExpectArgs a{};
         a.fw = h->d_fw; a.ops = x.d_ops; a.stride_k = ops_per_traj ? (size_t)M * m2 : 0; a.out = x.d_res;
@@ -5910,8 +5860,6 @@ GRAPE_BARRIER(h ? &h->err : &g_create_error)
 // ---------------------------------------------------------------------------------------
 namespace {
 
-typedef grape_handle::HvpSplit HvpSplit;
-
 // why this handle cannot take a split call (nullptr: it can); every test precedes the first HIP call
 const char *hvp_split_refusal(const grape_handle *h, bool builtin) {
     if (h->open) return "open-system handles are out of scope (DESIGN.md 20)";
@@ -5924,118 +5872,48 @@ const char *hvp_split_refusal(const grape_handle *h, bool builtin) {
     return nullptr;
 }
 
-// the extras of the split calls for nv directions, in a store of their own
-int hvs_reserve(grape_handle *h, int nv) {
-    HvpSplit &x = h->hvs;
-    if (nv <= x.cap) return GRAPE_OK;
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    x.mem.release(); x.cap = 0;
-    const size_t K = (size_t)h->K, NP = (size_t)h->NP, n = (size_t)nv;
-    hipError_t e = x.mem.alloc(&x.d_chi, K * NP);
-    if (e == hipSuccess) e = x.mem.alloc(&x.d_dchi, n * K * NP);
-    if (e == hipSuccess) e = x.mem.alloc(&x.d_ztarget, K * (size_t)h->N);
-    if (e == hipSuccess) e = x.mem.alloc(&x.d_dpsiT, n * K * (size_t)h->N);
-    if (e == hipSuccess) e = x.mem.alloc(&x.d_ftot, (size_t)2);
-    if (e == hipSuccess) e = x.mem.alloc(&x.d_dftot, 2 * n);
-    if (e == hipSuccess) e = x.mem.alloc(&x.d_psums, 2 * n);
-    if (e == hipSuccess) e = hipMemsetAsync(x.d_ztarget, 0, K * (size_t)h->N * 16, h->stream);
-    if (e != hipSuccess) {
-        x.mem.release();
-        (void)hipGetLastError();
-        h->err = std::string("grape_hvp_forward: storage of the split calls: ") + hipGetErrorString(e);
-        return GRAPE_ERR_HIP;
-    }
-    x.cap = nv;
-    return GRAPE_OK;
-}
-
 HvpArgs hvp_split_args(const grape_handle *h) {
-    HvpArgs a{};
-    a.H0f = h->d_H0f; a.Hcf = h->d_Hcf; a.eps = h->d_eps; a.shape = h->d_shape; a.dts = h->d_dts; a.rb = h->d_rb;
-    a.V = h->hvp.d_hvV; a.fw = h->d_fw; a.target = h->no_target ? h->hvs.d_ztarget : h->d_target; a.weights = h->d_weights;
-    a.tau = (const double2 *)h->d_out; a.f = h->hvs.d_ftot;
-    a.dpsi = h->hvp.d_hvdpsi; a.dtau = h->hvp.d_hvdtau; a.dcoef = h->hvp.d_hvdcoef; a.tg = h->hvp.d_hvtg; a.ws = h->hvp.d_hvws;
-    a.flags = (int *)(h->hvp.d_hvstats + 4 * (size_t)h->hvp.store.cap * h->K); a.stats = h->hvp.d_hvstats;
-    a.tol = h->series_tol; a.theta = h->series_theta;
-    a.K = h->K; a.K_total = h->K_total; a.L = h->L; a.N = h->N; a.N_T = h->N_T; a.functional = h->p.functional;
-    a.hc_per_traj = h->p.hc_per_traj;
+    HvpArgs a = hvp_args(h);
+    a.f = h->hvs.d_ftot;   // the all-reduced sum_k w_k tau_k the caller passes
+    if (h->no_target) a.target = h->hvs.d_ztarget;
     return a;
-}
-
-template <int NP>
-void hvp_split_launch_chi(const HvpArgs &a, int nd, int nct, hipStream_t s, const double2 *chi, const double2 *dchi) {
-    const dim3 grid((unsigned)a.K, (unsigned)nd), blk(4 * NP);
-    if (nct == 1) hipLaunchKernelGGL((hvp_backward_chi_kernel<NP, 1>), grid, blk, 0, s, a, chi, dchi);
-    else hipLaunchKernelGGL((hvp_backward_chi_kernel<NP, 2>), grid, blk, 0, s, a, chi, dchi);
-}
-template <int NP>
-void hvp_split_launch_builtin(const HvpArgs &a, int nd, int nct, hipStream_t s) {
-    const dim3 grid((unsigned)a.K, (unsigned)nd), blk(4 * NP);
-    if (nct == 1) hipLaunchKernelGGL((hvp_backward_kernel<NP, 1>), grid, blk, 0, s, a);
-    else hipLaunchKernelGGL((hvp_backward_kernel<NP, 2>), grid, blk, 0, s, a);
-}
-
-// the statistics of one half (which = 0: forward workgroups, 1: backward workgroups) and the flag word
-int hvp_split_stats(grape_handle *h, const HvpArgs &a, int nv, int which, double *terms, double *steps, bool *taylor) {
-    const size_t n = 2 * (size_t)nv * h->K;
-    std::vector<unsigned long long> st(n + 1, 0ull);
-    HIPCHK(h, hipMemcpyAsync(st.data(), a.stats + (size_t)which * n, n * 8, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(&st[n], a.flags, 8, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    *terms = 0.; *steps = 0.;
-    for (size_t q = 0; q < n / 2; ++q) { *terms += (double)st[2 * q]; *steps += (double)st[2 * q + 1]; }
-    *taylor = ((int)(st[n] & 0xffffffffull) & 16) != 0;
-    return GRAPE_OK;
 }
 
 int hvp_split_forward(grape_handle *h, int nv, const double *V, double *dtau, double *dsums, double *dpsiT) {
     const auto t0 = std::chrono::steady_clock::now();
-    HvpSplit &x = h->hvs;
-    HIPCHK(h, hipSetDevice(h->device));
-    if (h->foreign_stream) HIPCHK(h, hipDeviceSynchronize());   // (see grape_get_time_gradient)
-    (void)hipGetLastError();
-    // all nv directions stay resident between the halves: the budget of grape_hvp decides how many that can be
-    int nd = 0;
-    const hipError_t ep = h->hvp.store.plan(nv, hvp_bytes_per_direction(h), 8.0 * 1073741824.0, &nd);
-    if (ep != hipSuccess) { h->err = std::string("hipMemGetInfo(&free_b, &total_b): ") + hipGetErrorString(ep); return GRAPE_ERR_HIP; }
-    if (nd < nv) {
-        h->err = "grape_hvp_forward: nv = " + std::to_string(nv) + " directions do not fit the storage budget of grape_hvp (8 GB, half of the "
-                 "free memory, GRAPE_HVP_DIRS): at most " + std::to_string(nd) + " stay resident between the halves; loop over groups of that size";
-        return GRAPE_ERR_INVALID;
-    }
-    h->ev.split_forward_begun();   // (failed until this half has succeeded: the tangent storage is being overwritten)
-    int rc = hvp_reserve(h, nv, &nd);
-    if (rc) return rc;
-    rc = hvs_reserve(h, nv);
-    if (rc) return rc;
+    SplitExtras<double2> &x = h->hvs;
     const size_t LN = (size_t)h->L * h->N_T, K = (size_t)h->K, N = (size_t)h->N;
+    int rc = second_order_begin(h);
+    if (rc) return rc;
+    rc = split_resident(h, h->hvp.store, nv, hvp_bytes_per_direction(h), "grape_hvp_forward", "grape_hvp");
+    if (rc) return rc;
+    h->ev.split_forward_begun();   // (failed until this half has succeeded: the tangent storage is being overwritten)
+    int nd = 0;
+    rc = hvp_reserve(h, nv, &nd);
+    if (rc) return rc;
+    rc = split_reserve(h, x, nv, K * h->NP, K * N, "grape_hvp_forward");
+    if (rc) return rc;
     hipStream_t s = h->stream;
     const HvpArgs a = hvp_split_args(h);
     HIPCHK(h, hipMemcpyAsync(h->hvp.d_hvV, V, (size_t)nv * LN * 8, hipMemcpyHostToDevice, s));
     HIPCHK(h, hipMemsetAsync(h->hvp.d_hvstats, 0, (4 * (size_t)h->hvp.store.cap * K + 1) * 8, s));
-    {
-        const dim3 grid((unsigned)K, (unsigned)nv);
-        switch (h->NP) {
-            case 16: hipLaunchKernelGGL(hvp_forward_kernel<16>, grid, dim3(64), 0, s, a); break;
-            case 32: hipLaunchKernelGGL(hvp_forward_kernel<32>, grid, dim3(128), 0, s, a); break;
-            case 48: hipLaunchKernelGGL(hvp_forward_kernel<48>, grid, dim3(192), 0, s, a); break;
-            default: hipLaunchKernelGGL(hvp_forward_kernel<64>, grid, dim3(256), 0, s, a); break;
-        }
-    }
+    with_np(h->NP, [&](auto np) {
+        constexpr int NP = decltype(np)::value;
+        hipLaunchKernelGGL(hvp_forward_kernel<NP>, dim3((unsigned)K, (unsigned)nv), dim3(4 * NP), 0, s, a);
+    });
     hipLaunchKernelGGL(hvp_partial_sum_kernel, dim3((unsigned)nv), dim3(64), 0, s, a, x.d_psums);
     HIPCHK(h, hipGetLastError());
     if (dtau) HIPCHK(h, hipMemcpyAsync(dtau, h->hvp.d_hvdtau, (size_t)nv * K * 16, hipMemcpyDeviceToHost, s));
     if (dsums) HIPCHK(h, hipMemcpyAsync(dsums, x.d_psums, (size_t)nv * 16, hipMemcpyDeviceToHost, s));
     if (dpsiT) {   // Psi~'_k(T): row N_T of every (direction, trajectory) block, packed on the device, one copy on this stream
-        hipLaunchKernelGGL(hvp_final_tangent_kernel, dim3((unsigned)((size_t)nv * K)), dim3(64), 0, s, a, h->NP, x.d_dpsiT);
+        hipLaunchKernelGGL(hvp_final_tangent_kernel, dim3((unsigned)((size_t)nv * K)), dim3(64), 0, s, a, h->NP, x.d_dfinal);
         HIPCHK(h, hipGetLastError());
-        HIPCHK(h, hipMemcpyAsync(dpsiT, x.d_dpsiT, (size_t)nv * K * N * 16, hipMemcpyDeviceToHost, s));
+        HIPCHK(h, hipMemcpyAsync(dpsiT, x.d_dfinal, (size_t)nv * K * N * 16, hipMemcpyDeviceToHost, s));
     }
-    double terms = 0., steps = 0.;
-    bool taylor = false;
-    rc = hvp_split_stats(h, a, nv, 0, &terms, &steps, &taylor);
+    WorkStats w;
+    rc = read_stats(h, a.stats, (size_t)nv * K, a.flags, &w);
     if (rc) return rc;
-    if (taylor) { h->err = "grape_hvp_forward: a series did not converge within 200 terms"; return GRAPE_ERR_TAYLOR; }
+    if (w.taylor) { h->err = "grape_hvp_forward: a series did not converge within 200 terms"; return GRAPE_ERR_TAYLOR; }
     if (dpsiT && !h->bal.empty())   // the caller's frame: Psi' = D Psi~'
         for (size_t r = 0; r < (size_t)nv * K; ++r)
             for (size_t i = 0; i < N; ++i) { dpsiT[2 * (r * N + i)] *= h->bal[i]; dpsiT[2 * (r * N + i) + 1] *= h->bal[i]; }
@@ -6044,11 +5922,8 @@ int hvp_split_forward(grape_handle *h, int nv, const double *V, double *dtau, do
         if (dtau) std::fill(dtau, dtau + 2 * (size_t)nv * K, nan);
         if (dsums) std::fill(dsums, dsums + 2 * (size_t)nv, nan);
     }
-    h->ev.split_forward_succeeded(nv, terms, steps);
-    double *info = h->hvp.info;
-    info[0] = terms; info[1] = steps; info[2] = (double)nv; info[3] = (double)(h->hvp.store.mem.bytes() + x.mem.bytes());
-    info[4] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    info[5] = terms; info[6] = 0.;
+    h->ev.split_forward_succeeded(nv, w.terms, w.steps);
+    fill_info(h->hvp.info, w.terms, w.steps, nv, h->hvp.store.mem.bytes() + x.mem.bytes(), t0, w.terms, 0.);
     return GRAPE_OK;
 }
 
@@ -6056,10 +5931,8 @@ int hvp_split_forward(grape_handle *h, int nv, const double *V, double *dtau, do
 int hvp_split_backward(grape_handle *h, const char *call, int nv, const double *f_total, const double *df_total, const double *chi,
                        const double *dchi, double *HV) {
     const auto t0 = std::chrono::steady_clock::now();
-    HvpSplit &x = h->hvs;
-    HIPCHK(h, hipSetDevice(h->device));
-    if (h->foreign_stream) HIPCHK(h, hipDeviceSynchronize());
-    (void)hipGetLastError();
+    SplitExtras<double2> &x = h->hvs;
+    if (const int rc = second_order_begin(h)) return rc;
     const size_t LN = (size_t)h->L * h->N_T, K = (size_t)h->K, N = (size_t)h->N, NP = (size_t)h->NP;
     hipStream_t s = h->stream;
     const HvpArgs a = hvp_split_args(h);
@@ -6080,40 +5953,28 @@ int hvp_split_backward(grape_handle *h, const char *call, int nv, const double *
         }
         HIPCHK(h, hipMemcpyAsync(x.d_chi, x.stage.data(), K * NP * 16, hipMemcpyHostToDevice, s));
         HIPCHK(h, hipMemcpyAsync(x.d_dchi, x.stage.data() + 2 * K * NP, (size_t)nv * K * NP * 16, hipMemcpyHostToDevice, s));
-        switch (h->NP) {
-            case 16: hvp_split_launch_chi<16>(a, nv, nct, s, x.d_chi, x.d_dchi); break;
-            case 32: hvp_split_launch_chi<32>(a, nv, nct, s, x.d_chi, x.d_dchi); break;
-            case 48: hvp_split_launch_chi<48>(a, nv, nct, s, x.d_chi, x.d_dchi); break;
-            default: hvp_split_launch_chi<64>(a, nv, nct, s, x.d_chi, x.d_dchi); break;
-        }
     } else {
         HIPCHK(h, hipMemcpyAsync(x.d_ftot, f_total, 16, hipMemcpyHostToDevice, s));
         HIPCHK(h, hipMemcpyAsync(x.d_dftot, df_total, (size_t)nv * 16, hipMemcpyHostToDevice, s));
         hipLaunchKernelGGL(hvp_coef_total_kernel, dim3((unsigned)nv), dim3(64), 0, s, a, (const double *)x.d_dftot);
-        switch (h->NP) {
-            case 16: hvp_split_launch_builtin<16>(a, nv, nct, s); break;
-            case 32: hvp_split_launch_builtin<32>(a, nv, nct, s); break;
-            case 48: hvp_split_launch_builtin<48>(a, nv, nct, s); break;
-            default: hvp_split_launch_builtin<64>(a, nv, nct, s); break;
-        }
     }
+    with_np(h->NP, [&](auto np) {   // chi == nullptr: the boundary values of the built-in functional
+        constexpr int NP = decltype(np)::value;
+        const dim3 grid((unsigned)K, (unsigned)nv), blk(4 * NP);
+        if (chi && nct == 1) hipLaunchKernelGGL((hvp_backward_chi_kernel<NP, 1>), grid, blk, 0, s, a, x.d_chi, x.d_dchi);
+        else if (chi) hipLaunchKernelGGL((hvp_backward_chi_kernel<NP, 2>), grid, blk, 0, s, a, x.d_chi, x.d_dchi);
+        else if (nct == 1) hipLaunchKernelGGL((hvp_backward_kernel<NP, 1>), grid, blk, 0, s, a);
+        else hipLaunchKernelGGL((hvp_backward_kernel<NP, 2>), grid, blk, 0, s, a);
+    });
     HIPCHK(h, hipGetLastError());
-    // (H v)_j = -2 Re sum_k of the per-trajectory terms: the gradient's reduction, fixed order
-    for (int j = 0; j < nv; ++j)
-        hipLaunchKernelGGL(grad_reduce_kernel, dim3((unsigned)((LN + 15) / 16)), dim3(256), 0, s, h->hvp.d_hvtg + (size_t)j * K * LN, h->K,
-                           (int)LN, h->hvp.d_hvout + (size_t)j * LN, (const double2 *)nullptr);
+    reduce_directions(h, h->hvp.d_hvtg, h->hvp.d_hvout, nv);
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipMemcpyAsync(HV, h->hvp.d_hvout, (size_t)nv * LN * 8, hipMemcpyDeviceToHost, s));
-    double terms = 0., steps = 0.;
-    bool taylor = false;
-    const int rc = hvp_split_stats(h, a, nv, 1, &terms, &steps, &taylor);
-    if (rc) return rc;
-    if (taylor) { h->err = std::string(call) + ": a series did not converge within 200 terms"; return GRAPE_ERR_TAYLOR; }
-    double *info = h->hvp.info;
-    info[0] = h->ev.terms_fw + terms; info[1] = h->ev.steps_fw + steps; info[2] = (double)nv;
-    info[3] = (double)(h->hvp.store.mem.bytes() + x.mem.bytes());
-    info[4] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    info[5] = h->ev.terms_fw; info[6] = terms;
+    WorkStats w;   // (the nv K backward workgroups, behind the forward ones)
+    if (const int rc = read_stats(h, a.stats + 2 * (size_t)nv * K, (size_t)nv * K, a.flags, &w)) return rc;
+    if (w.taylor) { h->err = std::string(call) + ": a series did not converge within 200 terms"; return GRAPE_ERR_TAYLOR; }
+    fill_info(h->hvp.info, h->ev.terms_fw + w.terms, h->ev.steps_fw + w.steps, nv, h->hvp.store.mem.bytes() + x.mem.bytes(), t0, h->ev.terms_fw,
+              w.terms);
     return GRAPE_OK;
 }
 
